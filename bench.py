@@ -20,6 +20,20 @@ all-reduce, RCCL, once at the end of the timed region).  Rank 0 prints ONE JSON 
     eval  configs[3]  YT-All stand-in: 1024 synthetic clips x 9 windows, batches of 16 cut from one global window order and dealt
                       whole to the ranks (spatialaudiogen_amd.evaluate.batch_shard), forward + on-device evaluation_ops per batch,
                       ONE all-reduce of the metric sums at the end; strong scaling (total work fixed); --steps caps the batches per rank
+
+A plain run sets up (autotune included), runs the W warm-up steps, times the K steps and prints the line.  --full adds everything
+else this script measures, after the timed region: the CPU baseline, four more timed regions, the one-in-flight / float-frame /
+H2D-inclusive legs, the roofline of the dominant kernel (with its rocprofv3 --pmc passes), the gradient-exchange timing of a
+multi-rank training run and, for the default configuration, the legs of the other configurations; the --no-* switches take
+pieces out of a --full run again.
+
+--dump-outputs DIR writes what the last timed step computed (rank 0) as DIR/<name>.npy:
+    av, a, avf, eval  output.npy   float32 [batch, 4800, 3]  ambisonic output of the last timed step's batch
+                      metric.npy   float64 [14]              the metric vector the timed region reduced (sum of squares of the outputs,
+                                                             batch, evaluation sums)
+    train             loss.npy, prediction.npy [batch, 4800, 3], and variables_sample.npy / gradients_sample.npy: a fixed seeded
+                      sample of up to 4096 elements of every variable after the last Adam update / of its gradient in the last step
+Inputs and weights are seeded, so the same arguments give the same inputs in every run.
 """
 import argparse
 import json
@@ -97,6 +111,11 @@ def parse():
     ap.add_argument('--steps', type=int, default=30)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--config', choices=sorted(CONFIGS), default='av')
+    ap.add_argument('--full', action='store_true',
+                    help='measure everything beyond the headline as well (CPU baseline, extra timed regions and legs, roofline, the legs of the '
+                         'other configurations: see the module docstring); off: set up, warm up, time the steps, print the line')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last timed step computed to DIR/<name>.npy (see the module docstring)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-extra-legs', action='store_true', help='skip the one-in-flight and H2D-inclusive legs (they run after the timed region)')
     ap.add_argument('--in-flight', type=int, default=DEFAULT_IN_FLIGHT,
@@ -105,7 +124,7 @@ def parse():
                          '2 210 against 2 083-2 131 ambisonic-s/s with two on one box - the fp16x2 kernels leave LDS and registers for a third '
                          "batch's workgroups; four = three)")
     ap.add_argument('--no-other-configs', action='store_true',
-                    help='default run (config av, one GPU): skip the short legs of the other BASELINE configurations (a, avf, eval, train) that '
+                    help='--full run of config av on one GPU: skip the short legs of the other BASELINE configurations (a, avf, eval, train) that '
                          'follow the headline, each a fresh process of this script whose line is attached as `leg_<config>`')
     ap.add_argument('--no-autotune', action='store_true', help='use shape heuristics instead of the timed per-layer plan')
     ap.add_argument('--plan-file', default=None, help='replay this saved launch plan if it exists, else autotune and save it')
@@ -123,7 +142,10 @@ def parse():
     ap.add_argument('--float-frames', action='store_true',
                     help='keep the resident video frames as the float32 the feeder would make of them (x/255 - 0.5) instead of the uint8 the '
                          'JPEG decoder produced: the general float entry point (sagen_forward) in the timed region')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if not args.full:           # a plain run: only what the headline needs
+        args.no_cpu_baseline = args.no_extra_legs = args.no_other_configs = args.no_repeats = args.no_pmc = True
+    return args
 
 
 def cpu_baseline(P, inputs, budget_s, encoders, batch):
@@ -177,7 +199,7 @@ def cpu_baseline_train(P, inputs, target, budget_s, encoders, batch):
 
 
 def other_config_legs(args):
-    """BASELINE configs[0], [2], [3], [4] next to the headline (configs[1]) in the default one-GPU run: each leg is `bench.py --config X`
+    """BASELINE configs[0], [2], [3], [4] next to the headline (configs[1]) in a --full one-GPU run: each leg is `bench.py --full --config X`
     in a fresh process AFTER the headline's timed region and extra legs (nothing of this process is running on the GPU any more), with
     its own warm-up / autotune / timed region under the same contract; its line is reduced to value, ms_per_step, steps and roofline.
     A leg that fails is recorded as such - the headline never depends on it."""
@@ -187,7 +209,7 @@ def other_config_legs(args):
     plan = {'a': (300, 30), 'avf': (40, 6), 'eval': (100, 10), 'train': (14, 3)}
     for name, (steps, warm) in plan.items():
         cmd = [sys.executable, os.path.abspath(__file__), '--gpus', '1', '--config', name, '--steps', str(steps), '--warmup', str(warm),
-               '--no-cpu-baseline', '--no-extra-legs', '--no-other-configs'] + (['--no-autotune'] if args.no_autotune else [])
+               '--full', '--no-cpu-baseline', '--no-extra-legs', '--no-other-configs'] + (['--no-autotune'] if args.no_autotune else [])
         t0 = time.time()
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=420)
@@ -303,10 +325,12 @@ def main_train(args, cfg):
         dist.barrier()
     elapsed = time.perf_counter() - t0
     last_loss = float(loss)
+    if args.dump_outputs and rank == 0:
+        dump_train_outputs(args.dump_outputs, tr, loss)
     ranks = ranks_report(dist, torch, world, backend, elapsed, args.steps)
     assert ranks['ranks_seen'] == world, ranks
     comm = {}
-    if world > 1 and tr.bucket_events is not None:      # one more step with timing events on the communication stream
+    if args.full and world > 1 and tr.bucket_events is not None:      # one more step with timing events on the communication stream
         tr.step(*dev, comm_timing=comm)
     if world > 1:
         t = torch.tensor([elapsed], dtype=torch.float64, device='cuda' if backend != 'gloo' else 'cpu')
@@ -316,62 +340,64 @@ def main_train(args, cfg):
     value = 0.1 * BATCH * world * steps / elapsed
     ms_per_step = 1e3 * elapsed / max(steps, 1)
 
-    # per-launch HIP events of the native runtime over two more steps (forward + backward launches; the optimiser and the
-    # all-reduce are torch-side and appear only in the step time)
-    tr.profile_enable(True)
-    agg, by_phase = {}, {}
-    nprof = 2
-    for _ in range(nprof):
-        tr.forward_backward(*dev)
-        for k, layer, us, fl in tr.profile_report():
-            a = agg.setdefault(k, [0, 0.0, 0.0])
-            a[0] += 1; a[1] += us; a[2] += fl
-            ph = 'wgrad' if layer.startswith('wgrad:') else 'dgrad' if layer.startswith('dgrad:') else \
-                'bwd-elementwise' if (':' in layer.split('/')[0] or layer.endswith(':bwd')) else 'forward'
-            b = by_phase.setdefault(ph, [0.0, 0.0])
-            b[0] += us; b[1] += fl
-    tr.profile_enable(False)
-    total_us = sum(a[1] for a in agg.values())
-    total_fl = sum(a[2] for a in agg.values())
-    dom = max(agg, key=lambda k: agg[k][1])
-    n_l, us_l, fl_l = agg[dom]
-    achieved = fl_l / (us_l * 1e-6) / 1e12
-    h2 = dom.startswith('conv3h') or dom.startswith('wgrad3h') or (dom.startswith('conv3g') and dom.rstrip('>').endswith('true'))
-    b3 = not h2 and (dom.startswith('igemm3') or dom.startswith('conv3p') or dom.startswith('wgrad3') or dom.startswith('conv3g'))
-    peak = PEAK_FP16X2_TFLOPS if h2 else (PEAK_BF16X3_TFLOPS if b3 else PEAK_FP32_MFMA_TFLOPS)
-    traffic, traffic_src = None, None
-    try:     # HBM bytes per launch of the dominant kernel from the committed PMC passes (profiles/)
-        with open(os.path.join(ROOT, 'profiles', 'pmc_traffic_train.json')) as f:
-            traffic = json.load(f).get(dom)
-        if traffic is not None:
-            traffic_src = ('profiles/pmc_traffic_train.json (%s): rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command (FETCH_SIZE x2 per the '
-                           'gfx950 note), launch-weighted mean, NOT measured in this run' % committed_rev('profiles/pmc_traffic_train.json'))
-    except Exception:
-        pass
-    step_tflops = total_fl / nprof / (ms_per_step * 1e-3) / 1e12
-    roofline = {
-        'bound': 'mfma', 'kernel': dom, 'achieved': round(achieved, 2), 'peak': round(peak, 1), 'unit': 'TFLOP/s',
-        'frac': round(achieved / peak, 4), 'traffic': traffic, 'traffic_source': traffic_src,
-        'frac_of_sustained_mfma_rate': round(achieved / SUSTAINED_BF16X3_TFLOPS, 4) if b3 else None, 'sustained_note': SUSTAINED_NOTE if b3 else None,
-        'peak_basis': ('dense fp16 MFMA peak 2500 TF / 3 products per fp32 multiply (fp16x2 planes); algorithmic fp32 FLOPs' if h2 else
-                       'dense bf16 MFMA peak 2500 TF / 6 products per fp32 multiply (bf16x3 kernel); algorithmic fp32 FLOPs'
-                       if b3 else 'fp32 MFMA peak (v_mfma_f32_32x32x2_f32)'),
-        'fp16x2_families_us_per_step': round(sum(a[1] for k, a in agg.items() if k.startswith(('conv3h', 'wgrad3h')) or (k.startswith('conv3g') and k.rstrip('>').endswith('true'))) / nprof, 1),
-        'bf16x3_families_us_per_step': round(sum(a[1] for k, a in agg.items() if k.startswith(('igemm3', 'conv3p', 'wgrad3_', 'wgrad3r')) or (k.startswith('conv3g') and not k.rstrip('>').endswith('true'))) / nprof, 1),
-        'achieved_over_fp32_mfma_peak': round(achieved / PEAK_FP32_MFMA_TFLOPS, 4),
-        'launches_per_step': n_l // nprof, 'avg_launch_us': round(us_l / n_l, 2), 'gflop_per_launch': round(fl_l / n_l / 1e9, 3),
-        'share_of_step_time': round(us_l / total_us, 3),
-        'phases_us_per_step': {k: round(v[0] / nprof, 1) for k, v in sorted(by_phase.items())},
-        'phases_tflops': {k: round(v[1] / (v[0] * 1e-6) / 1e12, 1) for k, v in sorted(by_phase.items()) if v[1] > 0},
-        'whole_step': {'achieved': round(step_tflops, 2), 'frac': round(step_tflops / PEAK_BF16X3_TFLOPS, 4),
-                       'frac_basis': 'all launched fp32-equivalent FLOPs of the step / step time, against the six-product bf16x3 roof (417 TFLOP/s); the '
-                                     "stride-1 3x3 trunk convs (forward, data and weight gradients: 39 of the step's contractions) run on "
-                                     'the three-product fp16x2 kernels, the rest on bf16x3',
-                       'achieved_over_fp32_mfma_peak': round(step_tflops / PEAK_FP32_MFMA_TFLOPS, 4),
-                       'gflop_per_window_launched': round(total_fl / nprof / BATCH / 1e9, 2),
-                       'gflop_per_window_forward_needed_only': cfg['gflop'],
-                       'kernel_time_us_per_step': round(total_us / nprof, 1)},
-    }
+    roofline = None
+    if args.full:
+        # per-launch HIP events of the native runtime over two more steps (forward + backward launches; the optimiser and the
+        # all-reduce are torch-side and appear only in the step time)
+        tr.profile_enable(True)
+        agg, by_phase = {}, {}
+        nprof = 2
+        for _ in range(nprof):
+            tr.forward_backward(*dev)
+            for k, layer, us, fl in tr.profile_report():
+                a = agg.setdefault(k, [0, 0.0, 0.0])
+                a[0] += 1; a[1] += us; a[2] += fl
+                ph = 'wgrad' if layer.startswith('wgrad:') else 'dgrad' if layer.startswith('dgrad:') else \
+                    'bwd-elementwise' if (':' in layer.split('/')[0] or layer.endswith(':bwd')) else 'forward'
+                b = by_phase.setdefault(ph, [0.0, 0.0])
+                b[0] += us; b[1] += fl
+        tr.profile_enable(False)
+        total_us = sum(a[1] for a in agg.values())
+        total_fl = sum(a[2] for a in agg.values())
+        dom = max(agg, key=lambda k: agg[k][1])
+        n_l, us_l, fl_l = agg[dom]
+        achieved = fl_l / (us_l * 1e-6) / 1e12
+        h2 = dom.startswith('conv3h') or dom.startswith('wgrad3h') or (dom.startswith('conv3g') and dom.rstrip('>').endswith('true'))
+        b3 = not h2 and (dom.startswith('igemm3') or dom.startswith('conv3p') or dom.startswith('wgrad3') or dom.startswith('conv3g'))
+        peak = PEAK_FP16X2_TFLOPS if h2 else (PEAK_BF16X3_TFLOPS if b3 else PEAK_FP32_MFMA_TFLOPS)
+        traffic, traffic_src = None, None
+        try:     # HBM bytes per launch of the dominant kernel from the committed PMC passes (profiles/)
+            with open(os.path.join(ROOT, 'profiles', 'pmc_traffic_train.json')) as f:
+                traffic = json.load(f).get(dom)
+            if traffic is not None:
+                traffic_src = ('profiles/pmc_traffic_train.json (%s): rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command (FETCH_SIZE x2 per the '
+                               'gfx950 note), launch-weighted mean, NOT measured in this run' % committed_rev('profiles/pmc_traffic_train.json'))
+        except Exception:
+            pass
+        step_tflops = total_fl / nprof / (ms_per_step * 1e-3) / 1e12
+        roofline = {
+            'bound': 'mfma', 'kernel': dom, 'achieved': round(achieved, 2), 'peak': round(peak, 1), 'unit': 'TFLOP/s',
+            'frac': round(achieved / peak, 4), 'traffic': traffic, 'traffic_source': traffic_src,
+            'frac_of_sustained_mfma_rate': round(achieved / SUSTAINED_BF16X3_TFLOPS, 4) if b3 else None, 'sustained_note': SUSTAINED_NOTE if b3 else None,
+            'peak_basis': ('dense fp16 MFMA peak 2500 TF / 3 products per fp32 multiply (fp16x2 planes); algorithmic fp32 FLOPs' if h2 else
+                           'dense bf16 MFMA peak 2500 TF / 6 products per fp32 multiply (bf16x3 kernel); algorithmic fp32 FLOPs'
+                           if b3 else 'fp32 MFMA peak (v_mfma_f32_32x32x2_f32)'),
+            'fp16x2_families_us_per_step': round(sum(a[1] for k, a in agg.items() if k.startswith(('conv3h', 'wgrad3h')) or (k.startswith('conv3g') and k.rstrip('>').endswith('true'))) / nprof, 1),
+            'bf16x3_families_us_per_step': round(sum(a[1] for k, a in agg.items() if k.startswith(('igemm3', 'conv3p', 'wgrad3_', 'wgrad3r')) or (k.startswith('conv3g') and not k.rstrip('>').endswith('true'))) / nprof, 1),
+            'achieved_over_fp32_mfma_peak': round(achieved / PEAK_FP32_MFMA_TFLOPS, 4),
+            'launches_per_step': n_l // nprof, 'avg_launch_us': round(us_l / n_l, 2), 'gflop_per_launch': round(fl_l / n_l / 1e9, 3),
+            'share_of_step_time': round(us_l / total_us, 3),
+            'phases_us_per_step': {k: round(v[0] / nprof, 1) for k, v in sorted(by_phase.items())},
+            'phases_tflops': {k: round(v[1] / (v[0] * 1e-6) / 1e12, 1) for k, v in sorted(by_phase.items()) if v[1] > 0},
+            'whole_step': {'achieved': round(step_tflops, 2), 'frac': round(step_tflops / PEAK_BF16X3_TFLOPS, 4),
+                           'frac_basis': 'all launched fp32-equivalent FLOPs of the step / step time, against the six-product bf16x3 roof (417 TFLOP/s); the '
+                                         "stride-1 3x3 trunk convs (forward, data and weight gradients: 39 of the step's contractions) run on "
+                                         'the three-product fp16x2 kernels, the rest on bf16x3',
+                           'achieved_over_fp32_mfma_peak': round(step_tflops / PEAK_FP32_MFMA_TFLOPS, 4),
+                           'gflop_per_window_launched': round(total_fl / nprof / BATCH / 1e9, 2),
+                           'gflop_per_window_forward_needed_only': cfg['gflop'],
+                           'kernel_time_us_per_step': round(total_us / nprof, 1)},
+        }
     result = {
         'metric': 'ambisonic seconds trained/sec (0.1 s windows, 224x448 video; one Adam step per batch)',
         'value': round(value, 2), 'unit': 'ambisonic-s/s', 'n_gpus': world, 'steps': steps, 'warmup': args.warmup,
@@ -389,8 +415,9 @@ def main_train(args, cfg):
                    'weights': 'random init (Xavier / BN identity), same replica on every rank', 'last_loss': last_loss},
         'ranks': ranks,
         'gradient_exchange_timing': comm or None,
-        'roofline': roofline,
     }
+    if roofline is not None:
+        result['roofline'] = roofline
     if rank == 0 and world == 1 and not args.no_cpu_baseline:
         cb = cpu_baseline_train(P, inp, target, args.cpu_seconds, ENCODERS, BATCH)
         cb['gpu_over_cpu'] = round(value / cb['value'], 1)
@@ -399,6 +426,36 @@ def main_train(args, cfg):
         print(json.dumps(result), flush=True)
     if world > 1:
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE = 4096          # elements per variable in the training dump's fixed seeded sample
+
+
+def write_dump(out_dir, arrays):
+    """--dump-outputs: one DIR/<name>.npy per array (float32 / float64 as given)."""
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + '.npy'), a)
+
+
+def dump_train_outputs(out_dir, tr, loss):
+    """What the last timed training step computed: its loss and prediction, and a fixed seeded sample (the same indices in every run)
+    of every variable after its Adam update and of every gradient it produced."""
+    import torch
+    torch.cuda.synchronize()
+    rng = np.random.Generator(np.random.PCG64(0))
+    var_s, grad_s = [], []
+    for name, v in tr.variables().items():
+        idx = np.sort(rng.integers(0, v.numel(), size=min(v.numel(), DUMP_SAMPLE)))
+        ix = torch.as_tensor(idx, device=v.device)
+        var_s.append(v.reshape(-1)[ix].cpu().numpy())
+        if name in tr.opt.layout:
+            grad_s.append(tr.grad(name).reshape(-1)[ix].cpu().numpy())
+    write_dump(out_dir, {'loss': np.array([float(loss)], np.float64), 'prediction': tr.pred.cpu().numpy(),
+                         'variables_sample': np.concatenate(var_s).astype(np.float32),
+                         'gradients_sample': np.concatenate(grad_s).astype(np.float32)})
 
 
 def committed_rev(path):
@@ -694,6 +751,13 @@ def main():
     torch.cuda.synchronize()
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        # the last timed step = the last batch of the last call (of the remainder call if there is one)
+        last = tail_out if tail is not None else (outs[(n_calls - 1) % NF] if n_calls else None)
+        dump = {'metric': metric.cpu().numpy()}
+        if last is not None:
+            dump['output'] = last[-BATCH:].cpu().numpy()
+        write_dump(args.dump_outputs, dump)
     ranks = ranks_report(dist, torch, world, backend, elapsed, steps)
     assert ranks['ranks_seen'] == world, ranks
     if world > 1:
@@ -803,67 +867,69 @@ def main():
                                   'note': 'inputs start in pinned host memory (video frames as uint8, normalised on the device): %.1f MB copied per batch on a copy stream into '
                                           'the second of two device buffer sets while the previous batch of the context runs; %d batches in flight, %d steps' % (mb, NF, ks)}
 
-    # ---- roofline of the dominant kernel: per-launch HIP events recorded by the native runtime on the
-    #      launch stream (sagen_profile_*), three extra forwards outside the timed region ----
-    torch.cuda.synchronize()
-    net.profile_enable(BATCH, True)
-    agg = {}
-    nprof = 3
-    for _ in range(nprof):
-        net.inference_ops(*a0, out=outs[0])              # context 0 alone on the current stream: unoverlapped launch times
-        for k, layer, us, fl in net.profile_report(BATCH):
-            a = agg.setdefault(k, [0, 0.0, 0.0])
-            a[0] += 1; a[1] += us; a[2] += fl * G          # (the runtime reports the work of ONE group; a grouped launch carries G)
-    net.profile_enable(BATCH, False)
-    total_us = sum(a[1] for a in agg.values())
-    dom = max((k for k in agg if agg[k][2] > 0), key=lambda k: agg[k][1])        # the dominant CONTRACTION (the path is matrix-bound)
-    n_l, us_l, fl_l = agg[dom]
-    achieved = fl_l / (us_l * 1e-6) / 1e12
-    # the largest HBM-bound kernel family beside it (the plane passes): algorithmic bytes are not tracked per launch, so only its share
-    hbm_dom = max((k for k in agg if agg[k][2] == 0), key=lambda k: agg[k][1], default=None)
-    traffic, traffic_src = None, None
-    if rank == 0 and world == 1 and not args.no_pmc:
-        traffic, traffic_src = pmc_traffic_in_run(args, net, BATCH, dom)
-    if traffic is None:
-      try:   # HBM bytes per launch of the dominant kernel from the committed PMC passes (profiles/)
-        with open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')) as f:
-            traffic = json.load(f).get(dom)
-        if traffic is not None:
-            traffic_src = ('profiles/pmc_traffic.json (%s): rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command (FETCH_SIZE x2 per the '
-                           'gfx950 note), NOT measured in this run' % committed_rev('profiles/pmc_traffic.json'))
-      except Exception:
-        pass
-    step_tflops = cfg['gflop'] * BATCH / (ms_per_step * 1e-3) / 1e3          # throughput-based (steps overlap when NF > 1)
-    def is_h2(k):        # three matrix products per fp32 multiply: fp16x2 planes (conv3h, conv3g<..., true, ...>) / the exact uint8 plane
-        return k.startswith('conv3h') or k.startswith('stem8pool') or (k.startswith('conv3g') and ',true' in k)
+    roofline = None
+    if args.full:
+        # ---- roofline of the dominant kernel: per-launch HIP events recorded by the native runtime on the
+        #      launch stream (sagen_profile_*), three extra forwards outside the timed region ----
+        torch.cuda.synchronize()
+        net.profile_enable(BATCH, True)
+        agg = {}
+        nprof = 3
+        for _ in range(nprof):
+            net.inference_ops(*a0, out=outs[0])              # context 0 alone on the current stream: unoverlapped launch times
+            for k, layer, us, fl in net.profile_report(BATCH):
+                a = agg.setdefault(k, [0, 0.0, 0.0])
+                a[0] += 1; a[1] += us; a[2] += fl * G          # (the runtime reports the work of ONE group; a grouped launch carries G)
+        net.profile_enable(BATCH, False)
+        total_us = sum(a[1] for a in agg.values())
+        dom = max((k for k in agg if agg[k][2] > 0), key=lambda k: agg[k][1])        # the dominant CONTRACTION (the path is matrix-bound)
+        n_l, us_l, fl_l = agg[dom]
+        achieved = fl_l / (us_l * 1e-6) / 1e12
+        # the largest HBM-bound kernel family beside it (the plane passes): algorithmic bytes are not tracked per launch, so only its share
+        hbm_dom = max((k for k in agg if agg[k][2] == 0), key=lambda k: agg[k][1], default=None)
+        traffic, traffic_src = None, None
+        if rank == 0 and world == 1 and not args.no_pmc:
+            traffic, traffic_src = pmc_traffic_in_run(args, net, BATCH, dom)
+        if traffic is None:
+            try:   # HBM bytes per launch of the dominant kernel from the committed PMC passes (profiles/)
+                with open(os.path.join(ROOT, 'profiles', 'pmc_traffic.json')) as f:
+                    traffic = json.load(f).get(dom)
+                if traffic is not None:
+                    traffic_src = ('profiles/pmc_traffic.json (%s): rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command (FETCH_SIZE x2 per the '
+                                   'gfx950 note), NOT measured in this run' % committed_rev('profiles/pmc_traffic.json'))
+            except Exception:
+                pass
+        step_tflops = cfg['gflop'] * BATCH / (ms_per_step * 1e-3) / 1e3          # throughput-based (steps overlap when NF > 1)
+        def is_h2(k):        # three matrix products per fp32 multiply: fp16x2 planes (conv3h, conv3g<..., true, ...>) / the exact uint8 plane
+            return k.startswith('conv3h') or k.startswith('stem8pool') or (k.startswith('conv3g') and ',true' in k)
 
-    def is_b3(k):        # the six-product bf16x3 family
-        return k.startswith('igemm3') or k.startswith('conv3p') or (k.startswith('conv3g') and ',true' not in k)
-    h2, b3 = is_h2(dom), is_b3(dom)
-    peak = PEAK_FP16X2_TFLOPS if h2 else (PEAK_BF16X3_TFLOPS if b3 else PEAK_FP32_MFMA_TFLOPS)
-    b3_us = sum(a[1] for k, a in agg.items() if is_b3(k))
-    h2_us = sum(a[1] for k, a in agg.items() if is_h2(k))
-    f32_us = sum(a[1] for k, a in agg.items() if k.startswith('igemm_kernel'))
-    roofline = {
-        'bound': 'mfma', 'kernel': dom, 'achieved': round(achieved, 2), 'peak': round(peak, 1),
-        'unit': 'TFLOP/s', 'frac': round(achieved / peak, 4), 'traffic': traffic, 'traffic_source': traffic_src,
-        'frac_of_sustained_mfma_rate': round(achieved / (SUSTAINED_BF16X3_TFLOPS * (2.0 if h2 else 1.0)), 4) if (b3 or h2) else None,
-        'sustained_note': (SUSTAINED_NOTE.replace('290 TFLOP/s', '580 TFLOP/s (three products per multiply)') if h2 else SUSTAINED_NOTE) if (b3 or h2) else None,
-        'peak_basis': ('dense fp16 MFMA peak 2500 TF / 3 products per fp32 multiply (fp16x2 planes, conv3h_kernel); algorithmic fp32 FLOPs' if h2 else
-                       'dense bf16 MFMA peak 2500 TF / 6 products per fp32 multiply (bf16x3 kernel); algorithmic fp32 FLOPs'
-                       if b3 else 'fp32 MFMA peak (v_mfma_f32_32x32x2_f32)'),
-        'achieved_over_fp32_mfma_peak': round(achieved / PEAK_FP32_MFMA_TFLOPS, 4),
-        'launches_per_step': round(n_l / nprof / G, 2), 'batches_per_launch': G, 'avg_launch_us': round(us_l / n_l, 2),
-        'gflop_per_launch': round(fl_l / n_l / 1e9, 3),
-        'share_of_step_time': round(us_l / total_us, 3),
-        'largest_hbm_bound_kernel': None if hbm_dom is None else {'kernel': hbm_dom, 'launches_per_step': agg[hbm_dom][0] // nprof,
-                                                                  'us_per_step': round(agg[hbm_dom][1] / nprof, 1), 'share_of_step_time': round(agg[hbm_dom][1] / total_us, 3)},
-        'contraction_time_split': {'fp16x2_kernels_us': round(h2_us / nprof, 1), 'bf16x3_kernels_us': round(b3_us / nprof, 1), 'fp32_mfma_kernels_us': round(f32_us / nprof, 1)},
-        'whole_step': {'achieved': round(step_tflops, 2), 'frac': round(step_tflops / peak, 4),
-                       'achieved_over_fp32_mfma_peak': round(step_tflops / PEAK_FP32_MFMA_TFLOPS, 4),
-                       'gflop_per_window_needed_only': cfg['gflop'],
-                       'kernel_time_us_per_step': round(total_us / nprof / G, 1)},
-    }
+        def is_b3(k):        # the six-product bf16x3 family
+            return k.startswith('igemm3') or k.startswith('conv3p') or (k.startswith('conv3g') and ',true' not in k)
+        h2, b3 = is_h2(dom), is_b3(dom)
+        peak = PEAK_FP16X2_TFLOPS if h2 else (PEAK_BF16X3_TFLOPS if b3 else PEAK_FP32_MFMA_TFLOPS)
+        b3_us = sum(a[1] for k, a in agg.items() if is_b3(k))
+        h2_us = sum(a[1] for k, a in agg.items() if is_h2(k))
+        f32_us = sum(a[1] for k, a in agg.items() if k.startswith('igemm_kernel'))
+        roofline = {
+            'bound': 'mfma', 'kernel': dom, 'achieved': round(achieved, 2), 'peak': round(peak, 1),
+            'unit': 'TFLOP/s', 'frac': round(achieved / peak, 4), 'traffic': traffic, 'traffic_source': traffic_src,
+            'frac_of_sustained_mfma_rate': round(achieved / (SUSTAINED_BF16X3_TFLOPS * (2.0 if h2 else 1.0)), 4) if (b3 or h2) else None,
+            'sustained_note': (SUSTAINED_NOTE.replace('290 TFLOP/s', '580 TFLOP/s (three products per multiply)') if h2 else SUSTAINED_NOTE) if (b3 or h2) else None,
+            'peak_basis': ('dense fp16 MFMA peak 2500 TF / 3 products per fp32 multiply (fp16x2 planes, conv3h_kernel); algorithmic fp32 FLOPs' if h2 else
+                           'dense bf16 MFMA peak 2500 TF / 6 products per fp32 multiply (bf16x3 kernel); algorithmic fp32 FLOPs'
+                           if b3 else 'fp32 MFMA peak (v_mfma_f32_32x32x2_f32)'),
+            'achieved_over_fp32_mfma_peak': round(achieved / PEAK_FP32_MFMA_TFLOPS, 4),
+            'launches_per_step': round(n_l / nprof / G, 2), 'batches_per_launch': G, 'avg_launch_us': round(us_l / n_l, 2),
+            'gflop_per_launch': round(fl_l / n_l / 1e9, 3),
+            'share_of_step_time': round(us_l / total_us, 3),
+            'largest_hbm_bound_kernel': None if hbm_dom is None else {'kernel': hbm_dom, 'launches_per_step': agg[hbm_dom][0] // nprof,
+                                                                      'us_per_step': round(agg[hbm_dom][1] / nprof, 1), 'share_of_step_time': round(agg[hbm_dom][1] / total_us, 3)},
+            'contraction_time_split': {'fp16x2_kernels_us': round(h2_us / nprof, 1), 'bf16x3_kernels_us': round(b3_us / nprof, 1), 'fp32_mfma_kernels_us': round(f32_us / nprof, 1)},
+            'whole_step': {'achieved': round(step_tflops, 2), 'frac': round(step_tflops / peak, 4),
+                           'achieved_over_fp32_mfma_peak': round(step_tflops / PEAK_FP32_MFMA_TFLOPS, 4),
+                           'gflop_per_window_needed_only': cfg['gflop'],
+                           'kernel_time_us_per_step': round(total_us / nprof / G, 1)},
+        }
 
     result = {
         'metric': 'ambisonic seconds generated/sec (0.1 s windows, 224x448 video)',
@@ -891,8 +957,9 @@ def main():
         'ranks': ranks,
         'step_latency_ms_event': {'median': round(float(np.median(step_ms)), 4), 'p10': round(step_ms[len(step_ms) // 10], 4),
                           'p90': round(step_ms[(9 * len(step_ms)) // 10], 4)},
-        'roofline': roofline,
     }
+    if roofline is not None:
+        result['roofline'] = roofline
     result.update(extra)
     if is_eval:
         tot = metric[2:].cpu().numpy().reshape(4, 3) / max(windows, 1)

@@ -6,9 +6,10 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
-from util import ensure_lib
+from util import ensure_lib, rms
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -36,7 +37,7 @@ def _run(args, world=1):
 @pytest.mark.parametrize('config,batch', [('a', 10), ('av', 32), ('avf', 32)])
 def test_bench_configs_emit_the_contract_line(config, batch):
     ensure_lib()
-    r = _run(['--config', config, '--steps', '4'] + FAST)
+    r = _run(['--config', config, '--steps', '4', '--full'] + FAST)
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype',
               'data', 'config', 'roofline', 'one_in_flight', 'h2d_inclusive'):
         assert k in r, k
@@ -76,7 +77,7 @@ def test_bench_train_config_line_and_two_ranks():
     """configs[4]: one Adam step per `step`; the line carries its own roofline (dominant kernel of forward + backward) and phase
     split; two ranks on this GPU (gloo standing in for RCCL) exchange the gradient buckets and print one line."""
     ensure_lib()
-    r = _run(['--config', 'train', '--steps', '3'] + FAST)
+    r = _run(['--config', 'train', '--steps', '3', '--full'] + FAST)
     for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype', 'data', 'config', 'roofline'):
         assert k in r, k
     assert r['config']['name'] == 'train' and r['config']['workload'].startswith('configs[4]') and r['value'] > 0
@@ -84,7 +85,7 @@ def test_bench_train_config_line_and_two_ranks():
     ph = r['roofline']['phases_us_per_step']
     assert ph['wgrad'] > 0 and ph['dgrad'] > 0 and ph['forward'] > 0
     assert r['config']['last_loss'] == r['config']['last_loss']            # not NaN
-    two = _run(['--config', 'train', '--steps', '2'] + FAST, world=2)
+    two = _run(['--config', 'train', '--steps', '2', '--full'] + FAST, world=2)
     assert two['n_gpus'] == 2 and two['value'] > 0 and 'gloo' in two['config']['gradient_exchange']
 
 
@@ -92,7 +93,46 @@ def test_four_ranks_share_one_tuned_plan():
     """--gpus 4 (gloo, four ranks on this GPU) WITH autotune: rank 0 tunes, the plan is broadcast, every rank asserts it runs the
     same kernels (bench.py) - for the headline configuration and for the training step."""
     ensure_lib()
-    r = _run(['--config', 'av', '--steps', '2', '--warmup', '1', '--no-cpu-baseline', '--no-extra-legs', '--in-flight', '1'], world=4)
+    r = _run(['--config', 'av', '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline', '--no-extra-legs', '--in-flight', '1'], world=4)
     assert r['n_gpus'] == 4 and r['value'] > 0 and r['config']['launch_plan'].startswith('autotuned')
-    t = _run(['--config', 'train', '--steps', '2', '--warmup', '1', '--no-cpu-baseline'], world=4)
+    t = _run(['--config', 'train', '--steps', '2', '--warmup', '1', '--full', '--no-cpu-baseline'], world=4)
     assert t['n_gpus'] == 4 and t['value'] > 0 and t['config']['launch_plan'].startswith('autotuned')
+
+
+# what a --full run adds to the line (a plain run carries none of it)
+FULL_ONLY = ('roofline', 'cpu_baseline', 'headline_repeats', 'one_in_flight', 'float_frames', 'h2d_inclusive')
+
+
+def test_plain_run_is_lean_and_dumps_the_last_step(tmp_path):
+    """Without --full a run sets up, warms up, times its steps and prints the line; --dump-outputs writes what the last timed step
+    computed, and the same arguments give the same outputs in a second process."""
+    ensure_lib()
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ('run%d' % i)
+        r = _run(['--config', 'av', '--steps', '6', '--warmup', '2', '--no-autotune', '--dump-outputs', str(d)])
+        for k in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+            assert k in r, k
+        assert r['steps'] == 6 and r['value'] > 0 and r['ms_per_step'] > 0
+        assert not [k for k in r if k in FULL_ONLY or k.startswith('leg_')], sorted(r)
+        out, metric = np.load(str(d / 'output.npy')), np.load(str(d / 'metric.npy'))
+        assert out.dtype == np.float32 and out.shape == (32, 4800, 3) and np.isfinite(out).all() and rms(out) > 0
+        assert metric.dtype == np.float64 and metric.shape == (14,) and metric[1] == 32 and metric[0] > 0
+        dumps.append((out, metric))
+    assert np.array_equal(dumps[0][0], dumps[1][0])
+    assert np.array_equal(dumps[0][1], dumps[1][1])
+
+
+def test_plain_train_run_dumps_the_last_step(tmp_path):
+    """--config train --dump-outputs: the loss of the last timed step (the one the line reports), its prediction and a fixed sample of
+    the updated variables and of the gradients."""
+    ensure_lib()
+    r = _run(['--config', 'train', '--steps', '2', '--warmup', '1', '--no-autotune', '--dump-outputs', str(tmp_path)])
+    assert r['steps'] == 2 and r['ms_per_step'] > 0 and not [k for k in r if k in FULL_ONLY], sorted(r)
+    loss = np.load(str(tmp_path / 'loss.npy'))
+    assert loss.dtype == np.float64 and loss.shape == (1,) and loss[0] == r['config']['last_loss']
+    pred = np.load(str(tmp_path / 'prediction.npy'))
+    assert pred.dtype == np.float32 and pred.shape == (32, 4800, 3) and np.isfinite(pred).all()
+    v, g = np.load(str(tmp_path / 'variables_sample.npy')), np.load(str(tmp_path / 'gradients_sample.npy'))
+    assert v.dtype == np.float32 and g.dtype == np.float32 and 0 < g.size <= v.size
+    assert np.isfinite(v).all() and np.isfinite(g).all() and rms(g) > 0

@@ -125,3 +125,34 @@ def test_bench_picks_a_group_size_that_divides_the_timed_steps():
     for k in range(1, 64):
         g = b.pick_group(k, 0)
         assert 1 <= g <= min(k, 16)
+
+
+def _bench_module():
+    import importlib.util
+    spec = importlib.util.spec_from_file_location('bench_mod', os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'bench.py'))
+    b = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(b)
+    return b
+
+
+def test_bench_plain_run_leaves_the_extras_to_full(monkeypatch):
+    """bench.py without --full: --steps is the number of timed steps and every extra measurement is off; --full turns them back on
+    and the --no-* switches still take single pieces out of it."""
+    import sys
+    b = _bench_module()
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--gpus', '1', '--steps', '7', '--warmup', '2'])
+    a = b.parse()
+    assert a.steps == 7 and a.warmup == 2 and not a.full and a.dump_outputs is None
+    assert a.no_cpu_baseline and a.no_extra_legs and a.no_other_configs and a.no_repeats and a.no_pmc
+    monkeypatch.setattr(sys, 'argv', ['bench.py', '--full', '--no-pmc', '--dump-outputs', 'out'])
+    a = b.parse()
+    assert a.full and a.dump_outputs == 'out' and a.no_pmc
+    assert not (a.no_cpu_baseline or a.no_extra_legs or a.no_other_configs or a.no_repeats)
+
+
+def test_bench_dump_writes_float_arrays(tmp_path):
+    b = _bench_module()
+    b.write_dump(str(tmp_path / 'd'), {'output': np.ones((2, 3), np.float32), 'metric': np.arange(4, dtype=np.float64)})
+    assert sorted(os.listdir(str(tmp_path / 'd'))) == ['metric.npy', 'output.npy']
+    assert np.load(str(tmp_path / 'd' / 'output.npy')).dtype == np.float32
+    assert np.array_equal(np.load(str(tmp_path / 'd' / 'metric.npy')), np.arange(4.0))

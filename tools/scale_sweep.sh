@@ -19,7 +19,7 @@ for N in 1 2 4 8; do
         python bench.py --gpus 1 --steps "$STEPS" --warmup "$WARM" --config "$CFG" --plan-file "$PLAN" --no-cpu-baseline | tail -1 >> "$OUT"
     else
         python -m torch.distributed.run --nnodes=1 --nproc-per-node "$N" --master-addr 127.0.0.1 --master-port $((29600 + N)) \
-            bench.py --gpus "$N" --steps "$STEPS" --warmup "$WARM" --config "$CFG" --plan-file "$PLAN" | tail -1 >> "$OUT"
+            bench.py --gpus "$N" --steps "$STEPS" --warmup "$WARM" --config "$CFG" --plan-file "$PLAN" --full | tail -1 >> "$OUT"
     fi
 done
 python - "$OUT" <<'PY'

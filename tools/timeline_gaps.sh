@@ -3,7 +3,7 @@
 cd /tmp && export TMPDIR=/tmp
 R=$GRAFT_REPO_ROOT; O=$R/gpurun_out/timeline; rm -rf $O; mkdir -p $O
 python $R/bench.py --no-cpu-baseline --steps 2 --warmup 1 --plan-file $O/plan.json > $O/tune.log 2>&1
-rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python $R/bench.py --no-cpu-baseline --plan-file $O/plan.json --steps 20 --warmup 5 > $O/trace.log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $O/trace -- python $R/bench.py --full --no-cpu-baseline --plan-file $O/plan.json --steps 20 --warmup 5 > $O/trace.log 2>&1
 python3 - <<PY
 import csv, glob
 f = glob.glob('$O/trace/*/*_kernel_trace.csv')[0]
