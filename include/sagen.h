@@ -58,7 +58,7 @@ typedef struct {
     int32_t num_sep_tracks;   /* params.sep_num_tracks (32) */
     int32_t n_loc_units;      /* len(params.loc_fc_units) (2) */
     int32_t loc_units[4];     /* params.loc_fc_units ([512,512]) */
-    int32_t ambi_order;       /* 1 */
+    int32_t ambi_order;       /* 1 or 2 (model.py:242-243: num_in = order^2 input channels, num_out = 2*order+1 predicted) */
     int32_t audio_rate;       /* 48000 */
     int32_t video_rate;       /* 10 */
     float   context;          /* 1.0 s */
@@ -88,7 +88,13 @@ const char* sagen_source_digest(void);
 const char* sagen_last_error(void);
 
 /* ---- model-level: replaces SptAudioGen.inference_ops (model.py:356-434), as called at
- *      deploy.py:77,141 / eval.py:90,145 ------------------------------------------------- */
+ *      deploy.py:77,141 / eval.py:90,145 -------------------------------------------------
+ * ambi_order 1 (num_in = 1, num_out = 3) or 2 (num_in = 4, num_out = 5; train.py:28,109-111, eval.py:69-70,96): at order 2 the
+ * first-order W,Y,Z,X recording goes in and the five second-order channels (ACN 4..8) come out.  Order 2 changes, per window:
+ * audio_encoder/conv1/weights [7,16,4,32] (one STFT magnitude channel per input channel, channels last: model.py:174);
+ * separation/deconv1 [7,16,4*nsep,64] (channel i*nsep + j = track j of input channel i: model.py:326-327); the last localisation FC
+ * num_out*num_in*(nsep+1) = 20*(nsep+1) outputs read as [B,3,5,4,nsep+1] (model.py:253-258).  Order 3 and above:
+ * SAGEN_ERR_UNSUPPORTED.  Order 2 runs inference only (sagen_train_bind refuses it). */
 int    sagen_create(sagen_ctx** out, const sagen_config* cfg);
 void   sagen_destroy(sagen_ctx* ctx);
 /* bytes of scratch the caller must provide (activations + packed weights); fixed per ctx */
@@ -103,7 +109,12 @@ int    sagen_variable_spec(const sagen_ctx* ctx, int i, const char** name, int32
 int    sagen_bind_weights(sagen_ctx* ctx, const sagen_tensor* tensors, int n,
                           void* workspace, size_t workspace_bytes, void* stream);
 /* audio [B, snd_size] (=[B,52799,1]); video/flow [B,224,448,3] (=[B,1,224,448,3]) or NULL;
- * ambi_yzx [B, snd_dur, 3] (channels Y,Z,X = ACN 1,2,3). */
+ * ambi_yzx [B, snd_dur, 3] (channels Y,Z,X = ACN 1,2,3).
+ * ambi_order 2: audio [B, snd_size, 4] = W,Y,Z,X interleaved (the feeder's ambix[:, :, :4], eval.py:69); output [B, snd_dur, 5]
+ * (ACN 4..8): out[b,n,o] = sum_i sum_j w[b,s(n),o,i,j] sep[b,i,j,n] + bias[b,s(n),o, input channel 0] (model.py:428-430 reads the
+ * biases of channel 0 only).  Separation 'none' (model.py:274-280): the reference's decoder product broadcasts the four audio
+ * channels against the one track, so out[b,n,o] = (sum_i w[b,s,o,i,0]) * (sum_c audio[b, snd_contx/2 + n, c]) + w[b,s,o,0,1].
+ * The same holds for the _u8 and grouped entries below. */
 int    sagen_forward(sagen_ctx* ctx, const float* audio, const float* video, const float* flow,
                      float* ambi_yzx, void* stream);
 /* The same with the video frames as they come out of the JPEG decoder: uint8 [B,224,448,3]; the reference's pixel normalisation
@@ -132,7 +143,9 @@ int    sagen_assemble_wyzx(const float* audio, const float* ambi_yzx, float* out
                            int batch, int snd_size, int snd_contx, int snd_dur, void* stream);
 /* named intermediate of the last forward (device pointer inside the workspace) for parity tests:
  * "mag", "stft", "audio_encoder/conv1".."conv5", "<enc>_encoder/conv5_2", "bottleneck",
- * "localization/coeffs", "separation/deconv1" (needed rows only). Returns dims in shape[4]. */
+ * "localization/coeffs", "separation/deconv1" (needed rows only). Returns dims in shape[4].
+ * With num_in input channels: "mag" [B,127,1024,num_in]; "stft" [B, num_in*28, 513, 2] (= [B,num_in,28,513,2]);
+ * "localization/coeffs" [B, 3, num_out*num_in, nsep+1] (= [B,3,num_out,num_in,nsep+1]); "separation/deconv1" [B,23,1024,num_in*nsep]. */
 int    sagen_get_intermediate(const sagen_ctx* ctx, const char* name, const float** data,
                               int32_t* ndim, int64_t shape[4], int64_t* pixel_stride);
 
@@ -229,6 +242,16 @@ int sagen_deconv2d(const float* x, int batch, int h, int w, int cin,
 size_t sagen_mask_istft_mix_scratch_bytes(int batch);
 int sagen_mask_istft_mix(const float* dmask, const float* spec, const float* coeffs, int batch,
                          int ntracks, float* ambi_yzx, void* scratch, size_t scratch_bytes, void* stream);
+/* The same tail for nin input and nout output channels (ambi_order 2: nin = 4, nout = 5, the only pair implemented;
+ * model.py:326-347, 428-430):
+ * dmask  [B, 28, 1024, nin*ntracks] : deconv1 output rows 43:71 (pre-sigmoid); channel i*ntracks + j = track j of input channel i
+ * spec   [B, nin, 28, 513, 2]       : STFT frames 89:117 of each input channel
+ * coeffs [B, 3, nout, nin, ntracks+1]
+ * out    [B, 4800, nout] = sum_i sum_j w[s,o,i,j] istft(sigmoid(m_ij) X_i) + coeffs[b,s,o,0,ntracks] (the bias of input channel 0).
+ * scratch >= sagen_mask_istft_mix_hoa_scratch_bytes(batch, nout). */
+size_t sagen_mask_istft_mix_hoa_scratch_bytes(int batch, int nout);
+int sagen_mask_istft_mix_hoa(const float* dmask, const float* spec, const float* coeffs, int batch, int ntracks, int nin, int nout,
+                             float* out, void* scratch, size_t scratch_bytes, void* stream);
 
 /* SptAudioGen.evaluation_ops (model.py:110-154) for 0.1 s windows at 48 kHz, first-order (3 predicted channels):
  * per_sample [4][B][3] = stft distance (model.py:62-76; before the x100 and channel masking of :122-127), log-spectral
@@ -239,6 +262,12 @@ size_t sagen_eval_scratch_bytes(int batch);
 int sagen_eval_init(void* scratch, size_t scratch_bytes, int batch, void* stream);
 int sagen_eval_metrics(const float* pred_yzx, const float* target_yzx, int batch, float* per_sample,
                        double* power_sums, void* scratch, size_t scratch_bytes, void* stream);
+/* The same metrics for `channels` predicted channels (ambi_order 2: 5, ACN 4..8): pred / target [B][4800][channels],
+ * per_sample [4][B][channels]; power_sums as above (-> /(channels*B)).  scratch: >= sagen_eval_scratch_bytes_c(batch, channels)
+ * bytes, initialised once with sagen_eval_init.  channels = 3 computes exactly what sagen_eval_metrics computes. */
+size_t sagen_eval_scratch_bytes_c(int batch, int channels);
+int sagen_eval_metrics_c(const float* pred, const float* target, int batch, int channels, float* per_sample,
+                         double* power_sums, void* scratch, size_t scratch_bytes, void* stream);
 
 /* AmbiDecoder.decode('projection') + RMS map (pyutils/ambisonics/decoder.py:24-28,
  * distance.py:41-52; SH matrix common.py:151-178, order 1 ACN/SN3D):
@@ -276,6 +305,7 @@ int sagen_adam_update(float* params, const float* grads, float* m, float* v, int
  *  - sagen_train_step: target_yzx [B,4800,3], mask [B,3] or NULL, pred_yzx [B,4800,3] or NULL (the prediction of this step),
  *    loss: device pointer to one fp64 or NULL.  Asynchronous on `stream`; gradients are complete when the stream reaches the end
  *    of the call's work.  Weight gradients are reduced in a fixed order (bit-reproducible). */
+/* The training step implements ambi_order 1: sagen_train_bind refuses a context of another order (SAGEN_ERR_UNSUPPORTED). */
 size_t sagen_train_workspace_bytes(sagen_ctx* ctx);
 int sagen_train_bind(sagen_ctx* ctx, const sagen_tensor* grads, int n_grads, const sagen_tensor* moving, int n_moving,
                      void* train_workspace, size_t train_workspace_bytes, void* stream);

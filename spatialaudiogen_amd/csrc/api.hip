@@ -370,12 +370,43 @@ int sagen_mask_istft_mix(const float* dmask, const float* spec, const float* coe
                                  (hipStream_t)stream);
 }
 
+size_t sagen_mask_istft_mix_hoa_scratch_bytes(int batch, int nout) {
+    return batch > 0 && nout > 0 ? mask_istft_hoa_scratch_bytes(batch, nout) : 0;
+}
+int sagen_mask_istft_mix_hoa(const float* dmask, const float* spec, const float* coeffs, int batch, int ntracks, int nin, int nout,
+                             float* out, void* scratch, size_t scratch_bytes, void* stream) {
+    return guarded([&]() -> int {
+        if (!dmask || !spec || !coeffs || !out || !scratch) return fail(SAGEN_ERR_NULL, "sagen_mask_istft_mix_hoa: null argument");
+        if (batch <= 0) return fail(SAGEN_ERR_SHAPE, "sagen_mask_istft_mix_hoa: batch=%d", batch);
+        if (nin != 4 || nout != 5)
+            return fail(SAGEN_ERR_UNSUPPORTED, "sagen_mask_istft_mix_hoa: (nin, nout) = (%d, %d) (supported: (4, 5), ambi_order 2)", nin, nout);
+        if (scratch_bytes < mask_istft_hoa_scratch_bytes(batch, nout)) return fail(SAGEN_ERR_WORKSPACE, "sagen_mask_istft_mix_hoa: scratch too small");
+        return mask_istft_hoa_launch(dmask, 28L * 1024 * nin * ntracks, 0, spec, coeffs, batch, ntracks, nin, nout, out, (float*)scratch,
+                                     (hipStream_t)stream);
+    });
+}
+
 size_t sagen_eval_scratch_bytes(int batch) { return batch > 0 ? eval_scratch_floats(batch) * sizeof(float) : 0; }
 
 int sagen_eval_init(void* scratch, size_t scratch_bytes, int batch, void* stream) {
     if (!scratch) return fail(SAGEN_ERR_NULL, "sagen_eval_init: null scratch");
     if (batch <= 0 || scratch_bytes < sagen_eval_scratch_bytes(batch)) return fail(SAGEN_ERR_WORKSPACE, "sagen_eval_init: scratch too small");
     return eval_init_launch((float*)scratch, (hipStream_t)stream);
+}
+
+size_t sagen_eval_scratch_bytes_c(int batch, int channels) {
+    return batch > 0 && channels > 0 ? eval_scratch_floats_c(batch, channels) * sizeof(float) : 0;
+}
+int sagen_eval_metrics_c(const float* pred, const float* target, int batch, int channels, float* per_sample, double* power_sums,
+                         void* scratch, size_t scratch_bytes, void* stream) {
+    return guarded([&]() -> int {
+        if (!pred || !target || !per_sample || !power_sums || !scratch) return fail(SAGEN_ERR_NULL, "sagen_eval_metrics_c: null argument");
+        if (channels <= 0 || channels > 64) return fail(SAGEN_ERR_SHAPE, "sagen_eval_metrics_c: channels=%d", channels);
+        if (batch <= 0 || scratch_bytes < sagen_eval_scratch_bytes_c(batch, channels))
+            return fail(SAGEN_ERR_WORKSPACE, "sagen_eval_metrics_c: scratch too small");
+        if (((uintptr_t)power_sums) % 8) return fail(SAGEN_ERR_SHAPE, "sagen_eval_metrics_c: power_sums must be 8-byte aligned");
+        return eval_metrics_c_launch(pred, target, batch, channels, per_sample, power_sums, (float*)scratch, (hipStream_t)stream);
+    });
 }
 
 int sagen_eval_metrics(const float* pred_yzx, const float* target_yzx, int batch, float* per_sample, double* power_sums,

@@ -258,6 +258,38 @@ int nosep_mix_launch(const float* audio, const float* coeffs, float* out, int B,
     return SAGEN_OK;
 }
 
+// 'none' separation at NIN > 1 input channels (model.py:274-280, 428-430): x_sep = mono[:, :, ss:ss+dur] gets a new axis 1, i.e.
+// [B, 1 track, NIN, dur], and after the transpose of model.py:421 the decoder's product broadcasts the NIN audio channels against
+// the ONE track axis of the weights [B, dur, NOUT, NIN, 1]:  out[b,n,o] = (sum_i w[b,s,o,i,0]) * (sum_c audio[b,ss+n,c]) + w[b,s,o,0,1].
+// coeffs [B, 3, NOUT, NIN, 2]; audio [B, snd_size, NIN] interleaved.
+__global__ __launch_bounds__(256) void nosep_mix_multi_kernel(const float* __restrict__ audio, const float* __restrict__ coeffs,
+                                                              float* __restrict__ out, int B, int snd_size, int ss, int snd_dur,
+                                                              int nin, int num_out) {
+    const long total = (long)B * snd_dur * num_out;
+    const int step_len = snd_dur / 3;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const int o = (int)(idx % num_out);
+        const long p = idx / num_out;
+        const int n = (int)(p % snd_dur);
+        const int b = (int)(p / snd_dur);
+        const float* cf = coeffs + (((long)b * 3 + n / step_len) * num_out + o) * nin * 2;
+        const float* a = audio + ((long)b * snd_size + ss + n) * nin;
+        float ws = 0.f, as = 0.f;
+        for (int i = 0; i < nin; ++i) { ws += cf[2 * i]; as += a[i]; }
+        out[idx] = fmaf(ws, as, cf[1]);
+    }
+}
+
+int nosep_mix_multi_launch(const float* audio, const float* coeffs, float* out, int B, int snd_size, int snd_contx,
+                           int snd_dur, int nin, int num_out, hipStream_t s) {
+    if (cur_group().G > 1) return fail(SAGEN_ERR_UNSUPPORTED, "%s: no grouped launch (common.h: GroupInfo)", __func__);
+    const long total = (long)B * snd_dur * num_out;
+    hipLaunchKernelGGL(nosep_mix_multi_kernel, dim3(cdiv(total, 256)), dim3(256), 0, s, audio, coeffs, out, B, snd_size,
+                       snd_contx / 2, snd_dur, nin, num_out);
+    SAGEN_LAUNCH_CHECK();
+    return SAGEN_OK;
+}
+
 // Ambisonic power map (decoder.py:24-28 'projection', distance.py:41-52):
 // rms[p] = sqrt(mean_t (sum_c ambi[t,c] * sh[p,c])^2).  Expanded as the 4x4 second-moment matrix
 // S = sum_t ambi^T ambi (one wavefront-reduced pass over the audio, DPP/shuffle tree), then

@@ -29,16 +29,16 @@ __global__ __launch_bounds__(256) void eval_dft_matrix_kernel(float* __restrict_
     wp[idx] = part == 0 ? (float)c : (float)(-s);
 }
 
-// time-domain metrics: one 256-thread workgroup per (b, c).  ps = [4][B][3]: stft, lsd (filled later), mse, snr;
+// time-domain metrics: one 256-thread workgroup per (b, c).  ps = [4][B][C]: stft, lsd (filled later), mse, snr;
 // pw[2] += per-sample power sums (atomics)
 __global__ __launch_bounds__(256) void eval_time_kernel(const float* __restrict__ pred, const float* __restrict__ gt, int B,
-                                                        float* __restrict__ ps, double* __restrict__ pw) {
-    const int b = blockIdx.x / EV_C, c = blockIdx.x % EV_C;
-    const float* p = pred + (long)b * EV_N * EV_C + c;
-    const float* g = gt + (long)b * EV_N * EV_C + c;
+                                                        int C, float* __restrict__ ps, double* __restrict__ pw) {
+    const int b = blockIdx.x / C, c = blockIdx.x % C;
+    const float* p = pred + (long)b * EV_N * C + c;
+    const float* g = gt + (long)b * EV_N * C + c;
     float acc[5] = {0.f, 0.f, 0.f, 0.f, 0.f};      // sum d^2, sum g^2, sum p^2, sum_w (hann d)^2 (3 windows), unused
     for (int n = threadIdx.x; n < EV_N; n += 256) {
-        const float pv = p[(long)n * EV_C], gv = g[(long)n * EV_C];
+        const float pv = p[(long)n * C], gv = g[(long)n * C];
         const float d = gv - pv;
         acc[0] += d * d; acc[1] += gv * gv; acc[2] += pv * pv;
         // stft_for_loss windows: [0,2048), [2048,4096) (overlap 0) and [1024,3072) (overlap 1)  (myutils.py:166-172)
@@ -64,34 +64,34 @@ __global__ __launch_bounds__(256) void eval_time_kernel(const float* __restrict_
     if (threadIdx.x == 0) {
         float s[4];
         for (int k = 0; k < 4; ++k) s[k] = red[0][k] + red[1][k] + red[2][k] + red[3][k];
-        const int o = b * EV_C + c;
-        ps[0 * B * EV_C + o] = s[3] / 3.f;                                            // mean over the 3 windows of mean_f |X|^2
-        ps[2 * B * EV_C + o] = s[0] / (float)EV_N;                                    // temporal mse
-        ps[3 * B * EV_C + o] = 10.f * logf((s[1] + 1e-1f) / (s[0] + 1e-1f)) / logf(10.f);   // snr
+        const int o = b * C + c;
+        ps[0 * B * C + o] = s[3] / 3.f;                                            // mean over the 3 windows of mean_f |X|^2
+        ps[2 * B * C + o] = s[0] / (float)EV_N;                                    // temporal mse
+        ps[3 * B * C + o] = 10.f * logf((s[1] + 1e-1f) / (s[0] + 1e-1f)) / logf(10.f);   // snr
         atomicAdd(&pw[0], (double)s[2]);
         atomicAdd(&pw[1], (double)s[1]);
     }
 }
 
-// rows r = ((src*B + b)*3 + c)*6 + t, src 0 = gt, 1 = pred: frame t of channel c, periodic Hann(1200) in float32
+// rows r = ((src*B + b)*C + c)*6 + t, src 0 = gt, 1 = pred: frame t of channel c, periodic Hann(1200) in float32
 __global__ __launch_bounds__(256) void eval_lsd_frames_kernel(const float* __restrict__ pred, const float* __restrict__ gt, int B,
-                                                              float* __restrict__ frames) {
+                                                              int C, float* __restrict__ frames) {
     const int r = blockIdx.x;
-    const int t = r % LSD_T, c = (r / LSD_T) % EV_C, b = (r / (LSD_T * EV_C)) % B, src = r / (LSD_T * EV_C * B);
-    const float* x = (src ? pred : gt) + (long)b * EV_N * EV_C + c;
+    const int t = r % LSD_T, c = (r / LSD_T) % C, b = (r / (LSD_T * C)) % B, src = r / (LSD_T * C * B);
+    const float* x = (src ? pred : gt) + (long)b * EV_N * C + c;
     for (int n = threadIdx.x; n < LSD_W; n += 256) {
         const float h = (float)(0.5 - 0.5 * cospi(2.0 * (double)n / (double)LSD_W));
-        frames[(long)r * LSD_W + n] = x[(long)(t * LSD_HOP + n) * EV_C] * h;
+        frames[(long)r * LSD_W + n] = x[(long)(t * LSD_HOP + n) * C] * h;
     }
 }
 
 // spec [2*B*18][1202] (re | im).  lsd[b,c] = mean_t sqrt(mean_f (P_gt - P_pred)^2), P = 10 log10(|X| + 0.01)
-__global__ __launch_bounds__(256) void eval_lsd_reduce_kernel(const float* __restrict__ spec, int B, float* __restrict__ ps) {
-    const int b = blockIdx.x / EV_C, c = blockIdx.x % EV_C;
+__global__ __launch_bounds__(256) void eval_lsd_reduce_kernel(const float* __restrict__ spec, int B, int C, float* __restrict__ ps) {
+    const int b = blockIdx.x / C, c = blockIdx.x % C;
     __shared__ float red[4];
     float lsd = 0.f;
     for (int t = 0; t < LSD_T; ++t) {
-        const long rg = (((long)0 * B + b) * EV_C + c) * LSD_T + t, rp = (((long)1 * B + b) * EV_C + c) * LSD_T + t;
+        const long rg = (((long)0 * B + b) * C + c) * LSD_T + t, rp = (((long)1 * B + b) * C + c) * LSD_T + t;
         const float* sg = spec + rg * (2 * LSD_BINS);
         const float* sp = spec + rp * (2 * LSD_BINS);
         float acc = 0.f;
@@ -107,13 +107,14 @@ __global__ __launch_bounds__(256) void eval_lsd_reduce_kernel(const float* __res
         if (threadIdx.x == 0) lsd += sqrtf((red[0] + red[1] + red[2] + red[3]) / (float)LSD_W);
         __syncthreads();
     }
-    if (threadIdx.x == 0) ps[1 * B * EV_C + b * EV_C + c] = lsd / (float)LSD_T;
+    if (threadIdx.x == 0) ps[1 * B * C + b * C + c] = lsd / (float)LSD_T;
 }
 
 // scratch layout (floats): [DFT matrix 1202*1200][frames 2*B*18*1200][spec 2*B*18*1202][pw: 2 doubles]
-size_t eval_scratch_floats(int B) {
-    return (size_t)2 * LSD_BINS * LSD_W + (size_t)2 * B * EV_C * LSD_T * LSD_W + (size_t)2 * B * EV_C * LSD_T * 2 * LSD_BINS + 16;
+size_t eval_scratch_floats_c(int B, int C) {
+    return (size_t)2 * LSD_BINS * LSD_W + (size_t)2 * B * C * LSD_T * LSD_W + (size_t)2 * B * C * LSD_T * 2 * LSD_BINS + 16;
 }
+size_t eval_scratch_floats(int B) { return eval_scratch_floats_c(B, EV_C); }
 
 int eval_init_launch(float* scratch, hipStream_t s) {
     const long total = 2L * LSD_BINS * LSD_W;
@@ -122,15 +123,16 @@ int eval_init_launch(float* scratch, hipStream_t s) {
     return SAGEN_OK;
 }
 
-int eval_metrics_launch(const float* pred, const float* gt, int B, float* ps, double* pw, float* scratch, hipStream_t s) {
+// C predicted channels (the first-order entry: C = EV_C = 3; second order: 5, ACN 4..8)
+int eval_metrics_c_launch(const float* pred, const float* gt, int B, int C, float* ps, double* pw, float* scratch, hipStream_t s) {
     float* wp = scratch;
     float* frames = wp + (size_t)2 * LSD_BINS * LSD_W;
-    float* spec = frames + (size_t)2 * B * EV_C * LSD_T * LSD_W;
+    float* spec = frames + (size_t)2 * B * C * LSD_T * LSD_W;
     SAGEN_HIP_CHECK(hipMemsetAsync(pw, 0, 2 * sizeof(double), s));
-    hipLaunchKernelGGL(eval_time_kernel, dim3(B * EV_C), dim3(256), 0, s, pred, gt, B, ps, pw);
+    hipLaunchKernelGGL(eval_time_kernel, dim3(B * C), dim3(256), 0, s, pred, gt, B, C, ps, pw);
     SAGEN_LAUNCH_CHECK();
-    const int rows = 2 * B * EV_C * LSD_T;
-    hipLaunchKernelGGL(eval_lsd_frames_kernel, dim3(rows), dim3(256), 0, s, pred, gt, B, frames);
+    const int rows = 2 * B * C * LSD_T;
+    hipLaunchKernelGGL(eval_lsd_frames_kernel, dim3(rows), dim3(256), 0, s, pred, gt, B, C, frames);
     SAGEN_LAUNCH_CHECK();
     IgemmDesc d;                                   // spec[rows, 1202] = frames[rows, 1200] x DFT
     d.x = frames; d.w = wp; d.y = spec;
@@ -138,9 +140,13 @@ int eval_metrics_launch(const float* pred, const float* gt, int B, float* ps, do
     d.Cout = d.N; d.ldy = d.N; d.y_rstride = d.N; d.y_bstride = d.N;
     int rc = igemm_launch(d, TILE_AUTO, s);
     if (rc) return rc;
-    hipLaunchKernelGGL(eval_lsd_reduce_kernel, dim3(B * EV_C), dim3(256), 0, s, spec, B, ps);
+    hipLaunchKernelGGL(eval_lsd_reduce_kernel, dim3(B * C), dim3(256), 0, s, spec, B, C, ps);
     SAGEN_LAUNCH_CHECK();
     return SAGEN_OK;
+}
+
+int eval_metrics_launch(const float* pred, const float* gt, int B, float* ps, double* pw, float* scratch, hipStream_t s) {
+    return eval_metrics_c_launch(pred, gt, B, EV_C, ps, pw, scratch, s);
 }
 
 }  // namespace sagen

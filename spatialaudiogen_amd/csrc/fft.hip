@@ -330,6 +330,223 @@ int mask_istft_mix_launch(const float* dmask, long dmask_bstride, int dmask_f0, 
 }
 
 // -----------------------------------------------------------------------------------------
+// Second order (ambi_order 2): NIN = 4 input channels (W,Y,Z,X), NOUT = 5 predicted channels (ACN 4..8).
+//
+// STFT of each input channel of the interleaved audio [B, n_samples, NIN] (model.py:369 runs one per channel):
+// mag [B, f1-f0, 1024, NIN] channels last (model.py:174), spec [B, NIN, c1-c0, 513, 2].  grid (ceil(nframes/2) * NIN, B, G).
+// -----------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void stft_multi_kernel(const float* __restrict__ audio_, int n_samples, int nin, int f0, int f1,
+                                                         float* __restrict__ mag_, int c0, int c1, float2* __restrict__ spec_,
+                                                         float* __restrict__ zero_ptr_, int zero_n, const GroupInfo gi) {
+    const float* __restrict__ audio = audio_ + (size_t)blockIdx.z * ((size_t)gridDim.y * n_samples * nin);
+    float* __restrict__ mag = SAGEN_GRP(mag_);
+    float2* __restrict__ spec = SAGEN_GRP(spec_);
+    float* __restrict__ zero_ptr = SAGEN_GRP(zero_ptr_);
+    __shared__ float2 bufA[1024], bufB[1024];
+    const int tid = threadIdx.x;
+    for (int i = (blockIdx.y * gridDim.x + blockIdx.x) * 256 + tid; i < zero_n; i += gridDim.x * gridDim.y * 256) zero_ptr[i] = 0.f;
+    const int b = blockIdx.y, ch = blockIdx.x % nin;
+    const int fa = f0 + 2 * (blockIdx.x / nin), fb = fa + 1;
+    const bool has_b = fb < f1;
+    const float* xa = audio + ((long)b * n_samples + 256L * fa) * nin + ch;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int n = tid + 256 * t;
+        const float h = g_hann[n];
+        const float va = xa[(long)n * nin] * h;
+        const float vb = has_b ? xa[(long)(256 + n) * nin] * h : 0.f;
+        bufA[n] = make_float2(va, vb);
+    }
+    __syncthreads();
+    const float2* Z = fft1024<false>(bufA, bufB, tid);
+    const int nf = f1 - f0, nc = c1 - c0;
+#pragma unroll
+    for (int t = 0; t < 4; ++t) {
+        const int k = tid + 256 * t;
+        const float2 zk = Z[k];
+        float2 zn = Z[(1024 - k) & 1023];
+        zn.y = -zn.y;
+        const float2 xA = make_float2(0.5f * (zk.x + zn.x), 0.5f * (zk.y + zn.y));
+        const float dx = zk.x - zn.x, dy = zk.y - zn.y;
+        const float2 xB = make_float2(0.5f * dy, -0.5f * dx);
+        if (mag) {
+            mag[(((long)b * nf + (fa - f0)) * 1024 + k) * nin + ch] = sqrtf(xA.x * xA.x + xA.y * xA.y);
+            if (has_b) mag[(((long)b * nf + (fb - f0)) * 1024 + k) * nin + ch] = sqrtf(xB.x * xB.x + xB.y * xB.y);
+        }
+        if (spec && k <= 512) {
+            float2* sp = spec + ((long)b * nin + ch) * nc * 513;
+            if (fa >= c0 && fa < c1) sp[(long)(fa - c0) * 513 + k] = xA;
+            if (has_b && fb >= c0 && fb < c1) sp[(long)(fb - c0) * 513 + k] = xB;
+        }
+    }
+}
+
+int stft_multi_launch(const float* audio, int B, int n_samples, int nin, int f0, int f1, float* mag, int c0, int c1, float* spec,
+                      hipStream_t s, float* zero_ptr, int zero_n) {
+    if (nin < 1 || nin > 16) return fail(SAGEN_ERR_SHAPE, "stft: %d input channels", nin);
+    if (f1 <= f0 || 256L * (f1 - 1) + 1024 > n_samples)
+        return fail(SAGEN_ERR_SHAPE, "stft: frames [%d,%d) do not fit %d samples", f0, f1, n_samples);
+    if (spec && (c0 < f0 || c1 > f1 || c1 <= c0)) return fail(SAGEN_ERR_SHAPE, "stft: spec frames must lie in [f0,f1)");
+    int rc = fft_tables_ensure(s);
+    if (rc) return rc;
+    const GroupInfo gi = cur_group();
+    hipLaunchKernelGGL(stft_multi_kernel, dim3(cdiv(f1 - f0, 2) * nin, B, gi.G), dim3(256), 0, s, audio, n_samples, nin, f0, f1, mag, c0, c1,
+                       (float2*)spec, zero_ptr, zero_ptr ? zero_n : 0, gi);
+    SAGEN_LAUNCH_CHECK();
+    return SAGEN_OK;
+}
+
+// mask -> iSTFT -> mix for NIN input and NOUT output channels (model.py:326-347, 421-434): deconv1's channel k = i * NTR + j is the
+// logit of track j of input channel i (the reshape of model.py:326-327), and
+//     out[n, o] = 1/4 sum_f real(ifft(Y_f^{o, step(n)}))[p] + bias[step(n), o, input channel 0]          (model.py:430)
+//     Y^{o,s}[k] = sum_i X_i[k] sum_j w[s, o, i, j] sigmoid(m_{i,j}[k])
+// (iSTFT is linear and the coefficients are constant over a step).  real(ifft(Y)) = ifft((Y[k] + conj Y[N-k]) / 2), so two of the
+// Hermitian parts share one complex 1024-point inverse transform, as in mask_istft_kernel.  grid (23 live frames, B, G).
+// The mask rows of a frame (NIN * NTR logits per bin) are read as one contiguous stream: lane q of a bin's NIN * NTR / 4 lanes takes
+// the 16-byte chunk q (input channel q / (NTR / 4), tracks 4 (q % (NTR / 4)) ..); the track sums are reduced across lanes with DPP
+// (wave_reduce.h), then weighted by X_i and reduced across the input channels.
+template <int NTR, int NIN, int NOUT>
+__global__ __launch_bounds__(256) void mask_istft_hoa_kernel(const float* __restrict__ dmask_, long dmask_bstride, int dmask_f0,
+                                                             const float2* __restrict__ spec_, const float* __restrict__ coeffs_,
+                                                             float* __restrict__ frames_, const GroupInfo gi) {
+    constexpr int QPI = NTR / 4;                  // 16-byte chunks per input channel of a bin
+    constexpr int CPB = NIN * QPI;                // lanes per bin
+    static_assert(CPB <= 64 && (CPB & (CPB - 1)) == 0, "one bin's chunks must fit a power-of-two lane group of a wave");
+    constexpr int BPI = 256 / CPB;                // bins per workgroup iteration
+    constexpr int NS = 2 * NOUT;                  // (step slot, output channel) spectra
+    const float* __restrict__ dmask = SAGEN_GRP(dmask_);
+    const float2* __restrict__ spec = SAGEN_GRP(spec_);
+    const float* __restrict__ coeffs = SAGEN_GRP(coeffs_);
+    float* __restrict__ frames = SAGEN_GRP(frames_);
+    __shared__ float2 Y[NS][1024];
+    __shared__ float2 fbuf[2][1024];
+    const int tid = threadIdx.x;
+    const int fi = blockIdx.x, f = MASK_F_LO + fi, b = blockIdx.y;
+    const int n_lo = max(256 * f - OUT_SHIFT, 0), n_hi = min(256 * f - OUT_SHIFT + 1023, 4799);
+    const int s_lo = n_lo / 1600, s_hi = n_hi / 1600;
+    const bool two = s_hi != s_lo;
+
+    const int q = tid % CPB, i = q / QPI, j0 = (q % QPI) * 4;
+    float w[2][NOUT][4];
+#pragma unroll
+    for (int si = 0; si < 2; ++si)
+#pragma unroll
+        for (int o = 0; o < NOUT; ++o)
+#pragma unroll
+            for (int u = 0; u < 4; ++u)
+                w[si][o][u] = coeffs[((((long)b * 3 + (si ? s_hi : s_lo)) * NOUT + o) * NIN + i) * (NTR + 1) + j0 + u];
+    const float4* src = reinterpret_cast<const float4*>(dmask + (long)b * dmask_bstride + (long)(f - dmask_f0) * 1024 * NIN * NTR);
+    const float2* X = spec + ((long)b * NIN + i) * 28 * 513 + (long)f * 513;
+#pragma unroll 2
+    for (int k = tid / CPB; k < 1024; k += BPI) {
+        const float4 v = src[(long)k * CPB + q];
+        float2 xk = X[k <= 512 ? k : 1024 - k];
+        if (k > 512) xk.y = -xk.y;
+        const float sg[4] = {1.f / (1.f + expf(-v.x)), 1.f / (1.f + expf(-v.y)), 1.f / (1.f + expf(-v.z)), 1.f / (1.f + expf(-v.w))};
+        float yr[2][NOUT], yi[2][NOUT];
+#pragma unroll
+        for (int si = 0; si < 2; ++si)
+#pragma unroll
+            for (int o = 0; o < NOUT; ++o) {
+                float m = 0.f;
+#pragma unroll
+                for (int u = 0; u < 4; ++u) m = fmaf(w[si][o][u], sg[u], m);
+                m = wave_sum<1, QPI>(m);                  // sum over the tracks of input channel i
+                yr[si][o] = wave_sum<QPI, CPB>(m * xk.x);  // ... times X_i, summed over the input channels
+                yi[si][o] = wave_sum<QPI, CPB>(m * xk.y);
+            }
+        if (q == 0) {
+#pragma unroll
+            for (int si = 0; si < 2; ++si)
+#pragma unroll
+                for (int o = 0; o < NOUT; ++o) Y[si * NOUT + o][k] = make_float2(yr[si][o], yi[si][o]);
+        }
+    }
+    __syncthreads();
+
+    float* fout = frames + ((long)b * MASK_NF + fi) * NOUT * 1024;
+    const int ns = two ? NS : NOUT;
+    for (int ca = 0; ca < ns; ca += 2) {
+        const int cb = ca + 1 < ns ? ca + 1 : -1;
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int k = tid + 256 * t;
+            const int km = (1024 - k) & 1023;
+            const float2 a0 = Y[ca][k], a1 = Y[ca][km];
+            const float2 ha = make_float2(0.5f * (a0.x + a1.x), 0.5f * (a0.y - a1.y));      // (Y[k] + conj Y[N-k]) / 2
+            float2 hb = make_float2(0.f, 0.f);
+            if (cb >= 0) {
+                const float2 b0 = Y[cb][k], b1 = Y[cb][km];
+                hb = make_float2(0.5f * (b0.x + b1.x), 0.5f * (b0.y - b1.y));
+            }
+            fbuf[0][k] = make_float2(ha.x - hb.y, ha.y + hb.x);                               // ha + i hb
+        }
+        __syncthreads();
+        const float2* R = fft1024<true>(fbuf[0], fbuf[1], tid);
+#pragma unroll
+        for (int t = 0; t < 4; ++t) {
+            const int p = tid + 256 * t;
+            const int n = 256 * f + p - OUT_SHIFT;
+            if (n >= 0 && n < 4800) {
+                const int st = n / 1600;
+                const float2 y = R[p];
+                if (st == ((ca / NOUT) ? s_hi : s_lo)) fout[(ca % NOUT) * 1024 + p] = y.x * (1.f / 1024.f);
+                if (cb >= 0 && st == ((cb / NOUT) ? s_hi : s_lo)) fout[(cb % NOUT) * 1024 + p] = y.y * (1.f / 1024.f);
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// overlap-add of the 4 covering frames + the bias of input channel 0 (biases[:, :, :, 0], model.py:430)
+template <int NIN, int NOUT>
+__global__ __launch_bounds__(256) void ola_mix_hoa_kernel(const float* __restrict__ frames_, const float* __restrict__ coeffs_,
+                                                          int ntr, float* __restrict__ out_, int B, const GroupInfo gi) {
+    const float* __restrict__ frames = SAGEN_GRP(frames_);
+    const float* __restrict__ coeffs = SAGEN_GRP(coeffs_);
+    float* __restrict__ out = out_ + (size_t)blockIdx.z * ((size_t)B * 4800 * NOUT);
+    const long total = (long)B * 4800 * NOUT;
+    for (long idx = (long)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (long)gridDim.x * 256) {
+        const int o = (int)(idx % NOUT);
+        const long r = idx / NOUT;
+        const int n = (int)(r % 4800);
+        const int b = (int)(r / 4800);
+        const int st = n / 1600;
+        float acc = 0.f;
+        const int fl = max((n + 193 + 255) / 256, MASK_F_LO), fh = min((n + OUT_SHIFT) / 256, MASK_F_HI - 1);
+        for (int f = fl; f <= fh; ++f)
+            acc += frames[(((long)b * MASK_NF + (f - MASK_F_LO)) * NOUT + o) * 1024 + (n + OUT_SHIFT - 256 * f)];
+        out[idx] = fmaf(acc, 0.25f, coeffs[((((long)b * 3 + st) * NOUT + o) * NIN + 0) * (ntr + 1) + ntr]);
+    }
+}
+
+size_t mask_istft_hoa_scratch_bytes(int B, int nout) { return (size_t)B * MASK_NF * nout * 1024 * sizeof(float); }
+
+int mask_istft_hoa_launch(const float* dmask, long dmask_bstride, int dmask_f0, const float* spec, const float* coeffs, int B,
+                          int ntracks, int nin, int nout, float* out, float* scratch, hipStream_t s) {
+    int rc = fft_tables_ensure(s);
+    if (rc) return rc;
+    if (dmask_f0 > MASK_F_LO || dmask_f0 < 0) return fail(SAGEN_ERR_SHAPE, "mask_istft_hoa: dmask must start at frame 0..%d", MASK_F_LO);
+    if (nin != 4 || nout != 5) return fail(SAGEN_ERR_UNSUPPORTED, "mask_istft_hoa: (nin, nout) = (%d, %d) (supported: (4, 5), ambi_order 2)", nin, nout);
+    const GroupInfo gi = cur_group();
+    dim3 grid(MASK_NF, B, gi.G);
+    if (ntracks == 32)
+        hipLaunchKernelGGL((mask_istft_hoa_kernel<32, 4, 5>), grid, dim3(256), 0, s, dmask, dmask_bstride, dmask_f0, (const float2*)spec, coeffs, scratch, gi);
+    else if (ntracks == 64)
+        hipLaunchKernelGGL((mask_istft_hoa_kernel<64, 4, 5>), grid, dim3(256), 0, s, dmask, dmask_bstride, dmask_f0, (const float2*)spec, coeffs, scratch, gi);
+    else if (ntracks == 16)
+        hipLaunchKernelGGL((mask_istft_hoa_kernel<16, 4, 5>), grid, dim3(256), 0, s, dmask, dmask_bstride, dmask_f0, (const float2*)spec, coeffs, scratch, gi);
+    else
+        return fail(SAGEN_ERR_UNSUPPORTED, "mask_istft_hoa: num_sep_tracks=%d (supported: 16, 32, 64)", ntracks);
+    SAGEN_LAUNCH_CHECK();
+    const long total = (long)B * 4800 * nout;
+    hipLaunchKernelGGL((ola_mix_hoa_kernel<4, 5>), dim3((int)std::min<long>(cdiv(total, 256), 4096L), 1, gi.G), dim3(256), 0, s, scratch, coeffs,
+                       ntracks, out, B, gi);
+    SAGEN_LAUNCH_CHECK();
+    return SAGEN_OK;
+}
+
+// -----------------------------------------------------------------------------------------
 // Adjoint of mask -> iSTFT -> overlap-add -> mix (backward of model.py:326-347, myutils.py:181-211, model.py:421-434).
 // Forward per (window b, frame f):  out[n,o] = 1/4 sum_f y_f^{o,step(n)}[p] + bias,  y^{o,s} = real(ifft((sum_j w[s,o,j] sigma(m_j)) X)),
 // n = 256 f + p - 1216.  With g^{o,s}[p] = 1/4 dL/dout[n,o] [step(n) = s] and G = FFT(g):

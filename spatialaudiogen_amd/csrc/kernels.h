@@ -275,6 +275,9 @@ int power_map_batched_launch(const float* ambi, int nchunks, long T, const float
 // NO_SEPARATION decoder (model.py:274-280, 430): out[b,n,o] = w[b,step,o,0]*mono + bias
 int nosep_mix_launch(const float* audio, const float* coeffs, float* out, int B, int snd_size,
                      int snd_contx, int snd_dur, int num_out, hipStream_t s);
+// ... with nin > 1 input channels: coeffs [B,3,num_out,nin,2] (elementwise.hip)
+int nosep_mix_multi_launch(const float* audio, const float* coeffs, float* out, int B, int snd_size, int snd_contx,
+                           int snd_dur, int nin, int num_out, hipStream_t s);
 
 // -----------------------------------------------------------------------------------------
 // P3 activation planes (p3.hip): [C/16][B*H*(W+1)][3][16] bf16, one zero pixel after every image row
@@ -331,6 +334,14 @@ int mask_istft_mix_launch(const float* dmask, long dmask_bstride, int dmask_f0, 
                           const float* coeffs, int B, int ntracks, float* out, float* scratch,
                           hipStream_t s, const float* ebuf = nullptr);
 // ebuf (then dmask may be null): the weighted sigmoid sums E[B][23][1024][8] written by the fused deconv1 epilogue (IgemmDesc::mm_out)
+// second order (fft.hip): audio [B, n_samples, nin] interleaved -> mag [B, f1-f0, 1024, nin], spec [B, nin, c1-c0, 513, 2]
+int stft_multi_launch(const float* audio, int B, int n_samples, int nin, int f0, int f1, float* mag, int c0, int c1, float* spec,
+                      hipStream_t s, float* zero_ptr = nullptr, int zero_n = 0);
+// dmask [B][..][1024][nin * ntracks] (frame dmask_f0 first), spec [B][nin][28][513][2], coeffs [B][3][nout][nin][ntracks + 1] ->
+// out [B][4800][nout]; scratch: frames [B][23][nout][1024]
+size_t mask_istft_hoa_scratch_bytes(int B, int nout);
+int mask_istft_hoa_launch(const float* dmask, long dmask_bstride, int dmask_f0, const float* spec, const float* coeffs, int B,
+                          int ntracks, int nin, int nout, float* out, float* scratch, hipStream_t s);
 
 // -----------------------------------------------------------------------------------------
 // evaluation metrics (eval.hip)
@@ -339,6 +350,9 @@ size_t eval_scratch_floats(int B);
 int eval_init_launch(float* scratch, hipStream_t s);                  // fills the DFT matrix once
 // ps [4][B][3] = per-sample stft distance, lsd, temporal mse, snr;  pw[2] = sum pred^2, sum gt^2 (fp64)
 int eval_metrics_launch(const float* pred, const float* gt, int B, float* ps, double* pw, float* scratch, hipStream_t s);
+// ... for C predicted channels: ps [4][B][C]; scratch of eval_scratch_floats_c(B, C) floats (C = 3: the two calls above)
+size_t eval_scratch_floats_c(int B, int C);
+int eval_metrics_c_launch(const float* pred, const float* gt, int B, int C, float* ps, double* pw, float* scratch, hipStream_t s);
 
 // -----------------------------------------------------------------------------------------
 // training-step pieces (train.hip): stft loss + gradient w.r.t. the prediction, fused Adam over a flat bucket

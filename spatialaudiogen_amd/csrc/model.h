@@ -82,6 +82,7 @@ struct sagen_ctx {
     int enc_h[6], enc_w[6], enc_c[6];   // audio encoder pyramid (index 0 = magnitude)
     int Cb = 0;                         // bottleneck width
     int nsep = 32;
+    int nin = 1, nout = 3;              // ambisonic channels in / predicted (model.py:242-243): order 1 = (1, 3), order 2 = (4, 5)
     bool has_video = false, has_flow = false, freq_mask = true;
 
     std::vector<VarSpec> vars;
@@ -517,7 +518,7 @@ struct Fwd {
         const std::string name = "separation/deconv" + std::to_string(l + 1);
         layer = name;
         const int kh = AENC_K[l][0], kw = AENC_K[l][1], sh = AENC_S[l][0], sw = AENC_S[l][1];
-        const int Cout = l == 0 ? c->nsep : AENC_F[l - 1];
+        const int Cout = l == 0 ? c->nsep * c->nin : AENC_F[l - 1];          // deconv1: channel i * nsep + j (model.py:326-327)
         const int Hout = Hin * sh + kh - sh, Wout = Win * sw + kw - sw;
         const int nth = cdiv(kh, sh), ntw = cdiv(kw, sw);
         IgemmDesc d;

@@ -17,10 +17,13 @@ int sagen_create_impl(sagen_ctx** out, const sagen_config* cfg, int groups) {
     if (!(cfg->encoders & SAGEN_ENC_AUDIO))
         return fail(SAGEN_ERR_UNSUPPORTED, "the audio encoder is mandatory (reference model.py:207)");
     if (cfg->audio_rate != 48000 || cfg->video_rate != 10 || cfg->context != 1.0f || cfg->sample_duration != 0.1f ||
-        cfg->ambi_order != 1 || cfg->fft_window != 0.025f)
+        cfg->fft_window != 0.025f)
         return fail(SAGEN_ERR_UNSUPPORTED,
-                    "HIP path implements audio_rate=48000 video_rate=10 context=1.0 sample_duration=0.1 ambi_order=1 "
+                    "HIP path implements audio_rate=48000 video_rate=10 context=1.0 sample_duration=0.1 "
                     "fft_window=0.025 (the geometry of every BASELINE config)");
+    if (cfg->ambi_order != 1 && cfg->ambi_order != 2)
+        return fail(SAGEN_ERR_UNSUPPORTED, "ambi_order=%d (supported: 1, 2; order 3 would need audio_encoder/conv1 with cin = 9, "
+                    "which the contraction kernels do not take)", cfg->ambi_order);
     if (cfg->separation != SAGEN_SEP_NONE && cfg->separation != SAGEN_SEP_FREQ_MASK)
         return fail(SAGEN_ERR_UNSUPPORTED, "unknown separation mode %d", cfg->separation);
     if (cfg->separation == SAGEN_SEP_NONE && cfg->num_sep_tracks > 1)
@@ -73,10 +76,12 @@ int sagen_create_impl(sagen_ctx** out, const sagen_config* cfg, int groups) {
     c->has_flow = cfg->encoders & SAGEN_ENC_FLOW;
     c->freq_mask = cfg->separation == SAGEN_SEP_FREQ_MASK;
     c->nsep = c->freq_mask ? cfg->num_sep_tracks : 1;
+    c->nin = cfg->ambi_order * cfg->ambi_order;                                              // model.py:243
+    c->nout = (cfg->ambi_order + 1) * (cfg->ambi_order + 1) - cfg->ambi_order * cfg->ambi_order;      // model.py:242
     const int B = c->B;
 
     // audio encoder pyramid (model.py:161-187), H = frames 46:173, W = 1024 bins
-    c->enc_h[0] = 127; c->enc_w[0] = 1024; c->enc_c[0] = 1;
+    c->enc_h[0] = 127; c->enc_w[0] = 1024; c->enc_c[0] = c->nin;
     for (int l = 0; l < 5; ++l) {
         c->enc_h[l + 1] = (c->enc_h[l] - AENC_K[l][0]) / AENC_S[l][0] + 1;
         c->enc_w[l + 1] = (c->enc_w[l] - AENC_K[l][1]) / AENC_S[l][1] + 1;
@@ -86,7 +91,7 @@ int sagen_create_impl(sagen_ctx** out, const sagen_config* cfg, int groups) {
 
     // ---- variable inventory ----
     {
-        int cin = 1;
+        int cin = c->nin;                  // one magnitude channel per input ambisonic channel (model.py:174)
         for (int l = 0; l < 5; ++l) {
             const std::string n = "audio_encoder/conv" + std::to_string(l + 1);
             c->add_var(n + "/weights", {AENC_K[l][0], AENC_K[l][1], cin, AENC_F[l]});
@@ -111,14 +116,14 @@ int sagen_create_impl(sagen_ctx** out, const sagen_config* cfg, int groups) {
             c->add_var(n + "/biases", {cfg->loc_units[i]});
             fin = cfg->loc_units[i];
         }
-        const int nlast = 3 * 1 * (c->nsep + 1);
+        const int nlast = c->nout * c->nin * (c->nsep + 1);          // model.py:253-254
         const std::string n = "localization/fc" + std::to_string(cfg->n_loc_units + 1);
         c->add_var(n + "/weights", {fin, nlast});
         c->add_var(n + "/biases", {nlast});
         if (c->freq_mask) {
             c->add_var("separation/fc-feats/weights", {c->Cb, 512});
             c->add_var("separation/fc-feats/biases", {512});
-            const int nfs[5] = {c->nsep, 32, 64, 128, 256};
+            const int nfs[5] = {c->nsep * c->nin, 32, 64, 128, 256};
             int dcin = 1024;
             for (int l = 4; l >= 0; --l) {
                 const std::string dn = "separation/deconv" + std::to_string(l + 1);
@@ -186,14 +191,14 @@ int sagen_create_impl(sagen_ctx** out, const sagen_config* cfg, int groups) {
     c->grp_off = c->ws_floats;
     c->alloc("h2s", 256);                  // fp16x2 scales: [0], [1] = 2^-ka of the planes in the video / flow trunk's plane buffer, [2..5] block-input bounds, [6] scratch, [7] saturation counter, [8..] 2^-kw per layer, [2 + H2_RIG_OFF ..] the rigorous bounds behind [2..5] (p3.hip)
     // activations
-    c->alloc("mag", (size_t)B * 127 * 1024);
-    c->alloc("spec", (size_t)B * 28 * 513 * 2);
+    c->alloc("mag", (size_t)B * 127 * 1024 * c->nin);
+    c->alloc("spec", (size_t)B * c->nin * 28 * 513 * 2);
     // concat buffers cat_l: [B, H_l, W_l, C_dec + C_enc]; cat5 = [conv5 | fc-feats]
     for (int l = 1; l <= 5; ++l)
         c->alloc("cat" + std::to_string(l), (size_t)B * c->enc_h[l] * c->enc_w[l] * 2 * c->enc_c[l]);
     c->alloc("bott", (size_t)B * 3 * c->Cb);
     for (int i = 0; i < cfg->n_loc_units; ++i) c->alloc("loc" + std::to_string(i + 1), (size_t)B * 3 * cfg->loc_units[i]);
-    c->alloc("coeffs", (size_t)B * 3 * 3 * (c->nsep + 1));
+    c->alloc("coeffs", (size_t)B * 3 * c->nout * c->nin * (c->nsep + 1));
     {   // fcm_kernel (fcm.hip) for the skinny FC layers at inference: partial buffers [slices][rows][N] per layer
         struct L { std::string name; int rows, K, N; };
         std::vector<L> ls;
@@ -202,7 +207,7 @@ int sagen_create_impl(sagen_ctx** out, const sagen_config* cfg, int groups) {
         if (c->has_flow) ls.push_back({"bottleneck/flow-fc", B, 7 * 14 * 128, 512});
         int fin = c->Cb;
         for (int i = 0; i < cfg->n_loc_units; ++i) { ls.push_back({"localization/fc" + std::to_string(i + 1), 3 * B, fin, cfg->loc_units[i]}); fin = cfg->loc_units[i]; }
-        ls.push_back({"localization/fc" + std::to_string(cfg->n_loc_units + 1), 3 * B, fin, 3 * (c->nsep + 1)});
+        ls.push_back({"localization/fc" + std::to_string(cfg->n_loc_units + 1), 3 * B, fin, c->nout * c->nin * (c->nsep + 1)});
         if (c->freq_mask) ls.push_back({"separation/fc-feats", 3 * B, c->Cb, 512});
         // OPT-IN (SAGEN_FCM=1): measured slower than the general kernels it replaces (audio-fc 33 vs 15 us, video-fc 22 vs 18, fc2 / fc3 17 vs
         // 9 - 10; only fc1 + fc-feats in one launch wins, 19 vs 23): these layers are bound by the latency of a short dependent launch
@@ -234,8 +239,8 @@ int sagen_create_impl(sagen_ctx** out, const sagen_config* cfg, int groups) {
             c->alloc("aencp", (mx + 3) / 4 + 64);
         }
         c->alloc("amax", 10 * H2_AMAX_FLOATS + 64);       // [cat_l: l = 1..5][decoder half, encoder half][H2_AMAX_FLOATS], then 2^-ka of the planes of cat_l at [.. + l]
-        c->alloc("dmask", (size_t)B * 23 * 1024 * c->nsep);
-        c->alloc("frames", mask_istft_scratch_bytes(B) / sizeof(float));
+        c->alloc("dmask", (size_t)B * 23 * 1024 * c->nsep * c->nin);
+        c->alloc("frames", (c->nin == 1 ? mask_istft_scratch_bytes(B) : mask_istft_hoa_scratch_bytes(B, c->nout)) / sizeof(float));
     }
     c->alloc("splitk_aux", (size_t)8 << 20);          // split-K scratch of the second stream (audio chain / flow FCs)
     c->alloc("splitk:tk", SK_TICKETS);                // per-tile tickets of the in-launch split-K combine (zero between launches)
@@ -260,16 +265,16 @@ int sagen_create_impl(sagen_ctx** out, const sagen_config* cfg, int groups) {
     // and is rewritten before its next use: the mask buffer, else the second stream's split-K scratch)
     c->bufs["dmask_or_scratch_flush"] = c->freq_mask ? c->bufs.at("dmask") : c->bufs.at("splitk_aux");
     // intermediates for parity tests
-    c->expose("mag", "mag", 0, {B, 127, 1024, 1}, 1);
-    c->expose("stft", "spec", 0, {B, 28, 513, 2}, 2);
+    c->expose("mag", "mag", 0, {B, 127, 1024, c->nin}, c->nin);
+    c->expose("stft", "spec", 0, {B, c->nin * 28, 513, 2}, 2);              // [B, nin, 28, 513, 2] with the channel and frame axes merged
     for (int l = 1; l <= 5; ++l) {
         const int ce = c->enc_c[l];
         c->expose("audio_encoder/conv" + std::to_string(l), "cat" + std::to_string(l), l == 5 ? 0 : ce,
                   {B, c->enc_h[l], c->enc_w[l], ce}, 2 * ce);
     }
     c->expose("bottleneck", "bott", 0, {B, 3, c->Cb}, c->Cb);
-    c->expose("localization/coeffs", "coeffs", 0, {B, 3, 3, c->nsep + 1}, c->nsep + 1);
-    if (c->freq_mask) c->expose("separation/deconv1", "dmask", 0, {B, 23, 1024, c->nsep}, c->nsep);
+    c->expose("localization/coeffs", "coeffs", 0, {B, 3, c->nout * c->nin, c->nsep + 1}, c->nsep + 1);      // [B, 3, nout, nin, nsep+1] (model.py:257)
+    if (c->freq_mask) c->expose("separation/deconv1", "dmask", 0, {B, 23, 1024, c->nsep * c->nin}, c->nsep * c->nin);
     // second stream + fork/join events (host-side objects; no device memory)
     // SAGEN_AUX_PRIO=low|high: the second stream below / above the default priority (experiment: the dispatcher then prefers one branch)
     int prio_lo = 0, prio_hi = 0;
@@ -515,7 +520,7 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
     // the epilogues of its two producers (conv1: encoder half, deconv2: decoder half) into words zeroed here
     const bool no_d1p = c->no_d1_planes;
     // (the opt-in in-launch split-K combine, SAGEN_SK_FUSED=1, has no reducer to publish a maximum from: it keeps the round-4 decoder)
-    bool d1_planes = !no_d1p && !c->sk_fused && c->freq_mask && !c->train_mode && !c->materialize_mask && !c->fp32_only && c->nsep == 32 && f.h2() &&
+    bool d1_planes = !no_d1p && !c->sk_fused && c->freq_mask && !c->train_mode && !c->materialize_mask && !c->fp32_only && c->nsep == 32 && c->nin == 1 && f.h2() &&
                      c->bufs.count("cat1p") != 0 && c->h2_slot.count("separation/deconv1") != 0 && getenv("SAGEN_NO_MASKFUSE") == nullptr;
     if (d1_planes && !c->tuning) {             // a plan that names a register-staged tile for deconv1 keeps the round-4 path (no pack pass)
         auto it = c->plan.find("separation/deconv1");
@@ -534,8 +539,12 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
 
     // ---- stream g: STFT (myutils.py:119-147) -> |.| of frames 46:173 (model.py:166-178) + spectrum of frames 89:117
     g.layer = "stft";
-    g.timed("stft_kernel", 0.0, [&] { return stft_launch(audio, B, c->snd_size, 46, 173, c->p("mag"), 89, 117, c->p("spec"), g.s,
-                                                         want_amax ? c->p("amax") : nullptr, 10 * H2_AMAX_FLOATS + 64); });
+    if (c->nin == 1)
+        g.timed("stft_kernel", 0.0, [&] { return stft_launch(audio, B, c->snd_size, 46, 173, c->p("mag"), 89, 117, c->p("spec"), g.s,
+                                                             want_amax ? c->p("amax") : nullptr, 10 * H2_AMAX_FLOATS + 64); });
+    else      // one STFT per input channel of the interleaved [B, snd_size, nin] audio (model.py:369)
+        g.timed("stft_multi_kernel", 0.0, [&] { return stft_multi_launch(audio, B, c->snd_size, c->nin, 46, 173, c->p("mag"), 89, 117, c->p("spec"), g.s,
+                                                                         want_amax ? c->p("amax") : nullptr, 10 * H2_AMAX_FLOATS + 64); });
     if (forked) {
         // The LDS FFT kernels give wrong results when bf16x3 contraction waves of ANOTHER stream share their CUs
         // (open): the first matrix launch of the main stream waits for the STFT (it overlaps the pad kernel).
@@ -558,7 +567,10 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
         float* y = c->p("cat" + std::to_string(l + 1)) + (l == 4 ? 0 : ce);
         int Ho, Wo;
         IgemmDesc d;
-        if (l == 0) {
+        if (l == 0 && c->nin > 1) {
+            // Cin = nin (4 at order 2): the magnitude is channels last, a plain power-of-two-Cin VALID conv
+            d = g.conv_desc(c->p("mag"), 127, 1024, c->nin, c->nin, c->p("pk:" + name + "/weights"), 7, 16, 4, 8, false, ce, y, 2 * ce, Ho, Wo);
+        } else if (l == 0) {
             // Cin = 1: the 16 taps along frequency are contiguous floats -> treat kw as 16 channels of a 7-tap conv
             d = g.conv_desc(c->p("mag"), 127, 1024, 16, 1, c->p("pk:" + name + "/weights"), 7, 1, 4, 8, false, ce, y, 2 * ce, Ho, Wo);
             Wo = c->enc_w[1];
@@ -675,7 +687,7 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
     // independent consumers of the bottleneck: second fork, the FCs go to the context's stream.
     static const bool no_fork2 = getenv("SAGEN_NO_FORK2") != nullptr;
     const bool fork2 = forked && c->freq_mask && !no_fork2;
-    const int nlast_fcm = 3 * (c->nsep + 1);
+    const int nlast_fcm = c->nout * c->nin * (c->nsep + 1);
     if (fcm) {
         // fc1 and fc-feats read the same rows (the bottleneck): one launch; the feats tile (cat5, six frequency columns: the decoder's
         // input) is finished on the caller's stream, then the streams fork: fc1's reducer, fc2, fc3 run next to the decoder.
@@ -716,7 +728,7 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
             w.fc(x, B * 3, K, K, "localization/fc" + std::to_string(i + 1), c->cfg.loc_units[i], true, y, c->cfg.loc_units[i]);
             x = y; K = c->cfg.loc_units[i];
         }
-        const int nlast = 3 * (c->nsep + 1);
+        const int nlast = c->nout * c->nin * (c->nsep + 1);
         w.fc(x, B * 3, K, K, "localization/fc" + std::to_string(c->cfg.n_loc_units + 1), nlast, false, c->p("coeffs"), nlast);
         if (f.rc || g.rc) return bail(f.rc ? f.rc : g.rc);
     }
@@ -724,7 +736,11 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
 
     if (!c->freq_mask) {
         f.layer = "decoder";
-        f.timed("nosep_mix_kernel", 0.0, [&] { return nosep_mix_launch(audio, c->p("coeffs"), out, B, c->snd_size, c->snd_contx, c->snd_dur, 3, s); });
+        if (c->nin == 1)
+            f.timed("nosep_mix_kernel", 0.0, [&] { return nosep_mix_launch(audio, c->p("coeffs"), out, B, c->snd_size, c->snd_contx, c->snd_dur, 3, s); });
+        else
+            f.timed("nosep_mix_multi_kernel", 0.0, [&] {
+                return nosep_mix_multi_launch(audio, c->p("coeffs"), out, B, c->snd_size, c->snd_contx, c->snd_dur, c->nin, c->nout, s); });
         return f.rc;
     }
 
@@ -767,7 +783,7 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
     // Inference: sigmoid and the track-weighted sums run in its epilogue (igemm_epilogue_maskmix) and the 94 MB of logits are never
     // written; the training step keeps them (the adjoint reads them), and so does sagen_set_option("materialize_mask", 1).
     static const bool no_maskfuse = getenv("SAGEN_NO_MASKFUSE") != nullptr;
-    const bool fused_tail = !no_maskfuse && !c->train_mode && !c->materialize_mask && !c->fp32_only && c->nsep == 32;
+    const bool fused_tail = !no_maskfuse && !c->train_mode && !c->materialize_mask && !c->fp32_only && c->nsep == 32 && c->nin == 1;
     c->mask_fused_last = fused_tail;
     if (fork2 && fused_tail) {                           // the epilogue needs the localisation coefficients (three small FCs, long done)
         SAGEN_HIP_CHECK(hipEventRecord(c->ev_join, c->aux));
@@ -795,12 +811,19 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
             d.h2_a_inv = a_inv; d.h2_w_inv = w_inv;
         };
     }
-    f.deconv(c->p("cat1"), 31, 127, 64, 0, c->p("dmask"), c->nsep, false, 11, 17, 67, 23L * 1024 * c->nsep, 44, c->p("coeffs"), ebuf, 23, d1_tweak);
+    const int nmask = c->nsep * c->nin;              // deconv1 channels: input channel i, track j -> i * nsep + j (model.py:326-327)
+    f.deconv(c->p("cat1"), 31, 127, 64, 0, c->p("dmask"), nmask, false, 11, 17, 67, 23L * 1024 * nmask, 44, c->p("coeffs"), ebuf, 23, d1_tweak);
     if (fork2 && !fused_tail) {                          // the mix needs the localisation coefficients
         SAGEN_HIP_CHECK(hipEventRecord(c->ev_join, c->aux));
         SAGEN_HIP_CHECK(hipStreamWaitEvent(s, c->ev_join, 0));
     }
     f.layer = "separation/mask-istft-mix";
+    if (c->nin > 1) {
+        f.timed("mask_istft_hoa_kernel+ola_mix_hoa_kernel", 0.0, [&] {
+            return mask_istft_hoa_launch(c->p("dmask"), 23L * 1024 * nmask, 1, c->p("spec"), c->p("coeffs"), B, c->nsep, c->nin, c->nout, out,
+                                         c->p("frames"), s); });
+        return f.rc;
+    }
     f.timed("mask_istft_kernel+ola_mix_kernel", 0.0, [&] {
         return mask_istft_mix_launch(c->p("dmask"), 23L * 1024 * c->nsep, 1, c->p("spec"), c->p("coeffs"), B, c->nsep, out,
                                      c->p("frames"), s, ebuf); });

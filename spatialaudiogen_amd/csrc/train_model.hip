@@ -743,6 +743,9 @@ int sagen_train_bind_impl(sagen_ctx* c, const sagen_tensor* grads, int n_grads, 
     if (!c->bound) return fail(SAGEN_ERR_WEIGHTS, "sagen_train_bind: bind the weights first");
     if (c->G != 1) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_train_bind: a grouped context (sagen_create_grouped) runs inference only");
     if (!c->freq_mask) return fail(SAGEN_ERR_UNSUPPORTED, "the training step implements separation 'unet_mask' (the configuration train.py trains)");
+    if (c->cfg.ambi_order != 1)
+        return fail(SAGEN_ERR_UNSUPPORTED, "sagen_train_bind: the training step implements ambi_order 1 only (got %d); order 2 runs inference only",
+                    c->cfg.ambi_order);
     train_carve(c);
     if (tws_bytes < c->tws_floats * sizeof(float))
         return fail(SAGEN_ERR_WORKSPACE, "train workspace has %zu bytes, need %zu", tws_bytes, c->tws_floats * sizeof(float));

@@ -46,6 +46,15 @@ def load_params(model_dir):
     return Struct(**params)
 
 
+def require_first_order(ambi_order, tool):
+    """The deploy, evaluate and train command lines run first-order models only: the reference's deploy.py:69,127 feeds a one-channel
+    placeholder whatever the order, the evaluation's power maps are first-order spherical harmonics, and the training step implements
+    order 1.  An order-2 model runs through SptAudioGen.inference_ops / evaluation_ops."""
+    if int(ambi_order) != 1:
+        raise SystemExit('%s: ambi_order %d is not supported by this command (first order only); a second-order model runs through '
+                         'SptAudioGen.inference_ops / evaluation_ops' % (tool, int(ambi_order)))
+
+
 def window_times(chunks_t, deploy_start, deploy_duration):
     """feeder.py:228-231 filters + deploy.py:106-107 shift (float64 arithmetic kept as written)."""
     ts = list(chunks_t)
@@ -287,6 +296,7 @@ def main(argv=None):
     import torch
     from .feeder import save_wav
     args = parse_arguments(argv)
+    require_first_order(load_params(args.model_dir).ambi_order, 'deploy')
     torch.cuda.set_device(args.gpu)
     model = W2XYZ(args.model_dir)
     model.groups = max(1, args.groups)

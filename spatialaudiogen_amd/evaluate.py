@@ -258,6 +258,8 @@ def main(argv=None):
                     help='also compute the per-sample directional RMS maps of prediction and ground truth on the device (the inputs of the '
                          "reference's EMD metric, eval.py:188-191) and save this rank's maps to <model_dir>/eval-powermaps-rank<r>.npz")
     args = ap.parse_args(argv)
+    from .deploy import load_params, require_first_order
+    require_first_order(load_params(args.model_dir).ambi_order, 'evaluate')
     means, count = evaluate(args.model_dir, args.db_dir, args.subset_fn, args.layouts_fn, overwrite=args.overwrite,
                             partial_batch=args.partial_batch, power_maps=args.power_maps, groups=args.groups)
     if args.power_maps and evaluate.last_maps:

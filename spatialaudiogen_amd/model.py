@@ -192,7 +192,8 @@ class SptAudioGen(object):
 
     # ---- the hot path ------------------------------------------------------------------------
     def inference_ops(self, audio, video=None, flow=None, is_training=True, out=None):
-        """audio [B,snd_size,1]; video/flow [B,1,224,448,3] -> x_ambi [B,snd_dur,3] (Y,Z,X).
+        """audio [B,snd_size,num_in]; video/flow [B,1,224,448,3] -> x_ambi [B,snd_dur,num_out]: order 1 [B,snd_size,1] -> Y,Z,X;
+        order 2 the W,Y,Z,X channels [B,snd_size,4] (eval.py:69) -> ACN 4..8.
         `is_training` is accepted for signature parity; as in the reference graph it does not change
         the arithmetic (BN uses batch statistics either way, model.py:197)."""
         def prep(t, name, tail):
@@ -204,7 +205,7 @@ class SptAudioGen(object):
             if tuple(t.shape[1:]) != tail:
                 raise ValueError('%s has shape %s, expected [B,%s]' % (name, tuple(t.shape), ','.join(map(str, tail))))
             return t
-        audio = prep(audio, 'audio', (self.snd_size, 1))
+        audio = prep(audio, 'audio', (self.snd_size, self.geom.num_in))
         if isinstance(video, np.ndarray) and video.dtype == np.uint8:
             video = torch.as_tensor(video)
         video_u8 = isinstance(video, torch.Tensor) and video.dtype == torch.uint8 and VIDEO in self.encoders
@@ -278,46 +279,52 @@ class SptAudioGen(object):
 
     # ---- evaluation metrics (model.py:110-154) -----------------------------------------------------
     def evaluation_ps(self, preds_t, targets_t):
-        """Device-only part of evaluation_ops: (ps [4, B, 3] = per-sample stft distance, lsd, mse, snr; pw [2] fp64 power sums),
+        """Device-only part of evaluation_ops: (ps [4, B, num_out] = per-sample stft distance, lsd, mse, snr; pw [2] fp64 power sums),
         no host synchronisation (the eval loop keeps batches in flight and reduces once at the end)."""
         pr = torch.as_tensor(preds_t).to(device=self.device, dtype=torch.float32).contiguous()
         gt = torch.as_tensor(targets_t).to(device=self.device, dtype=torch.float32).contiguous()
-        B = pr.shape[0]
-        if tuple(pr.shape) != (B, self.snd_dur, 3) or tuple(gt.shape) != tuple(pr.shape):
-            raise ValueError('predictions / targets must be [B, %d, 3]' % self.snd_dur)
+        B, nc = pr.shape[0], self.geom.num_out
+        if tuple(pr.shape) != (B, self.snd_dur, nc) or tuple(gt.shape) != tuple(pr.shape):
+            raise ValueError('predictions / targets must be [B, %d, %d]' % (self.snd_dur, nc))
         l = _lib.lib()
         key = ('eval', B)
         stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
         if key not in self._ctx:
-            nbytes = int(l.sagen_eval_scratch_bytes(B))
+            nbytes = int(l.sagen_eval_scratch_bytes(B) if nc == 3 else l.sagen_eval_scratch_bytes_c(B, nc))
             scratch = torch.empty((nbytes + 3) // 4, dtype=torch.float32, device=self.device)
             check(l.sagen_eval_init(C.c_void_p(scratch.data_ptr()), scratch.numel() * 4, B, stream))
             self._ctx[key] = scratch
         scratch = self._ctx[key]
-        ps = torch.empty(4, B, 3, dtype=torch.float32, device=self.device)
+        ps = torch.empty(4, B, nc, dtype=torch.float32, device=self.device)
         pw = torch.zeros(2, dtype=torch.float64, device=self.device)
-        check(l.sagen_eval_metrics(C.c_void_p(pr.data_ptr()), C.c_void_p(gt.data_ptr()), B, C.c_void_p(ps.data_ptr()),
-                                   C.c_void_p(pw.data_ptr()), C.c_void_p(scratch.data_ptr()), scratch.numel() * 4, stream))
+        if nc == 3:
+            check(l.sagen_eval_metrics(C.c_void_p(pr.data_ptr()), C.c_void_p(gt.data_ptr()), B, C.c_void_p(ps.data_ptr()),
+                                       C.c_void_p(pw.data_ptr()), C.c_void_p(scratch.data_ptr()), scratch.numel() * 4, stream))
+        else:
+            check(l.sagen_eval_metrics_c(C.c_void_p(pr.data_ptr()), C.c_void_p(gt.data_ptr()), B, nc, C.c_void_p(ps.data_ptr()),
+                                         C.c_void_p(pw.data_ptr()), C.c_void_p(scratch.data_ptr()), scratch.numel() * 4, stream))
         return ps, pw
 
     def evaluation_ops(self, preds_t, targets_t, w_t=None, mask_channels=None):
-        """preds/targets [B, snd_dur, 3] -> (metrics OrderedDict, stft_dist_ps, lsd_ps, mse_ps, snr_ps), the last four
-        [B, 3] device tensors exactly as the reference returns them.  `w_t` is accepted for signature parity (unused
+        """preds/targets [B, snd_dur, num_out] -> (metrics OrderedDict, stft_dist_ps, lsd_ps, mse_ps, snr_ps), the last four
+        [B, num_out] device tensors exactly as the reference returns them (per-channel entries: Y, Z, X at order 1, ACN4 .. ACN8 at
+        order 2).  `w_t` is accepted for signature parity (unused
         by the reference too).  Per-sample values are computed by libsagen_hip.so; the masked channel means of
         model.py:119-150 are a handful of scalar operations on [B,3] done here."""
         ps, pw = self.evaluation_ps(preds_t, targets_t)
-        B = ps.shape[1]
-        mask = torch.ones(B, 3, device=self.device) if mask_channels is None else \
+        B, nc = ps.shape[1], ps.shape[2]
+        names = 'YZX' if nc == 3 else ['ACN%d' % (self.geom.num_in + i) for i in range(nc)]
+        mask = torch.ones(B, nc, device=self.device) if mask_channels is None else \
             torch.as_tensor(mask_channels).to(device=self.device, dtype=torch.float32)
         num_masked = torch.clamp(mask.sum(0), min=1.0)
         metrics = OrderedDict()
         for name, idx, scale in (('stft', 0, 100.), ('lsd', 1, 1.), ('mse', 2, 5e3), ('snr', 3, 1.)):
             v = (ps[idx].double() * mask.double()).sum(0) / num_masked.double() * scale
             metrics[name + '/avg'] = float(v.mean())
-            for i, ch in enumerate('YZX'):
+            for i, ch in enumerate(names):
                 metrics[name + '/' + ch] = float(v[i])
-        metrics['pow/pred'] = float(pw[0]) / (3.0 * B)
-        metrics['pow/gt'] = float(pw[1]) / (3.0 * B)
+        metrics['pow/pred'] = float(pw[0]) / (float(nc) * B)
+        metrics['pow/gt'] = float(pw[1]) / (float(nc) * B)
         return metrics, ps[0], ps[1], ps[2], ps[3]
 
     def intermediate(self, batch, name):

@@ -706,12 +706,13 @@ def main(argv=None):
     """train.py:62-236 on the HIP path.  One process per GPU (torchrun): every rank holds a replica, draws its own batches and the
     gradient buckets are summed over the ranks (RCCL) before the fused Adam step."""
     import torch
-    from .deploy import load_params
+    from .deploy import load_params, require_first_order
     from .dist import init_process_group
     from .model import SptAudioGen, SptAudioGenParams
     from .weights import init_weights
     from .evaluate import read_layouts
     args = parse_arguments(argv)
+    require_first_order(load_params(args.model_dir).ambi_order if args.resume else args.ambi_order, 'train')
     rank, world = init_process_group()
     if torch.cuda.is_available():
         torch.cuda.set_device((int(os.environ.get('LOCAL_RANK', args.gpu))) % torch.cuda.device_count())

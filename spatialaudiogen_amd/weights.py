@@ -45,7 +45,7 @@ def variable_specs(encoders, separation=FREQ_MASK, num_sep_tracks=32, loc_units=
     geom = geom or Geometry()
     assert AUDIO in encoders, 'the audio encoder is mandatory (model.py:207 reads it unconditionally)'
     s = OrderedDict()
-    cin = 1
+    cin = geom.num_in                   # one STFT magnitude channel per input ambisonic channel (model.py:174)
     for l, (nf, k) in enumerate(zip(AENC_FILTERS, AENC_KERNELS)):
         s['audio_encoder/conv%d/weights' % (l + 1)] = (k[0], k[1], cin, nf)
         s['audio_encoder/conv%d/biases' % (l + 1)] = (nf,)
@@ -85,7 +85,7 @@ def variable_specs(encoders, separation=FREQ_MASK, num_sep_tracks=32, loc_units=
     if separation == FREQ_MASK:
         s['separation/fc-feats/weights'] = (cb, AENC_FILTERS[-1])
         s['separation/fc-feats/biases'] = (AENC_FILTERS[-1],)
-        nfs = [nsep * 1] + AENC_FILTERS[:-1]            # outputs of deconv1..5
+        nfs = [nsep * geom.num_in] + AENC_FILTERS[:-1]  # outputs of deconv1..5 (deconv1: nsep tracks per input channel, model.py:300-301)
         cin = 2 * AENC_FILTERS[-1]
         for l in reversed(range(5)):
             k = AENC_KERNELS[l]
@@ -169,17 +169,20 @@ def init_weights(specs, seed=0, mode='test', fc3_std=0.05):
 
 
 def synth_inputs(batch, encoders, seed=1234, geom=None):
-    """Seeded synthetic inputs of SURVEY 8(d): audio [B,snd_size,1], video/flow [B,1,224,448,3]."""
+    """Seeded synthetic inputs of SURVEY 8(d): audio [B,snd_size,num_in] (num_in = 1 at order 1; at order 2 the four W,Y,Z,X channels,
+    each its own mixture of sines), video/flow [B,1,224,448,3]."""
     geom = geom or Geometry()
     rng = np.random.Generator(np.random.PCG64(seed))
     n = np.arange(geom.snd_size)[None, :]
-    audio = np.zeros((batch, geom.snd_size))
-    for _ in range(3):
-        f = rng.uniform(100, 8000, size=(batch, 1))
-        ph = rng.uniform(0, 2 * np.pi, size=(batch, 1))
-        audio += np.sin(2 * np.pi * f * n / geom.audio_rate + ph)
-    audio = np.clip(0.25 * audio + 0.05 * rng.normal(size=audio.shape), -1, 1)
-    out = {AUDIO: audio.astype(np.float32)[:, :, None]}
+    chans = []
+    for _ in range(geom.num_in):
+        audio = np.zeros((batch, geom.snd_size))
+        for _ in range(3):
+            f = rng.uniform(100, 8000, size=(batch, 1))
+            ph = rng.uniform(0, 2 * np.pi, size=(batch, 1))
+            audio += np.sin(2 * np.pi * f * n / geom.audio_rate + ph)
+        chans.append(np.clip(0.25 * audio + 0.05 * rng.normal(size=audio.shape), -1, 1))
+    out = {AUDIO: np.stack(chans, 2).astype(np.float32)}
 
     def smooth(x):   # 8x8 box blur by block-mean + nearest upsample (cheap, deterministic)
         b, h, w, c = x.shape
