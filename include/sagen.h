@@ -281,6 +281,29 @@ int sagen_power_map(const float* ambi_wyzx, int64_t t, const float* sh, int p, f
 int sagen_power_map_batched(const float* ambi_wyzx, int nchunks, int64_t t, const float* sh, int p, float* rms, double* moments,
                             void* stream);
 
+/* The per-sample metrics eval.py computes on the host (eval.py:172-182), for 0.1 s windows at 48 kHz:
+ *  - mel_lsd [B][C] = myutils.compute_lsd_dist (myutils.py:96-106): librosa 0.6.0 melspectrogram(sr=48000, n_mels=128, fmax=12000;
+ *    reflect pad 1024, 10 frames of 2048 at hop 512, periodic Hann, power 2, Slaney mel basis with norm=1), L = 10 log10(M + 0.01),
+ *    sqrt(mean over 128 x 10 of (L_gt - L_pred)^2);
+ *  - env_mse [B][C] = myutils.compute_envelope_dist (myutils.py:109-116): |scipy.signal.hilbert| with N = 4800 (circular),
+ *    sqrt(mean_n (env_gt - env_pred)^2).
+ * pred / target [B][4800][C] (first order: C = 3, Y,Z,X; 1 <= C <= 8, SAGEN_ERR_UNSUPPORTED otherwise), no channel masking.
+ * scratch: >= sagen_eval_mel_env_scratch_bytes(batch, channels) bytes (no init). */
+size_t sagen_eval_mel_env_scratch_bytes(int batch, int channels);
+int sagen_eval_mel_env(const float* pred, const float* target, int batch, int channels, float* mel_lsd, float* env_mse, void* scratch,
+                       size_t scratch_bytes, void* stream);
+
+/* emd/dir and emd/dir2 of eval.py:188-193 (ambix_emd -> emd, distance.py:100-143; pyemd 0.5.1 emd with its default extra-mass
+ * penalty max(cost)) between directional RMS maps, exactly in fp64:
+ *   emd[m][0] = EMD-hat(p_m / nodes, q_m / nodes), emd[m][1] = EMD-hat(p_m / (sum p_m + 0.01), q_m / (sum q_m + 0.01)),
+ *   EMD-hat(P, Q) = min sum f_ij cost_ij over f >= 0 with row sums <= P_i, column sums <= Q_j, total min(sum P, sum Q)
+ *                   + |sum P - sum Q| * max cost.
+ * p / q [n_maps][nodes] (sagen_power_map_batched rows; nodes <= 96, SAGEN_ERR_UNSUPPORTED otherwise), cost [nodes][nodes] fp64 metric
+ * (ambisonics.angular_distance), emd [n_maps][2] fp64.  A non-finite map gives NaN.  *not_converged (device uint32, not cleared)
+ * is incremented once per problem that hit the solver's augmentation cap - the caller checks it. */
+int sagen_eval_emd(const float* p, const float* q, int n_maps, int nodes, const double* cost, double* emd, uint32_t* not_converged,
+                   void* stream);
+
 /* ---- training step (reference train.py:137-236) -------------------------------------------------------
  * Loss of the reference: losses['stft/mse'] = metrics['stft/avg'] (model.py:156-159, 122-127; stft_for_loss myutils.py:151-178).
  * pred / target [B,4800,3]; mask [B,3] channel mask (the Y,Z,X columns of the feeder's [B,4] W,Y,Z,X mask, train.py:127) or NULL;

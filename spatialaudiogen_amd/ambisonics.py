@@ -27,3 +27,15 @@ def sh_matrix(angular_res):
 def mesh_shape(angular_res):
     phi, _ = spherical_mesh(angular_res)
     return phi.shape
+
+
+def angular_distance(angular_res):
+    """[P, P] fp64 great-circle distance between the mesh's directions, the ground distance of the EMD metric (distance.py:101-110);
+    same row-major node order as sh_matrix.  The reference's arccos(clip(u_i . u_j, -1, 1)) turns the rounding of a dot product
+    of 1 into 1.5e-8 rad on the diagonal and between the coincident pole nodes, which pyemd's cost quantisation (max C / 1e6) then
+    rounds back to 0; atan2(|u_i x u_j|, u_i . u_j) gives those exactly 0 (to 1e-16) and equals the arccos form everywhere else."""
+    phi, nu = spherical_mesh(angular_res)
+    phi, nu = phi.reshape(-1), nu.reshape(-1)
+    u = np.stack([np.cos(nu) * np.cos(phi), np.cos(nu) * np.sin(phi), np.sin(nu)], -1)
+    cross = np.linalg.norm(np.cross(u[:, None, :], u[None, :, :]), axis=-1)
+    return np.arctan2(cross, u @ u.T)

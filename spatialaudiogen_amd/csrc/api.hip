@@ -1,6 +1,7 @@
 // extern "C" surface of libsagen_hip.so (include/sagen.h).  Thin: argument checking, error codes,
 // no exceptions across the boundary.
 #include "kernels.h"
+#include "emd_core.h"
 #include <new>
 #include <cstdlib>
 #include <algorithm>
@@ -432,6 +433,29 @@ int sagen_power_map_batched(const float* ambi_wyzx, int nchunks, int64_t t, cons
     if (((uintptr_t)moments) % 8 || ((uintptr_t)ambi_wyzx) % 16 || ((uintptr_t)sh) % 16)
         return fail(SAGEN_ERR_SHAPE, "sagen_power_map_batched: ambi / sh must be 16-byte aligned, moments 8-byte aligned");
     return power_map_batched_launch(ambi_wyzx, nchunks, t, sh, p, rms, moments, (hipStream_t)stream);
+}
+
+size_t sagen_eval_mel_env_scratch_bytes(int batch, int channels) {
+    return batch > 0 && channels > 0 ? evalx_scratch_floats(batch, channels) * sizeof(float) : 0;
+}
+
+int sagen_eval_mel_env(const float* pred, const float* target, int batch, int channels, float* mel_lsd, float* env_mse, void* scratch,
+                       size_t scratch_bytes, void* stream) {
+    if (!pred || !target || !mel_lsd || !env_mse || !scratch) return fail(SAGEN_ERR_NULL, "sagen_eval_mel_env: null argument");
+    if (batch <= 0) return fail(SAGEN_ERR_SHAPE, "sagen_eval_mel_env: batch=%d", batch);
+    if (channels < 1 || channels > 8) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_eval_mel_env: channels=%d (supported: 1..8)", channels);
+    if (scratch_bytes < sagen_eval_mel_env_scratch_bytes(batch, channels)) return fail(SAGEN_ERR_WORKSPACE, "sagen_eval_mel_env: scratch too small");
+    return evalx_mel_env_launch(pred, target, batch, channels, mel_lsd, env_mse, (float*)scratch, (hipStream_t)stream);
+}
+
+int sagen_eval_emd(const float* p, const float* q, int n_maps, int nodes, const double* cost, double* emd, uint32_t* not_converged,
+                   void* stream) {
+    if (!p || !q || !cost || !emd || !not_converged) return fail(SAGEN_ERR_NULL, "sagen_eval_emd: null argument");
+    if (n_maps <= 0 || nodes <= 0) return fail(SAGEN_ERR_SHAPE, "sagen_eval_emd: n_maps=%d nodes=%d", n_maps, nodes);
+    if (nodes > EMD_MAX_NODES) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_eval_emd: nodes=%d (supported: <= %d)", nodes, EMD_MAX_NODES);
+    if (((uintptr_t)cost) % 8 || ((uintptr_t)emd) % 8 || ((uintptr_t)not_converged) % 4)
+        return fail(SAGEN_ERR_SHAPE, "sagen_eval_emd: cost / emd must be 8-byte aligned, not_converged 4-byte aligned");
+    return evalx_emd_launch(p, q, n_maps, nodes, cost, emd, (unsigned int*)not_converged, (hipStream_t)stream);
 }
 
 int sagen_stft_loss_grad(const float* pred_yzx, const float* target_yzx, const float* mask, int batch, float* grad, double* loss,

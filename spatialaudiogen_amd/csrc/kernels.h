@@ -353,6 +353,13 @@ int eval_metrics_launch(const float* pred, const float* gt, int B, float* ps, do
 // ... for C predicted channels: ps [4][B][C]; scratch of eval_scratch_floats_c(B, C) floats (C = 3: the two calls above)
 size_t eval_scratch_floats_c(int B, int C);
 int eval_metrics_c_launch(const float* pred, const float* gt, int B, int C, float* ps, double* pw, float* scratch, hipStream_t s);
+// eval.py's host metrics (evalx.hip): mel_lsd / env_mse [B][C] from pred / gt [B][4800][C]; scratch of evalx_scratch_floats(B, C)
+size_t evalx_scratch_floats(int B, int C);
+int evalx_mel_env_launch(const float* pred, const float* gt, int B, int C, float* mel_lsd, float* env_mse, float* scratch,
+                         hipStream_t s);
+// exact EMD-hat of map pairs p / q [n_maps][nodes] (nodes <= EMD_MAX_NODES) on cost [nodes][nodes]: out [n_maps][2] = dir, dir2
+int evalx_emd_launch(const float* p, const float* q, int n_maps, int nodes, const double* cost, double* out, unsigned int* not_converged,
+                     hipStream_t s);
 
 // -----------------------------------------------------------------------------------------
 // training-step pieces (train.hip): stft loss + gradient w.r.t. the prediction, fused Adam over a flat bucket

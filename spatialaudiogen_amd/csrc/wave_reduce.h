@@ -56,3 +56,82 @@ __device__ __forceinline__ float wave_sum(float v) {
 }
 
 }  // namespace sagen
+
+namespace sagen {
+
+// ---- fp64 / (value, index) butterflies (the EMD solver, evalx.hip) --------------------------------------------------------------
+template <int CTRL, int BANK_MASK = 0xF>
+__device__ __forceinline__ int dpp_mov_i(int old, int v) {
+    return __builtin_amdgcn_update_dpp(old, v, CTRL, 0xF, BANK_MASK, false);
+}
+
+// {a, b} = {v of this lane, v of lane ^ M} (for M = 16, 32 in either order: the row swaps hand one of each to both lanes)
+template <int M>
+__device__ __forceinline__ void lane_pair(int v, int& a, int& b) {
+    static_assert(M == 1 || M == 2 || M == 4 || M == 8 || M == 16 || M == 32, "lane mask must be a power of two below 64");
+    a = v;
+    if constexpr (M == 1) {
+        b = dpp_mov_i<0xB1>(v, v);
+    } else if constexpr (M == 2) {
+        b = dpp_mov_i<0x4E>(v, v);
+    } else if constexpr (M == 4) {
+        b = dpp_mov_i<0x114, 0xA>(dpp_mov_i<0x104, 0x5>(v, v), v);
+    } else if constexpr (M == 8) {
+        b = dpp_mov_i<0x118, 0xC>(dpp_mov_i<0x108, 0x3>(v, v), v);
+    } else if constexpr (M == 16) {
+        b = v;
+        asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+    } else {
+        b = v;
+        asm volatile("s_nop 1\n\tv_permlane32_swap_b32 %0, %1" : "+v"(a), "+v"(b));
+    }
+}
+
+template <int M>
+__device__ __forceinline__ void lane_pair_f64(double v, double& a, double& b) {
+    int ha, hb, la, lb;
+    lane_pair<M>(__double2hiint(v), ha, hb);
+    lane_pair<M>(__double2loint(v), la, lb);
+    a = __hiloint2double(ha, la);
+    b = __hiloint2double(hb, lb);
+}
+
+// every lane ends with the sum of all 64 lanes, in one fixed order (a + b == b + a: both lanes of a pair agree bit for bit)
+template <int M = 1>
+__device__ __forceinline__ double wave_sum_f64(double v) {
+    if constexpr (M < 64) {
+        double a, b;
+        lane_pair_f64<M>(v, a, b);
+        return wave_sum_f64<M * 2>(a + b);
+    } else {
+        return v;
+    }
+}
+
+template <int M = 1>
+__device__ __forceinline__ double wave_max_f64(double v) {
+    if constexpr (M < 64) {
+        double a, b;
+        lane_pair_f64<M>(v, a, b);
+        return wave_max_f64<M * 2>(a > b ? a : b);
+    } else {
+        return v;
+    }
+}
+
+// lexicographic minimum of (d, i) over the wave: the smaller distance, then the smaller index
+template <int M = 1>
+__device__ __forceinline__ void wave_argmin_f64(double& d, int& i) {
+    if constexpr (M < 64) {
+        double da, db;
+        int ia, ib;
+        lane_pair_f64<M>(d, da, db);
+        lane_pair<M>(i, ia, ib);
+        const bool second = db < da || (db == da && ib < ia);
+        d = second ? db : da;
+        i = second ? ib : ia;
+        wave_argmin_f64<M * 2>(d, i);
+    }
+}
+
+}  // namespace sagen

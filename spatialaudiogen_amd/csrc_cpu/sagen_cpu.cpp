@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/sagen.h"
+#include "../csrc/emd_core.h"
 
 namespace {
 
@@ -325,6 +326,27 @@ int sagen_assemble_wyzx(const float* audio, const float* ambi_yzx, float* out_wy
             float* o = out_wyzx + ((size_t)b * snd_dur + n) * 4;
             o[0] = audio[(size_t)b * snd_size + snd_contx / 2 + n];
             for (int c = 0; c < 3; ++c) o[1 + c] = ambi_yzx[((size_t)b * snd_dur + n) * 3 + c];
+        }
+    return SAGEN_OK;
+}
+
+// emd/dir, emd/dir2 (distance.py:100-143): the solver core of the device kernel (csrc/emd_core.h) run by one host "lane"
+int sagen_eval_emd(const float* p, const float* q, int n_maps, int nodes, const double* cost, double* emd, uint32_t* not_converged, void*) {
+    if (!p || !q || !cost || !emd || !not_converged) return fail(SAGEN_ERR_NULL, "sagen_eval_emd: null argument");
+    if (n_maps <= 0 || nodes <= 0) return fail(SAGEN_ERR_SHAPE, "sagen_eval_emd: n_maps=%d nodes=%d", n_maps, nodes);
+    if (nodes > sagen::EMD_MAX_NODES) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_eval_emd: nodes=%d", nodes);
+    std::vector<sagen::EmdState> st(1);
+    std::vector<double> P(nodes), Q(nodes);
+    const sagen::EmdSerial w;
+    for (int m = 0; m < n_maps; ++m)
+        for (int var = 0; var < 2; ++var) {
+            double sp = 0.0, sq = 0.0;
+            for (int v = 0; v < nodes; ++v) { sp += p[(size_t)m * nodes + v]; sq += q[(size_t)m * nodes + v]; }
+            const double np_ = var == 0 ? (double)nodes : sp + 0.01, nq = var == 0 ? (double)nodes : sq + 0.01;
+            for (int v = 0; v < nodes; ++v) { P[v] = p[(size_t)m * nodes + v] / np_; Q[v] = q[(size_t)m * nodes + v] / nq; }
+            int conv = 1;
+            emd[m * 2 + var] = sagen::emd_hat(w, st[0], P.data(), Q.data(), nodes, cost, &conv);
+            if (!conv) ++*not_converged;
         }
     return SAGEN_OK;
 }

@@ -10,8 +10,11 @@ batch-norm runs on batch statistics; batches are cut from ONE global window orde
 of ranks); per-sample metric rows are written by rank 0 to `eval-detailed.txt` in the
 reference's format, and the global means come from ONE all-reduce of float64 sums + count (RCCL).
 
-Host-only metrics of eval.py (mel-LSD via librosa, envelope distance via scipy.hilbert, EMD via pyemd) are outside
-this path and are not computed.
+By default the file holds the 18 on-graph columns (METRIC_KEYS).  With --all_metrics it holds all 28 columns of eval.py:125-132
+(ALL_METRIC_KEYS, the reference's order): the metrics the reference computes on the host per sample - mel-LSD (librosa,
+myutils.py:96-106), envelope distance (scipy.signal.hilbert, myutils.py:109-116) and EMD between directional RMS maps (pyemd,
+distance.py:100-143) - are computed on the device too (sagen_eval_mel_env, sagen_eval_emd: exact fp64 EMD-hat), and only
+per-sample scalars come back to the host.
 """
 import os
 from collections import OrderedDict
@@ -26,6 +29,12 @@ SKIP_RATE = 10             # feeder.py:379 (for_eval)
 METRIC_KEYS = ['amplitude/predicted', 'amplitude/gt',
                'mse/avg', 'mse/X', 'mse/Y', 'mse/Z', 'stft/avg', 'stft/X', 'stft/Y', 'stft/Z',
                'lsd/avg', 'lsd/X', 'lsd/Y', 'lsd/Z', 'snr/avg', 'snr/X', 'snr/Y', 'snr/Z']    # eval.py:125-133 (on-graph subset)
+ALL_METRIC_KEYS = ['amplitude/predicted', 'amplitude/gt',
+                   'mse/avg', 'mse/X', 'mse/Y', 'mse/Z', 'stft/avg', 'stft/X', 'stft/Y', 'stft/Z',
+                   'lsd/avg', 'lsd/X', 'lsd/Y', 'lsd/Z', 'mel_lsd/avg', 'mel_lsd/X', 'mel_lsd/Y', 'mel_lsd/Z',
+                   'snr/avg', 'snr/X', 'snr/Y', 'snr/Z', 'env_mse/avg', 'env_mse/X', 'env_mse/Y', 'env_mse/Z',
+                   'emd/dir', 'emd/dir2']                                                      # eval.py:125-132 (--all_metrics)
+EMD_ANGULAR_RES = 30.0     # eval.py:190
 
 
 def read_layouts(fn):
@@ -64,7 +73,7 @@ def batch_shard(n_windows, rank, world, partial_batch='drop'):
 
 
 class Evaluator(object):
-    def __init__(self, net, params, power_maps=False):
+    def __init__(self, net, params, power_maps=False, all_metrics=False):
         self.net, self.params = net, params
         self.ss = int(params.audio_rate * params.context) // 2
         self.t = int(params.audio_rate * 0.1)
@@ -72,6 +81,8 @@ class Evaluator(object):
         self.power_maps = power_maps
         self.maps = []                    # per sample (pred map, gt map) [7,12] each (eval.py:190: ang_res=30)
         self._sh = None
+        self.all_metrics = all_metrics    # + mel_lsd, env_mse, emd (ALL_METRIC_KEYS rows)
+        self._cost = None
 
     def run_batches(self, batches, grouped_net):
         """`len(batches)` FULL batches (each (ids, ambix [16,52799,4], video, flow, masks), frames of one dtype) as ONE grouped forward
@@ -109,30 +120,61 @@ class Evaluator(object):
         amp_p = pred.abs().amax(dim=(1, 2)); amp_g = target.abs().amax(dim=(1, 2))
         per = torch.stack([amp_p, amp_g], 1).cpu().numpy()
         S = [x.cpu().numpy() for x in (mse_ps, stft_ps, lsd_ps, snr_ps)]
-        if self.power_maps:
-            self._power_maps(a, pred, target, m, n)
+        maps = None
+        if self.power_maps or self.all_metrics:
+            maps = self._power_maps(a, pred, target, m, n)
+        if self.all_metrics:
+            from . import ops
+            mel, env = ops.eval_mel_env(pred, target)         # unmasked, as eval.py:174,182 pass pred / gt
+            emd = self._emd(*maps, n)
+            # eval.py:125-132 order: mse, stft, lsd, mel_lsd, snr, env_mse (each avg, X, Y, Z), then emd/dir, emd/dir2
+            S = S[:3] + [mel[:n].cpu().numpy()] + S[3:] + [env[:n].cpu().numpy()]
         for i in range(n):
             row = [per[i, 0], per[i, 1]]
             for k, arr in enumerate(S):         # eval.py:155-171 appends the RAW per-sample values (no x5e3 / x100)
                 v = arr[i]
-                avg = float(np.nanmean(v)) if k == 3 and np.isfinite(v).any() else float(np.mean(v))   # snr/avg is a nanmean (eval.py:168)
+                snr = k == (4 if self.all_metrics else 3)                                 # snr/avg is a nanmean (eval.py:168)
+                avg = float(np.nanmean(v)) if snr and np.isfinite(v).any() else float(np.mean(v))
                 row += [avg, float(v[2]), float(v[0]), float(v[1])]   # avg, X, Y, Z  (channels are Y,Z,X)
+            if self.all_metrics:
+                row += [float(emd[i, 0]), float(emd[i, 1])]
             self.rows.append(row)
             self.ids.append(ids[i])
 
     def _power_maps(self, a, pred, target, m, n):
         """Directional RMS maps of the masked WYZX prediction / ground truth of every sample - the inputs of the
         reference's EMD metric (eval.py:147-149,188-191 -> distance.py:41-59,133-143; one 0.1 s frame per sample, 30 degree
-        mesh), computed on the device by sagen_power_map_batched.  The EMD itself (pyemd) is host code outside the path."""
+        mesh), computed on the device by sagen_power_map_batched.  Returns the device maps [N, 84] (prediction, ground truth);
+        with power_maps the first n of each are kept on the host, [n, 7, 12] in eval.py's (flipud) orientation."""
         import torch
         from . import ops
-        from .ambisonics import sh_matrix
+        from .ambisonics import sh_matrix, mesh_shape
         if self._sh is None:
-            self._sh = torch.as_tensor(sh_matrix(30.0), dtype=torch.float32, device=pred.device)
+            self._sh = torch.as_tensor(sh_matrix(EMD_ANGULAR_RES), dtype=torch.float32, device=pred.device)
         mono = a[:, self.ss:self.ss + self.t, :1]
+        out = []
         for x in (pred, target):
             wyzx = (torch.cat([mono, x], 2) * m[:, None, :]).contiguous()
-            self.maps.append(ops.power_map_batched(wyzx, self._sh)[:n].reshape(n, 7, 12).flip(1).cpu().numpy())
+            out.append(ops.power_map_batched(wyzx, self._sh))
+            if self.power_maps:
+                self.maps.append(out[-1][:n].reshape((n,) + mesh_shape(EMD_ANGULAR_RES)).flip(1).cpu().numpy())
+        return out
+
+    def _emd(self, p_maps, q_maps, n):
+        """emd/dir, emd/dir2 per sample (eval.py:188-193) of the first n map pairs, on the device (sagen_eval_emd) -> [n, 2] host.
+        The maps stay in the device's row order: the reference's flipud is a reflection of the elevation grid, which is symmetric,
+        so the distances do not change."""
+        import torch
+        from . import ops
+        from .ambisonics import angular_distance
+        if self._cost is None:
+            self._cost = torch.as_tensor(angular_distance(EMD_ANGULAR_RES), dtype=torch.float64, device=p_maps.device)
+            self._not_converged = torch.zeros(1, dtype=torch.int32, device=p_maps.device)
+        emd = ops.eval_emd(p_maps[:n], q_maps[:n], self._cost, self._not_converged).cpu().numpy()
+        bad = int(self._not_converged.item())
+        if bad:
+            raise RuntimeError('EMD: %d problems hit the exact solver\'s augmentation cap (sagen_eval_emd): their values are not the optimum' % bad)
+        return emd
 
 
 class _ReaderCache(object):
@@ -152,7 +194,7 @@ class _ReaderCache(object):
 
 
 def evaluate(model_dir, db_dir, subset_fn=None, layouts_fn=None, variables=None, params=None, overwrite=True,
-             partial_batch='drop', power_maps=False, groups=1):
+             partial_batch='drop', power_maps=False, groups=1, all_metrics=False):
     import torch
     from .deploy import load_params, W2XYZ
     from .feeder import SampleReader
@@ -172,7 +214,8 @@ def evaluate(model_dir, db_dir, subset_fn=None, layouts_fn=None, variables=None,
         context=params.context, duration=0.1, return_video=VIDEO in params.encoders, img_prep=None,      # frames stay uint8 (sagen_forward_u8)
         return_flow=FLOW in params.encoders, skip_silence_thr=None, shuffle=False, random_rotations=False,
         skip_rate=SKIP_RATE))                                              # feeder.py:373-396 (for_eval)
-    ev = Evaluator(net, params, power_maps=power_maps)
+    ev = Evaluator(net, params, power_maps=power_maps, all_metrics=all_metrics)
+    keys = ALL_METRIC_KEYS if all_metrics else METRIC_KEYS
     # groups > 1 (round 6): `groups` consecutive FULL batches of the rank's shard per forward call (W2XYZ._grouped_model: the same
     # device variables, grouped native contexts) - per-sample rows unchanged; a zero-padded partial batch and the shard's tail run singly
     w2.groups = max(1, int(groups))
@@ -207,9 +250,9 @@ def evaluate(model_dir, db_dir, subset_fn=None, layouts_fn=None, variables=None,
     flush(force_single=True)
 
     # global means (np.mean over every sample, eval.py:223): ONE all-reduce of per-key sums (+ finite-only sums / counts) + sample count
-    red = MetricReducer(METRIC_KEYS, device=net.device if world > 1 and torch.cuda.is_available() and
+    red = MetricReducer(keys, device=net.device if world > 1 and torch.cuda.is_available() and
                         torch.distributed.get_backend() != 'gloo' else None)
-    rows = np.asarray(ev.rows, np.float64).reshape(-1, len(METRIC_KEYS))
+    rows = np.asarray(ev.rows, np.float64).reshape(-1, len(keys))
     red.add_rows(rows)
     means, count = red.reduce()
     # per-sample rows to rank 0 (eval.py:210-215 file format); ranks hold consecutive batch ranges, so rank order = global order
@@ -223,7 +266,7 @@ def evaluate(model_dir, db_dir, subset_fn=None, layouts_fn=None, variables=None,
         eval_fn = os.path.join(model_dir, 'eval-detailed.txt')
         assert overwrite or not os.path.exists(eval_fn), 'Evaluation file already exists.'
         with open(eval_fn, 'w') as f:
-            f.write('SampleID | {}\n'.format(' '.join(METRIC_KEYS)))
+            f.write('SampleID | {}\n'.format(' '.join(keys)))
             for ids_r, rows_r in zip(all_ids, all_rows):
                 for sid, row in zip(ids_r, rows_r):
                     f.write('{} | {}\n'.format(sid, ' '.join(str(v) for v in row)))
@@ -239,10 +282,10 @@ def evaluate(model_dir, db_dir, subset_fn=None, layouts_fn=None, variables=None,
         if dropped:
             print('EVAL | %d trailing windows (a partial batch of %d) were not evaluated' % (dropped, BATCH_SIZE))
     evaluate.last_maps = ev.maps
-    return OrderedDict((k, means[k]) for k in METRIC_KEYS), count
+    return OrderedDict((k, means[k]) for k in keys), count
 
 
-def main(argv=None):
+def arg_parser():
     import argparse
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument('model_dir')
@@ -257,11 +300,19 @@ def main(argv=None):
     ap.add_argument('--power_maps', action='store_true',
                     help='also compute the per-sample directional RMS maps of prediction and ground truth on the device (the inputs of the '
                          "reference's EMD metric, eval.py:188-191) and save this rank's maps to <model_dir>/eval-powermaps-rank<r>.npz")
-    args = ap.parse_args(argv)
+    ap.add_argument('--all_metrics', action='store_true',
+                    help="write all 28 columns of the reference's eval.py (ALL_METRIC_KEYS): adds mel_lsd, env_mse and emd/dir, emd/dir2, "
+                         'computed on the device')
+    return ap
+
+
+def main(argv=None):
+    args = arg_parser().parse_args(argv)
     from .deploy import load_params, require_first_order
     require_first_order(load_params(args.model_dir).ambi_order, 'evaluate')
     means, count = evaluate(args.model_dir, args.db_dir, args.subset_fn, args.layouts_fn, overwrite=args.overwrite,
-                            partial_batch=args.partial_batch, power_maps=args.power_maps, groups=args.groups)
+                            partial_batch=args.partial_batch, power_maps=args.power_maps, groups=args.groups,
+                            all_metrics=args.all_metrics)
     if args.power_maps and evaluate.last_maps:
         maps = evaluate.last_maps                      # [pred, gt, pred, gt, ...] per batch, each [n, 7, 12]
         np.savez(os.path.join(args.model_dir, 'eval-powermaps-rank%d.npz' % int(os.environ.get('RANK', 0))),

@@ -159,6 +159,35 @@ def power_map_batched(ambi_wyzx, sh_matrix):
     return rms
 
 
+def eval_mel_env(pred, target):
+    """myutils.compute_lsd_dist / compute_envelope_dist (myutils.py:96-116) per window: pred / target [B, 4800, C] ->
+    (mel_lsd [B, C], env_mse [B, C])."""
+    pred, target = _f32(pred, 'pred'), _f32(target, 'target')
+    B, _, C_ = pred.shape
+    l = _lib.lib()
+    mel = torch.empty(B, C_, dtype=torch.float32, device=pred.device)
+    env = torch.empty(B, C_, dtype=torch.float32, device=pred.device)
+    scratch = _scratch(l.sagen_eval_mel_env_scratch_bytes(B, C_), pred.device)
+    check(l.sagen_eval_mel_env(_ptr(pred), _ptr(target), B, C_, _ptr(mel), _ptr(env), _ptr(scratch), scratch.numel() * 4, _stream()))
+    return mel, env
+
+
+def eval_emd(p_maps, q_maps, cost, not_converged=None):
+    """emd/dir, emd/dir2 (distance.py:100-143) of map pairs p / q [n, P] on cost [P, P] (fp64 device tensor,
+    ambisonics.angular_distance) -> [n, 2] fp64.  not_converged: an int32 device counter to add to (a fresh one is checked here)."""
+    p, q = _f32(p_maps, 'p_maps'), _f32(q_maps, 'q_maps')
+    n, P = p.shape
+    if not (isinstance(cost, torch.Tensor) and cost.dtype == torch.float64 and cost.shape == (P, P)):
+        raise TypeError('cost must be a [%d, %d] float64 tensor' % (P, P))
+    out = torch.empty(n, 2, dtype=torch.float64, device=p.device)
+    own = not_converged is None
+    nc = torch.zeros(1, dtype=torch.int32, device=p.device) if own else not_converged
+    check(_lib.lib().sagen_eval_emd(_ptr(p), _ptr(q.contiguous()), n, P, _ptr(cost.contiguous()), _ptr(out), _ptr(nc), _stream()))
+    if own and int(nc.item()):
+        raise RuntimeError('eval_emd: %d EMD problems hit the solver\'s augmentation cap' % int(nc.item()))
+    return out
+
+
 def assemble_wyzx(audio, ambi_yzx, snd_contx=48000):
     """deploy.py:143-152: prepend W = mono[snd_contx/2 : snd_contx/2 + snd_dur]."""
     audio, ambi_yzx = _f32(audio, 'audio'), _f32(ambi_yzx, 'ambi')
