@@ -304,6 +304,26 @@ int sagen_eval_mel_env(const float* pred, const float* target, int batch, int ch
 int sagen_eval_emd(const float* p, const float* q, int n_maps, int nodes, const double* cost, double* emd, uint32_t* not_converged,
                    void* stream);
 
+/* ---- ambisonic rendering: one rotated FIR matrix ------------------------------------------------------------------------
+ * Every rendering of the reference's output stage is linear and time-invariant after an optional rotation of the sound field,
+ * so one operation replaces them all: the W+-Y stereo fold-down of myutils.gen_360video (myutils.py:285-294), AmbiDecoder.decode
+ * (pyutils/ambisonics/decoder.py:24-28), DirectAmbisonicBinauralizer (binauralizer.py:156-166) and AmbisonicBinauralizer
+ * (:124-153) over VirtualStereoMic.binauralize (:18-36) or Convolvotron.binauralize (:63-76) - the taps per rendering are built
+ * on the host (spatialaudiogen_amd/render.py).  For a stream x[s, c] of `channels` ambisonic channels (ACN / SN3D; 4 or 9):
+ *   x'[s]   = M(s) . x[s],   M(s) = (1 - a) R[m] + a R[min(m + 1, n_rot - 1)],
+ *             m = min(floor(s / rot_hop), n_rot - 1), a = (s - m rot_hop) / rot_hop, a = 0 once m = n_rot - 1 (the last
+ *             matrix is held exactly)                                                         (rot == NULL: M = I)
+ *   y[t, o] = sum_c sum_{k < ntaps} taps[o][c][k] x'[t - k, c],                               x'[s] = 0 for s < 0
+ * s, t are ABSOLUTE positions in the stream, so a stream may be rendered in pieces: x holds n_hist rows of history (the rows at
+ * positions pos0 - n_hist .. pos0 - 1, unrotated) followed by the n new rows at pos0 .. pos0 + n - 1; rows the taps reach
+ * before x[0] count as zero (n_hist < ntaps - 1 is legal at the start of a stream; n_hist <= pos0).  y [n, outputs]; outputs at
+ * absolute t < zero_before are written as 0 (Convolvotron places a 'valid' convolution at ntaps - 1).  taps [outputs][channels]
+ * [ntaps] and rot [n_rot][channels][channels] are device arrays.  fp32 throughout; the sum of one output sample runs in a fixed
+ * order (channels outermost, taps ascending, one accumulator), so its value does not depend on how the stream is cut.
+ * Supported: channels 4 or 9, outputs <= 32, ntaps <= 512 (SAGEN_ERR_UNSUPPORTED otherwise); a 4-channel x is 16-byte aligned. */
+int sagen_render_fir(const float* x, int64_t n_hist, int64_t n, int channels, const float* taps, int outputs, int ntaps, const float* rot,
+                     int n_rot, int rot_hop, int64_t pos0, int64_t zero_before, float* y, void* stream);
+
 /* ---- training step (reference train.py:137-236) -------------------------------------------------------
  * Loss of the reference: losses['stft/mse'] = metrics['stft/avg'] (model.py:156-159, 122-127; stft_for_loss myutils.py:151-178).
  * pred / target [B,4800,3]; mask [B,3] channel mask (the Y,Z,X columns of the feeder's [B,4] W,Y,Z,X mask, train.py:127) or NULL;

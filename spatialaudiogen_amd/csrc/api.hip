@@ -458,6 +458,23 @@ int sagen_eval_emd(const float* p, const float* q, int n_maps, int nodes, const 
     return evalx_emd_launch(p, q, n_maps, nodes, cost, emd, (unsigned int*)not_converged, (hipStream_t)stream);
 }
 
+int sagen_render_fir(const float* x, int64_t n_hist, int64_t n, int channels, const float* taps, int outputs, int ntaps, const float* rot,
+                     int n_rot, int rot_hop, int64_t pos0, int64_t zero_before, float* y, void* stream) {
+    if (!x || !taps || !y) return fail(SAGEN_ERR_NULL, "sagen_render_fir: null argument");
+    if (n_hist < 0 || n <= 0 || channels <= 0 || outputs <= 0 || ntaps <= 0 || pos0 < 0)
+        return fail(SAGEN_ERR_SHAPE, "sagen_render_fir: n_hist=%ld n=%ld channels=%d outputs=%d ntaps=%d pos0=%ld", (long)n_hist, (long)n,
+                    channels, outputs, ntaps, (long)pos0);
+    if (n_hist > pos0) return fail(SAGEN_ERR_SHAPE, "sagen_render_fir: %ld rows of history before position %ld", (long)n_hist, (long)pos0);
+    if (rot && (n_rot <= 0 || rot_hop <= 0)) return fail(SAGEN_ERR_SHAPE, "sagen_render_fir: n_rot=%d rot_hop=%d", n_rot, rot_hop);
+    if (channels != 4 && channels != 9)
+        return fail(SAGEN_ERR_UNSUPPORTED, "sagen_render_fir: channels=%d (supported: 4 and 9, ambisonic orders 1 and 2)", channels);
+    if (outputs > 32) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_render_fir: outputs=%d (supported: <= 32)", outputs);
+    if (ntaps > 512) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_render_fir: ntaps=%d (supported: <= 512)", ntaps);
+    if (n > ((int64_t)1 << 40)) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_render_fir: n=%ld rows in one call", (long)n);
+    if (channels == 4 && ((uintptr_t)x) % 16) return fail(SAGEN_ERR_SHAPE, "sagen_render_fir: a 4-channel x must be 16-byte aligned");
+    return render_fir_launch(x, n_hist, n, channels, taps, outputs, ntaps, rot, n_rot, rot_hop, pos0, zero_before, y, (hipStream_t)stream);
+}
+
 int sagen_stft_loss_grad(const float* pred_yzx, const float* target_yzx, const float* mask, int batch, float* grad, double* loss,
                          void* stream) {
     if (!pred_yzx || !target_yzx || (!grad && !loss)) return fail(SAGEN_ERR_NULL, "sagen_stft_loss_grad: null argument");

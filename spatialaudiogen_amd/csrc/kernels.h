@@ -362,6 +362,12 @@ int evalx_emd_launch(const float* p, const float* q, int n_maps, int nodes, cons
                      hipStream_t s);
 
 // -----------------------------------------------------------------------------------------
+// ambisonic rendering (render.hip): the rotated FIR matrix of include/sagen.h (sagen_render_fir), channels 4 or 9
+// -----------------------------------------------------------------------------------------
+int render_fir_launch(const float* x, long long n_hist, long long n, int channels, const float* taps, int outputs, int ntaps,
+                      const float* rot, int n_rot, int rot_hop, long long pos0, long long zero_before, float* y, hipStream_t s);
+
+// -----------------------------------------------------------------------------------------
 // training-step pieces (train.hip): stft loss + gradient w.r.t. the prediction, fused Adam over a flat bucket
 // -----------------------------------------------------------------------------------------
 int stft_loss_grad_launch(const float* pred, const float* gt, const float* mask, int B, float* grad, double* loss, hipStream_t s);

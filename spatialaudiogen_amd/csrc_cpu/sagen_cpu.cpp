@@ -330,6 +330,48 @@ int sagen_assemble_wyzx(const float* audio, const float* ambi_yzx, float* out_wy
     return SAGEN_OK;
 }
 
+/* The rotated FIR matrix of the renderings (include/sagen.h: sagen_render_fir; binauralizer.py:18-36, 63-76, 124-166, decoder.py:24-28,
+ * myutils.py:289): rotate every row by the matrix interpolated at its absolute position, then the direct-form sum in double */
+int sagen_render_fir(const float* x, int64_t n_hist, int64_t n, int channels, const float* taps, int outputs, int ntaps, const float* rot,
+                     int n_rot, int rot_hop, int64_t pos0, int64_t zero_before, float* y, void*) {
+    if (!x || !taps || !y) return fail(SAGEN_ERR_NULL, "sagen_render_fir: null argument");
+    if (n_hist < 0 || n <= 0 || channels <= 0 || outputs <= 0 || ntaps <= 0 || pos0 < 0 || n_hist > pos0)
+        return fail(SAGEN_ERR_SHAPE, "sagen_render_fir: bad sizes");
+    if (rot && (n_rot <= 0 || rot_hop <= 0)) return fail(SAGEN_ERR_SHAPE, "sagen_render_fir: n_rot=%d rot_hop=%d", n_rot, rot_hop);
+    if ((channels != 4 && channels != 9) || outputs > 32 || ntaps > 512)
+        return fail(SAGEN_ERR_UNSUPPORTED, "sagen_render_fir: channels=%d outputs=%d ntaps=%d", channels, outputs, ntaps);
+    const int C = channels;
+    const int64_t rows = n_hist + n;
+    std::vector<double> xr((size_t)rows * C);
+    for (int64_t r = 0; r < rows; ++r) {
+        const int64_t s = pos0 - n_hist + r;
+        for (int c = 0; c < C; ++c) {
+            if (!rot) {
+                xr[r * C + c] = x[r * C + c];
+                continue;
+            }
+            const int64_t m = std::min<int64_t>(s / rot_hop, n_rot - 1), m1 = std::min<int64_t>(m + 1, n_rot - 1);
+            const double al = m1 == m ? 0.0 : (double)(s - m * rot_hop) / (double)rot_hop;      // the last matrix is held
+            double v = 0.0;
+            for (int e = 0; e < C; ++e)
+                v += ((1.0 - al) * (double)rot[(m * C + c) * C + e] + al * (double)rot[(m1 * C + c) * C + e]) * (double)x[r * C + e];
+            xr[r * C + c] = v;
+        }
+    }
+    for (int64_t i = 0; i < n; ++i)
+        for (int o = 0; o < outputs; ++o) {
+            double acc = 0.0;
+            for (int c = 0; c < C; ++c)
+                for (int k = 0; k < ntaps; ++k) {
+                    const int64_t r = n_hist + i - k;
+                    if (r < 0) break;
+                    acc += (double)taps[((size_t)o * C + c) * ntaps + k] * xr[r * C + c];
+                }
+            y[i * outputs + o] = pos0 + i < zero_before ? 0.f : (float)acc;
+        }
+    return SAGEN_OK;
+}
+
 // emd/dir, emd/dir2 (distance.py:100-143): the solver core of the device kernel (csrc/emd_core.h) run by one host "lane"
 int sagen_eval_emd(const float* p, const float* q, int n_maps, int nodes, const double* cost, double* emd, uint32_t* not_converged, void*) {
     if (!p || !q || !cost || !emd || !not_converged) return fail(SAGEN_ERR_NULL, "sagen_eval_emd: null argument");

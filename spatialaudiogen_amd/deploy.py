@@ -193,13 +193,25 @@ class W2XYZ(object):
     def deploy(self, input_folder, deploy_start=0., deploy_duration=10., prefetch=True):
         """deploy.py:90-152.  `input_folder` is a clip directory (or a ClipArrays).  Returns
         [n_windows*snd_dur, 4] = W,Y,Z,X."""
+        return self._deploy(input_folder, deploy_start, deploy_duration, prefetch, None)[0]
+
+    def deploy_and_render(self, input_folder, deploy_start=0., deploy_duration=10., renderer=None, prefetch=True):
+        """deploy() plus the rendering the reference's --save_video path ends in (myutils.py:285-294; binauralizer.py): every forward
+        call's W,Y,Z,X rows go through renderer.process (render.Renderer) on the device, in stream order, before the copy to the
+        host.  Returns (ambi [N, 4] - the bits deploy() returns -, rendered [N, renderer.outputs])."""
+        if renderer is None or renderer.channels != 4:
+            raise ValueError('deploy_and_render needs a render.Renderer over 4 channels (W,Y,Z,X)')
+        renderer.reset()
+        return self._deploy(input_folder, deploy_start, deploy_duration, prefetch, renderer)
+
+    def _deploy(self, input_folder, deploy_start, deploy_duration, prefetch, renderer):
         import torch
         from . import ops
         from .feeder import BatchPrefetcher, frames_to_float
         p, m = self.params, self.model
         reader = self._reader(input_folder, deploy_start, deploy_duration)
         if not reader.chunks_t:
-            return np.zeros((0, 4), np.float32)
+            return np.zeros((0, 4), np.float32), np.zeros((0, renderer.outputs if renderer else 0), np.float32)
         dt = reader.chunks_t[0] - deploy_start                           # deploy.py:106-107
         reader.chunks_t = [t - dt for t in reader.chunks_t]
         use_v, use_f = VIDEO in p.encoders, FLOW in p.encoders
@@ -231,7 +243,7 @@ class W2XYZ(object):
                 yield out
 
         src = BatchPrefetcher(batches(), depth=2 * max(1, self.groups), pin=True) if prefetch else batches()
-        outs = []
+        outs, rendered = [], []
         G = max(1, int(self.groups))
         mg = self._grouped_model(G) if G > 1 else None
 
@@ -241,8 +253,12 @@ class W2XYZ(object):
             # deploy.py:141 - with the fp16x2 guard: a batch whose trunk planes clamped anything is re-run on bf16 planes
             pred = net.inference_ops_checked(a_dev, cat('video'), cat('flow'), on_saturation=self.on_saturation)
             wyzx = ops.assemble_wyzx(a_dev[:, :, 0].contiguous(), pred, m.snd_contx)   # deploy.py:143-152
-            for i, b in enumerate(bs):
-                outs.append(wyzx[i * self.batch_size:i * self.batch_size + b['n']].reshape(b['n'] * m.snd_dur, 4).cpu().numpy())
+            rows = [wyzx[i * self.batch_size:i * self.batch_size + b['n']].reshape(b['n'] * m.snd_dur, 4) for i, b in enumerate(bs)]
+            if renderer is not None:    # one call for everything this forward produced, in stream order, only the valid windows of a partial batch
+                valid = rows[0] if len(rows) == 1 else (wyzx.reshape(-1, 4) if all(b['n'] == self.batch_size for b in bs) else torch.cat(rows, 0))
+                rendered.append(renderer.process(valid).cpu().numpy())
+            for r in rows:
+                outs.append(r.cpu().numpy())
 
         pending = []
         groupable = lambda b: b['n'] == self.batch_size and all(b[k].dtype == pending[0][k].dtype for k in ('video', 'flow') if k in b)
@@ -259,7 +275,7 @@ class W2XYZ(object):
             run(m, [b])
         for q in pending:
             run(m, [q])
-        return np.concatenate(outs, 0)
+        return np.concatenate(outs, 0), (np.concatenate(rendered, 0) if renderer is not None else None)
 
     def _grouped_model(self, G):
         """A second facade over the SAME device variables whose native contexts carry G batches per call (SptAudioGen(groups=G))."""
@@ -273,7 +289,8 @@ class W2XYZ(object):
 
 
 def parse_arguments(argv=None):
-    """deploy.py:14-38 (the ffmpeg / 360-video outputs are outside this path; the ambisonic wav is written)."""
+    """deploy.py:14-38 (the ffmpeg muxing of the 360 video is outside this path; the ambisonic wav is written, and --render adds the
+    audio the reference's --save_video path ends in, rendered on the device: render.py)."""
     import argparse
     parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     parser.add_argument('model_dir', help='Directory containing model snapshot.')
@@ -285,9 +302,14 @@ def parse_arguments(argv=None):
     parser.add_argument('--groups', type=int, default=1,
                         help='batches of 10 windows per forward call (grouped launch: one launch per layer for all of them, each batch with '
                              'its own batch-norm statistics; output bit-identical to 1)')
+    from .render import add_render_arguments
+    add_render_arguments(parser)
+    parser.add_argument('--render_fn', default=None, help='Output wav of --render.')
     args = parser.parse_args(argv)
     if args.deploy_duration <= 0:
         args.deploy_duration = None
+    if (args.render is None) != (args.render_fn is None):
+        parser.error('--render and --render_fn come together')
     return args
 
 
@@ -295,14 +317,27 @@ def main(argv=None):
     """deploy.py:155-198 up to save_wav."""
     import torch
     from .feeder import save_wav
+    from . import render
     args = parse_arguments(argv)
-    require_first_order(load_params(args.model_dir).ambi_order, 'deploy')
+    params = load_params(args.model_dir)
+    require_first_order(params.ambi_order, 'deploy')
+    render.check_render_arguments(args, 4, 'deploy')
+    rendering = render.rendering_from_arguments(args, 4, params.audio_rate, 'deploy') if args.render else None   # host only (HRIR files, refusals)
     torch.cuda.set_device(args.gpu)
+    renderer = render.Renderer(*rendering) if rendering else None
     model = W2XYZ(args.model_dir)
     model.groups = max(1, args.groups)
-    ambi_pred = model.deploy(args.input_folder, args.deploy_start, args.deploy_duration)
+    if renderer is None:
+        ambi_pred = model.deploy(args.input_folder, args.deploy_start, args.deploy_duration)
+    else:
+        ambi_pred, rendered = model.deploy_and_render(args.input_folder, args.deploy_start, args.deploy_duration, renderer)
     save_wav(args.output_fn, ambi_pred, model.params.audio_rate)
     print('wrote %s: %d samples x 4 channels (ACN W,Y,Z,X / SN3D)' % (args.output_fn, ambi_pred.shape[0]))
+    if renderer is not None:
+        if args.normalize is not None:
+            rendered = render.normalize_peak(rendered, args.normalize)
+        save_wav(args.render_fn, rendered, model.params.audio_rate)
+        print('wrote %s: %d samples x %d channels (%s)' % (args.render_fn, rendered.shape[0], rendered.shape[1], args.render))
 
 
 if __name__ == '__main__':

@@ -198,6 +198,27 @@ def assemble_wyzx(audio, ambi_yzx, snd_contx=48000):
     return out
 
 
+def render_fir(x, n_hist, taps, rot=None, rot_hop=4800, pos0=0, zero_before=0):
+    """The rotated FIR matrix of the renderings (include/sagen.h: sagen_render_fir; render.py builds the taps): x [n_hist + n, C] =
+    n_hist rows of history then the n new rows at absolute positions pos0 .., taps [O, C, K], rot [n_rot, C, C] or None -> y [n, O];
+    outputs at absolute positions < zero_before are zero."""
+    x, taps = _f32(x, 'x'), _f32(taps, 'taps')
+    if x.dim() != 2 or taps.dim() != 3 or taps.shape[1] != x.shape[1]:
+        raise ValueError('render_fir: x [rows, C] and taps [O, C, K] expected')
+    n = x.shape[0] - int(n_hist)
+    O, C_, K = taps.shape
+    n_rot = 0
+    if rot is not None:
+        rot = _f32(rot, 'rot')
+        if rot.dim() != 3 or tuple(rot.shape[1:]) != (C_, C_):
+            raise ValueError('render_fir: rot [n_rot, C, C] expected')
+        n_rot = rot.shape[0]
+    y = torch.empty(max(n, 0), O, dtype=torch.float32, device=x.device)
+    check(_lib.lib().sagen_render_fir(_ptr(x), int(n_hist), n, C_, _ptr(taps), O, K, _ptr(rot), n_rot, int(rot_hop), int(pos0),
+                                      int(zero_before), _ptr(y), _stream()))
+    return y
+
+
 # ---- backward, op level (the gradients tf.gradients builds for the wrappers above; include/sagen.h) -----------------------
 def wgrad(g, d, kh, kw, stride=(1, 1), origin=(0, 0), split=True):
     """dw[th,tw,cg,cd] = sum_{b,i,j} G[b, i*sh+th+h0, j*sw+tw+w0, :] (x) D[b,i,j,:].  conv_2d: G = x, D = dy, origin = -pad_before

@@ -1,0 +1,282 @@
+"""The renderings on the device (csrc/render.hip through ops.render_fir / render.Renderer) against the fp64 oracle's long form
+(tests/render_oracle.py), and the drivers on top: W2XYZ.deploy_and_render and the two command lines.
+
+Bar: relative RMS error <= 1e-5 against the oracle.  Basis: an fp32 restatement on the CPU with one sequential accumulator
+(K = 200, C = 4, O = 2, white noise, decaying random responses) measures 6.0e-7; 1e-5 leaves 16x for another order of summation
+and is still 10x under the project's 1e-4 bar.  A stream cut into pieces must equal the one-call result BIT FOR BIT.
+
+The op-level cases (OP_CASES) also run against the CPU twin in a container without a GPU (tests/test_cpu_twin_render.py)."""
+import os
+
+import numpy as np
+import pytest
+
+import render_oracle as RO
+from util import rel_rms_err, ensure_lib
+
+pytestmark = pytest.mark.gpu
+
+BAR = 1e-5
+RATE = 48000
+OP_CASES = ('test_modes_match_oracle or test_rotation_static_and_trajectory or test_rotation_held_far_into_a_stream or test_lengths or '
+            'test_stream_in_pieces_is_bit_identical')
+
+
+def _dev():
+    from spatialaudiogen_amd import _lib
+    ensure_lib()
+    if _lib.IS_CPU_TWIN:
+        return 'cpu'
+    import torch
+    assert torch.cuda.is_available()
+    return 'cuda'
+
+
+def _signal(order, n, seed):
+    """Seeded noise plus a plane wave (a chirp from a fixed direction), fp32-representable."""
+    r = np.random.RandomState(seed)
+    C = (order + 1) ** 2
+    t = np.arange(n) / float(RATE)
+    x = 0.2 * r.normal(size=(n, C)) + RO.plane_wave(order, 0.7, -0.3, 0.5 * np.sin(2 * np.pi * (300. + 2000. * t) * t))
+    return x.astype(np.float32)
+
+
+def _hrirs():
+    return RO.make_hrirs(41)
+
+
+def _renderer(mode, order, rotation=None, rot_hop=4800, decode=None):
+    from spatialaudiogen_amd import render as R
+    dirs, left, right = _hrirs()
+    hset = R.HrirSet(dirs, left, right, RATE) if mode == 'hrir' else None
+    taps, zb = R.build_taps(mode, order, RATE, hrir=hset, decode=decode)
+    return R.Renderer(taps, zb, rotation, rot_hop, device=_dev()), taps, zb
+
+
+def _run(r, x, pieces=None):
+    import torch
+    r.reset()
+    xt = torch.as_tensor(x).to(r.device)
+    if pieces is None:
+        return r.process(xt).cpu().numpy()
+    out, i = [], 0
+    for p in pieces:
+        out.append(r.process(xt[i:i + p]).cpu().numpy())
+        i += p
+    assert i == x.shape[0]
+    return np.concatenate(out, 0)
+
+
+MODES = [('wy', 1), ('ears', 1), ('speakers', 1), ('mic', 1), ('hrir', 1), ('ears', 2), ('speakers', 2), ('mic', 2), ('hrir', 2)]
+
+
+@pytest.mark.parametrize('mode,order', MODES)
+def test_modes_match_oracle(mode, order):
+    x = _signal(order, 12000, 3 + order)
+    r, taps, zb = _renderer(mode, order)
+    got = _run(r, x)
+    ref = RO.render(mode, x.astype(np.float64), order, RATE, hrirs=_hrirs())
+    assert got.shape == ref.shape and got.dtype == np.float32
+    err = rel_rms_err(got, ref)
+    print('render %s order %d: rel rms err %.3g' % (mode, order, err))
+    assert err <= BAR
+    if mode == 'hrir':
+        assert not got[:zb].any() and got[zb:].any()
+
+
+@pytest.mark.parametrize('order', [1, 2])
+@pytest.mark.parametrize('kind,hop', [('static', 4800), ('trajectory', 4800), ('trajectory', 1000)])
+def test_rotation_static_and_trajectory(order, kind, hop):
+    """The rotated FIR matrix per its definition: one matrix, and a trajectory of control points `hop` samples apart that ends before
+    the stream does (the last matrix is held)."""
+    n = 24000
+    x = _signal(order, n, 9)
+    if kind == 'static':
+        rot = RO.head_rotation(order, 40., -15., 25.)
+    else:
+        k = np.arange(n // hop - 1)                 # 4 control points at hop 4800, 23 at hop 1000; the first is not the identity
+        assert len(k) >= 4
+        rot = np.stack([RO.head_rotation(order, 25. + 20. * i, 5. * i - 10., 15. - 3. * i) for i in k], 0)
+    for mode in ('hrir', 'speakers'):
+        r, taps, zb = _renderer(mode, order, rotation=rot, rot_hop=hop)
+        got = _run(r, x)
+        ref = RO.rotated_fir(x, np.asarray(taps, np.float32), np.asarray(rot, np.float32), hop, zb)
+        err = rel_rms_err(got, ref)
+        print('rotation %s hop %d %s order %d: rel rms err %.3g' % (kind, hop, mode, order, err))
+        assert err <= BAR
+        # and the rotation itself against the long form: rotate the field in fp64, then render the long way
+        if kind == 'static':
+            full = RO.render(mode, x.astype(np.float64) @ np.asarray(rot, np.float64).T, order, RATE, hrirs=_hrirs())
+            assert rel_rms_err(got, full) <= BAR
+
+
+@pytest.mark.parametrize('order', [1, 2])
+@pytest.mark.parametrize('n_rot', [1, 3])
+def test_rotation_held_far_into_a_stream(order, n_rot):
+    """Ten minutes into a stream the last control matrix is HELD: the rotated rows must be as accurate as at the start.  (A weight
+    (s - m hop) / hop left to grow past the last control point makes (1 - a) R + a R lose |a| 2^-24 in fp32: 1e-4 after ten minutes.)
+    Through ops.render_fir at pos0 = 48 000 x 600 with K - 1 = 199 rows of history, against the definition at that position."""
+    import torch
+    from spatialaudiogen_amd import ops, render as R
+    dev = _dev()
+    pos0, n_hist, n = 48000 * 600, 199, 6000
+    x = _signal(order, n_hist + n, 31)
+    rot = np.stack([RO.head_rotation(order, 30. + 40. * i, 10. - 5. * i, -5. + 9. * i) for i in range(n_rot)], 0).astype(np.float32)
+    dirs, left, right = _hrirs()
+    taps, zb = R.build_taps('hrir', order, RATE, hrir=R.HrirSet(dirs, left, right, RATE))
+    taps = np.asarray(taps, np.float32)
+    got = ops.render_fir(torch.as_tensor(x).to(dev), n_hist, torch.as_tensor(taps).to(dev), torch.as_tensor(rot).to(dev), 4800, pos0, zb).cpu().numpy()
+    ref = RO.rotated_fir(x, taps, rot, 4800, zb, pos0=pos0 - n_hist)[n_hist:]
+    err = rel_rms_err(got, ref)
+    print('held rotation, %d control point(s), order %d, 10 min into the stream: rel rms err %.3g' % (n_rot, order, err))
+    assert got.shape == (n, 2) and err <= BAR
+    # and the same rows rendered at the start of a stream past the trajectory's end: the held matrix is position-independent
+    if n_rot == 1:
+        early = ops.render_fir(torch.as_tensor(x).to(dev), n_hist, torch.as_tensor(taps).to(dev), torch.as_tensor(rot).to(dev), 4800, 48000, zb).cpu().numpy()
+        assert np.array_equal(early.view(np.uint32), got.view(np.uint32))
+
+
+@pytest.mark.parametrize('n', [1, 198, 4800, 48007])
+@pytest.mark.parametrize('order', [1, 2])
+def test_lengths(order, n):
+    """n in {1, K - 2, 4800, 48 000 + 7} (K = 200)."""
+    x = _signal(order, n, 17 + n % 5)
+    for mode in ('hrir', 'mic'):
+        r, taps, zb = _renderer(mode, order)
+        got = _run(r, x)
+        ref = RO.render(mode, x.astype(np.float64), order, RATE, hrirs=_hrirs())
+        assert got.shape == (n, 2)
+        if not ref.any():                       # shorter than the rendering's latency: silence, exactly
+            assert not got.any()
+        else:
+            assert rel_rms_err(got, ref) <= BAR
+
+
+@pytest.mark.parametrize('mode,order,rotated', [('hrir', 1, False), ('hrir', 1, True), ('hrir', 2, True), ('mic', 2, False), ('ears', 1, True)])
+def test_stream_in_pieces_is_bit_identical(mode, order, rotated):
+    n = 30011
+    x = _signal(order, n, 23)
+    rot = np.stack([RO.head_rotation(order, 33. * i, -7. * i, 4. * i) for i in range(5)], 0) if rotated else None
+    r, taps, zb = _renderer(mode, order, rotation=rot, rot_hop=4800)
+    whole = _run(r, x)
+    pieces = [1, 197, 2, 1024, 4800, 1023, 1, 199, 7000, 513, 48]
+    pieces.append(n - sum(pieces))
+    assert pieces[-1] > 0
+    cut = _run(r, x, pieces)
+    assert np.array_equal(whole.view(np.uint32), cut.view(np.uint32))
+    assert np.array_equal(whole.view(np.uint32), _run(r, x, [4800] * 6 + [n - 28800]).view(np.uint32))
+    ref = RO.rotated_fir(x, np.asarray(taps, np.float32), None if rot is None else np.asarray(rot, np.float32), 4800, zb)
+    assert rel_rms_err(whole, ref) <= BAR
+
+
+# ---- driver level (needs the device) ----------------------------------------------------------------------------------------------
+class Params(object):
+    ambi_order, audio_rate, video_rate, context, sample_dur = 1, 48000, 10, 1.0, 0.1
+    separation, num_sep_tracks, fft_window = 'unet_mask', 32, 0.025
+    context_units, freq_mask_units, loc_units = [64, 128, 128], [], [512, 512]
+
+    def __init__(self, encoders):
+        self.encoders = encoders
+
+
+def test_deploy_and_render_matches_deploy_and_the_oracle():
+    """A 12 s clip deployed for 10 s = 95 windows, the last batch partial (5 real + 5 zero windows): only the valid rows may reach
+    the renderer.  ambi is bit-identical to deploy(); rendered matches the oracle applied to that ambi; groups 1 and 3 agree bitwise."""
+    import torch
+    assert torch.cuda.is_available()
+    ensure_lib()
+    from spatialaudiogen_amd import render as R
+    from spatialaudiogen_amd.deploy import W2XYZ, ClipArrays
+    from spatialaudiogen_amd.weights import variable_specs, init_weights
+    from util import rng
+    enc = ['audio']
+    audio = (0.3 * rng(12).normal(size=(12 * 48000, 4))).astype(np.float32)
+    model = W2XYZ(params=Params(enc), variables=init_weights(variable_specs(enc), seed=4, mode='test'))
+    want = model.deploy(ClipArrays(audio), 0., 10.)
+    assert want.shape == (95 * 4800, 4)
+    dirs, left, right = _hrirs()
+    results = {}
+    for mode, rot in (('hrir', None), ('mic', R.head_trajectory(1, [0., 45., 90.], [0., 10., 0.]))):
+        taps, zb = R.build_taps(mode, 1, RATE, hrir=R.HrirSet(dirs, left, right, RATE))
+        renderer = R.Renderer(taps, zb, rot, 48000)
+        for groups in (1, 3):
+            model.groups = groups
+            ambi, rendered = model.deploy_and_render(ClipArrays(audio), 0., 10., renderer)
+            assert np.array_equal(ambi.view(np.uint32), want.view(np.uint32))
+            assert rendered.shape == (95 * 4800, 2) and rendered.dtype == np.float32
+            results[mode, groups] = rendered
+        assert np.array_equal(results[mode, 1].view(np.uint32), results[mode, 3].view(np.uint32))
+        ref = RO.rotated_fir(want, np.asarray(taps, np.float32), None if rot is None else np.asarray(rot, np.float32), 48000, zb)
+        assert rel_rms_err(results[mode, 1], ref) <= BAR
+    model.groups = 1
+    assert rel_rms_err(results['hrir', 1], RO.render_hrir(want.astype(np.float64), 1, dirs, left, right)) <= BAR
+    assert np.array_equal(model.deploy(ClipArrays(audio), 0., 10.).view(np.uint32), want.view(np.uint32))
+    with pytest.raises(ValueError):
+        model.deploy_and_render(ClipArrays(audio), 0., 10., None)
+
+
+def test_command_lines_end_to_end(tmp_path):
+    """deploy --render hrir and the render command line on temporary files: both write the rendering of the ambisonic wav the
+    deploy wrote (compared after the PCM16 quantisation of both files)."""
+    import torch
+    assert torch.cuda.is_available()
+    ensure_lib()
+    from test_feeder import make_clip
+    from spatialaudiogen_amd import deploy, feeder as F, render as R
+    from spatialaudiogen_amd.weights import variable_specs, init_weights
+    enc = ['audio']
+    model_dir = tmp_path / 'model'
+    model_dir.mkdir()
+    np.savez(str(model_dir / 'variables.npz'), **init_weights(variable_specs(enc), seed=8, mode='test'))
+    (model_dir / 'train-params.txt').write_text(
+        "encoders: ['audio']\nseparation: unet_mask\nambi_order: 1\naudio_rate: 48000\nvideo_rate: 10\ncontext: 1.0\n"
+        "num_sep_tracks: 32\nloc_units: [512, 512]\n")
+    clip_dir = str(tmp_path / 'clip')
+    make_clip(clip_dir, secs=4, video=False)
+    dirs, left, right = _hrirs()
+    RO.write_cipic_dir(str(tmp_path / 'hrir'), left, right, RATE)
+    ambi_fn, ren_fn, plain_fn = str(tmp_path / 'ambi.wav'), str(tmp_path / 'binaural.wav'), str(tmp_path / 'plain.wav')
+    deploy.main([str(model_dir), clip_dir, '--deploy_duration', '2.5', '--output_fn', plain_fn])
+    deploy.main([str(model_dir), clip_dir, '--deploy_duration', '2.5', '--output_fn', ambi_fn, '--render', 'hrir', '--render_fn', ren_fn,
+                 '--hrir_dir', str(tmp_path / 'hrir'), '--yaw', '30', '--groups', '2'])
+    assert open(plain_fn, 'rb').read() == open(ambi_fn, 'rb').read()                 # the ambisonic wav is written as before
+    ambi, rate = F.load_wav(ambi_fn)
+    got, rate2 = F.load_wav(ren_fn)
+    assert rate == rate2 == RATE and got.shape == (ambi.shape[0], 2) and ambi.shape[0] == 20 * 4800
+    # the rendering sees the UNQUANTISED prediction on the device: the same run in-process gives it, the oracle checks it, and the
+    # wav must be its PCM16 quantisation
+    hset = R.HrirSet.from_cipic_dir(str(tmp_path / 'hrir'))
+    taps, zb = R.build_taps('hrir', 1, RATE, hrir=hset)
+    model = deploy.W2XYZ(str(model_dir))
+    pred, rendered = model.deploy_and_render(clip_dir, 0., 2.5, R.Renderer(taps, zb, R.head_trajectory(1, [30.])))
+    lsb = 1.5 / 32768.          # save_wav writes rint(x * 32767), load_wav divides by 32768: |error| <= (0.5 + |x|) / 32768
+    assert np.abs(ambi - np.clip(pred, -1, 1)).max() <= lsb
+    ref = RO.render_hrir(pred.astype(np.float64) @ RO.head_rotation(1, 30.).T, 1, dirs, left, right)
+    err = rel_rms_err(rendered, ref)
+    print('deploy --render hrir: rel rms err %.3g' % err)
+    assert err <= BAR
+    K = left.shape[1]
+    assert np.abs(got - np.clip(rendered, -1, 1)).max() <= lsb and not got[:K - 1].any() and got[K - 1:].any()
+
+    # the render command line on the same ambisonic file: blocks of uneven size, mic rendering, peak normalisation, --overwrite
+    out_fn = str(tmp_path / 'mic.wav')
+    R.main([ambi_fn, out_fn, '--render', 'mic', '--normalize', '0.95', '--block', '7001'])
+    mic, _ = F.load_wav(out_fn)
+    ref = RO.render_mic(ambi, 1, RATE)
+    ref = ref * (0.95 / np.abs(ref).max())
+    assert mic.shape == ref.shape and np.abs(mic - ref).max() <= 2.5 / 32768.
+    with pytest.raises(SystemExit):
+        R.main([ambi_fn, out_fn, '--render', 'mic'])
+    R.main([ambi_fn, out_fn, '--render', 'hrir', '--hrir_dir', str(tmp_path / 'hrir'), '--overwrite'])
+    got2, _ = F.load_wav(out_fn)
+    ref2 = np.clip(RO.render_hrir(ambi, 1, dirs, left, right), -1, 1)
+    assert np.abs(got2 - ref2).max() <= 2.0 / 32768.
+
+    # second-order material through the render command line (no other command accepts it)
+    x9 = 0.05 * _signal(2, 9000, 5)
+    in9 = str(tmp_path / 'in9.wav')
+    F.save_wav(in9, x9, RATE, subtype='FLOAT')
+    R.main([in9, out_fn, '--render', 'speakers', '--decode', 'pseudoinv', '--overwrite'])
+    spk, _ = F.load_wav(out_fn)
+    ref9 = RO.render_speakers(x9.astype(np.float64), 2, None, 'pseudoinv')
+    assert spk.shape == (9000, 18) and np.abs(spk - np.clip(ref9, -1, 1)).max() <= 1.0 / 32768.
