@@ -383,6 +383,11 @@ int sagen_train_get_buffer(const sagen_ctx* ctx, const char* name, const float**
 size_t sagen_wgrad_scratch_bytes(int kh, int kw, int cg, int cd);
 int sagen_wgrad(const float* g, int batch, int hg, int wg, int cg, const float* d, int hd, int wd, int cd, int kh, int kw, int sh, int sw,
                 int h0, int w0, float* dw, void* scratch, size_t scratch_bytes, void* stream);
+/* Test accessor (host only, launches nothing): what sagen_wgrad would run for these arguments and a scratch of scratch_bytes
+ * (0 = none), as "<kernel><BM,BN> fold=F splitk=S" (just "wgrad_ref_kernel fold=1 splitk=1" under SAGEN_WGRAD_REF=1).
+ * buf: >= 64 bytes. */
+int sagen_wgrad_kernel_name(int batch, int hg, int wg, int cg, int hd, int wd, int cd, int kh, int kw, int sh, int sw, int h0, int w0,
+                            size_t scratch_bytes, char* buf, size_t buf_bytes);
 /* Input gradient of tfw.conv_2d (core.py:206): dy [B,hout,wout,cout], w HWIO -> dx [B,h,w,cin].  Stride 1: any padding; strided:
  * VALID, or SAME with no padding before (every strided conv of the path).  cout a power of two >= 4. */
 size_t sagen_conv2d_bwd_data_scratch_bytes(int kh, int kw, int cin, int cout, int sh, int sw);

@@ -94,6 +94,7 @@ SIGNATURES = {
     'sagen_train_set_grad_events': (C.c_int, [_P, C.POINTER(C.c_char_p), C.POINTER(C.c_int32), _I, C.POINTER(_P), _I]),
     'sagen_wgrad_scratch_bytes': (_SZ, [_I] * 4),
     'sagen_wgrad': (C.c_int, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _SZ, _P]),
+    'sagen_wgrad_kernel_name': (C.c_int, [_I] * 13 + [_SZ, C.c_char_p, _SZ]),
     'sagen_conv2d_bwd_data_scratch_bytes': (_SZ, [_I] * 6),
     'sagen_conv2d_bwd_data': (C.c_int, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _SZ, _P]),
     'sagen_bn_bwd_scratch_bytes': (_SZ, [_I]),

@@ -526,20 +526,38 @@ int sagen_train_get_buffer(const sagen_ctx* ctx, const char* name, const float**
 /* ---- backward, op level ---- */
 size_t sagen_wgrad_scratch_bytes(int kh, int kw, int cg, int cd) { return align_up((size_t)64 * kh * kw * cg * cd * sizeof(float), 256); }
 
+static WgradDesc wgrad_op_desc(const float* g, int batch, int hg, int wg, int cg, const float* d, int hd, int wd, int cd, int kh, int kw,
+                               int sh, int sw, int h0, int w0, float* dw, void* scratch, size_t scratch_bytes) {
+    WgradDesc w;
+    w.g = g; w.d = d; w.out = dw; w.B = batch; w.Hd = hd; w.Wd = wd; w.HG = hg; w.WG = wg; w.ldg = cg; w.Cg = cg; w.ldd = cd; w.Cd = cd;
+    w.g_rstride = (unsigned)((long)wg * cg); w.g_bstride = (unsigned)((long)hg * wg * cg);
+    w.d_rstride = (unsigned)((long)wd * cd); w.d_bstride = (unsigned)((long)hd * wd * cd);
+    w.sh = sh; w.sw = sw; w.TH = kh; w.TW = kw; w.h0 = h0; w.w0 = w0;
+    w.ws = (float*)scratch;
+    w.splitk = scratch ? wgrad_pick_splitk(w, scratch_bytes / sizeof(float)) : 1;
+    return w;
+}
+
 int sagen_wgrad(const float* g, int batch, int hg, int wg, int cg, const float* d, int hd, int wd, int cd, int kh, int kw, int sh, int sw,
                 int h0, int w0, float* dw, void* scratch, size_t scratch_bytes, void* stream) {
     return guarded([&]() -> int {
         if (!g || !d || !dw) return fail(SAGEN_ERR_NULL, "sagen_wgrad: null argument");
         if (cd % 4) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_wgrad: cd=%d must be a multiple of 4 at the op level (dense rows)", cd);
-        WgradDesc w;
-        w.g = g; w.d = d; w.out = dw; w.B = batch; w.Hd = hd; w.Wd = wd; w.HG = hg; w.WG = wg; w.ldg = cg; w.Cg = cg; w.ldd = cd; w.Cd = cd;
-        w.g_rstride = (unsigned)((long)wg * cg); w.g_bstride = (unsigned)((long)hg * wg * cg);
-        w.d_rstride = (unsigned)((long)wd * cd); w.d_bstride = (unsigned)((long)hd * wd * cd);
-        w.sh = sh; w.sw = sw; w.TH = kh; w.TW = kw; w.h0 = h0; w.w0 = w0;
-        w.ws = (float*)scratch;
-        w.splitk = scratch ? wgrad_pick_splitk(w, scratch_bytes / sizeof(float)) : 1;
+        WgradDesc w = wgrad_op_desc(g, batch, hg, wg, cg, d, hd, wd, cd, kh, kw, sh, sw, h0, w0, dw, scratch, scratch_bytes);
         return wgrad_launch(w, (hipStream_t)stream);
     });
+}
+
+/* host only: which kernel, tile, fold and number of pixel ranges sagen_wgrad runs for these arguments */
+int sagen_wgrad_kernel_name(int batch, int hg, int wg, int cg, int hd, int wd, int cd, int kh, int kw, int sh, int sw, int h0, int w0,
+                            size_t scratch_bytes, char* buf, size_t buf_bytes) {
+    if (!buf || buf_bytes < 64) return fail(SAGEN_ERR_NULL, "sagen_wgrad_kernel_name: buffer of >= 64 bytes needed");
+    if (batch <= 0 || hg <= 0 || wg <= 0 || cg <= 0 || hd <= 0 || wd <= 0 || cd <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0)
+        return fail(SAGEN_ERR_SHAPE, "sagen_wgrad_kernel_name: bad dimensions");
+    const WgradDesc w = wgrad_op_desc(nullptr, batch, hg, wg, cg, nullptr, hd, wd, cd, kh, kw, sh, sw, h0, w0, nullptr,
+                                      scratch_bytes ? (void*)buf : nullptr, scratch_bytes);
+    wgrad_describe(w, buf, buf_bytes);
+    return SAGEN_OK;
 }
 
 size_t sagen_conv2d_bwd_data_scratch_bytes(int kh, int kw, int cin, int cout, int sh, int sw) {

@@ -409,6 +409,7 @@ int wgrad_reduce_launch(const WgradDesc& d, hipStream_t s);
 // "wgrad3r_kernel" (bf16x3, one filter row per workgroup: dense 3x3 stride-1) | "wgrad3_kernel" (bf16x3, one tap) |
 // "wgrad_kernel" (exact fp32 MFMA) | "wgrad_ref_kernel"
 const char* wgrad_kernel_name(const WgradDesc& d);
+void wgrad_describe(const WgradDesc& d, char* buf, size_t n);       // name, tile, fold and pixel ranges of the launch (test accessor)
 bool wgrad_reads_fp32_operands();     // SAGEN_WGRAD_REF: the fp32 dy / activations must exist even where the planes do
 bool wgrad_planes_enabled();          // wgrad3h_kernel not switched off by the environment (exact fp32 / reference / SAGEN_WGRAD_NO_H2)
 

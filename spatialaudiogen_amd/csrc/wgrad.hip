@@ -32,6 +32,7 @@
 #else
 #define WG_MUL(a, b) __umul24((a), (b))
 #endif
+#include <cstdio>
 #include <cstdlib>
 
 namespace sagen {
@@ -740,6 +741,14 @@ static WgradShape wgrad_shape(const WgradDesc& d) {
                          : (long)d.TH * (w.row ? 1 : d.TW) * cdiv(d.Cg, w.bm) * cdiv(d.Cd, w.bn);
     w.nchunks = (P + 15) / 16;
     return w;
+}
+
+// what wgrad_launch would run for d (the op-level tests assert it per case): "<family><BM,BN> fold=F splitk=S"
+void wgrad_describe(const WgradDesc& d, char* buf, size_t n) {
+    const WgradShape w = wgrad_shape(d);
+    static const bool ref = getenv("SAGEN_WGRAD_REF") != nullptr;
+    if (ref) snprintf(buf, n, "wgrad_ref_kernel fold=1 splitk=1");
+    else snprintf(buf, n, "%s<%d,%d> fold=%d splitk=%d", wgrad_kernel_name(d), w.bm, w.bn, w.fold, std::max(1, d.splitk));
 }
 
 int wgrad_pick_splitk(const WgradDesc& d, size_t ws_capacity_floats) {

@@ -220,7 +220,16 @@ def render_fir(x, n_hist, taps, rot=None, rot_hop=4800, pos0=0, zero_before=0):
 
 
 # ---- backward, op level (the gradients tf.gradients builds for the wrappers above; include/sagen.h) -----------------------
-def wgrad(g, d, kh, kw, stride=(1, 1), origin=(0, 0), split=True):
+def _out(out, shape, like, name):
+    """The caller's output tensor (tests prefill it to see every element written) or a fresh one."""
+    if out is None:
+        return torch.empty(*shape, dtype=torch.float32, device=like.device)
+    if not (out.dtype == torch.float32 and out.device == like.device and tuple(out.shape) == tuple(shape) and out.is_contiguous()):
+        raise TypeError('%s must be a contiguous float32 tensor of shape %s on %s' % (name, tuple(shape), like.device))
+    return out
+
+
+def wgrad(g, d, kh, kw, stride=(1, 1), origin=(0, 0), split=True, out=None):
     """dw[th,tw,cg,cd] = sum_{b,i,j} G[b, i*sh+th+h0, j*sw+tw+w0, :] (x) D[b,i,j,:].  conv_2d: G = x, D = dy, origin = -pad_before
     -> HWIO; deconv_2d: G = dy, D = x -> [kh,kw,Cout,Cin]; fully_connected: 2-D G [M,K], D [M,N] -> [K,N]."""
     g, d = _f32(g, 'g'), _f32(d, 'd')
@@ -229,14 +238,14 @@ def wgrad(g, d, kh, kw, stride=(1, 1), origin=(0, 0), split=True):
     B, HG, WG, CG = g.shape
     _, HD, WD, CD = d.shape
     l = _lib.lib()
-    dw = torch.empty(kh, kw, CG, CD, dtype=torch.float32, device=g.device)
+    dw = _out(out, (kh, kw, CG, CD), g, 'out')
     scratch = _scratch(l.sagen_wgrad_scratch_bytes(kh, kw, CG, CD), g.device) if split else None
     check(l.sagen_wgrad(_ptr(g), B, HG, WG, CG, _ptr(d), HD, WD, CD, kh, kw, stride[0], stride[1], origin[0], origin[1], _ptr(dw),
                         _ptr(scratch), scratch.numel() * 4 if split else 0, _stream()))
     return dw
 
 
-def conv_2d_bwd_data(dy, weights, in_hw, stride=1, padding='SAME'):
+def conv_2d_bwd_data(dy, weights, in_hw, stride=1, padding='SAME', out=None):
     """Input gradient of conv_2d: dy [B,Ho,Wo,Cout], weights HWIO -> dx [B,H,W,Cin]."""
     dy, weights = _f32(dy, 'dy'), _f32(weights, 'weights')
     B, Ho, Wo, cout = dy.shape
@@ -245,23 +254,26 @@ def conv_2d_bwd_data(dy, weights, in_hw, stride=1, padding='SAME'):
     sh, sw = (stride, stride) if isinstance(stride, int) else stride
     H, W = in_hw
     l = _lib.lib()
-    dx = torch.empty(B, H, W, cin, dtype=torch.float32, device=dy.device)
+    dx = _out(out, (B, H, W, cin), dy, 'out')
     scratch = _scratch(l.sagen_conv2d_bwd_data_scratch_bytes(kh, kw, cin, cout, sh, sw), dy.device)
     check(l.sagen_conv2d_bwd_data(_ptr(dy), B, Ho, Wo, cout, _ptr(weights), kh, kw, cin, sh, sw, {'VALID': 0, 'SAME': 1}[padding], H, W,
                                   _ptr(dx), _ptr(scratch), scratch.numel() * 4, _stream()))
     return dx
 
 
-def bn_bwd(g, y, stats, gamma, beta, act=None, g2=None, eps=1e-3, want_dz=False):
+def bn_bwd(g, y, stats, gamma, beta, act=None, g2=None, eps=1e-3, want_dz=False, out=None):
     """Training-mode batch-norm backward at the raw conv output y [.., C] (stats from conv_2d(return_bn_stats=True)):
-    dz = (g + g2) * (act > 0) -> (dy, dgamma, dbeta[, dz])."""
+    dz = (g + g2) * (act > 0) -> (dy, dgamma, dbeta[, dz]).  out: optional (dy, dgamma, dbeta[, dz]) tensors to write into."""
     g, y = _f32(g, 'g'), _f32(y, 'y')
     C_ = y.shape[-1]
     npix = y.numel() // C_
-    dy = torch.empty_like(y)
-    dz = torch.empty_like(y) if want_dz else None
-    dgamma = torch.empty(C_, dtype=torch.float32, device=y.device)
-    dbeta = torch.empty(C_, dtype=torch.float32, device=y.device)
+    if out is not None and len(out) != (4 if want_dz else 3):
+        raise TypeError('out must be (dy, dgamma, dbeta%s)' % (', dz' if want_dz else ''))
+    out = out or (None,) * 4
+    dy = _out(out[0], y.shape, y, 'out[0]')
+    dz = _out(out[3], y.shape, y, 'out[3]') if want_dz else None
+    dgamma = _out(out[1], (C_,), y, 'out[1]')
+    dbeta = _out(out[2], (C_,), y, 'out[2]')
     scratch = torch.empty((int(_lib.lib().sagen_bn_bwd_scratch_bytes(C_)) + 7) // 8, dtype=torch.float64, device=y.device)
     check(_lib.lib().sagen_bn_bwd(_ptr(g), _ptr(g2), _ptr(act), _ptr(y), _ptr(stats), _ptr(_f32(gamma, 'gamma')), _ptr(_f32(beta, 'beta')), eps,
                                   npix, C_, _ptr(dy), _ptr(dz), _ptr(dgamma), _ptr(dbeta), _ptr(scratch), scratch.numel() * 8, _stream()))
