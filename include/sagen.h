@@ -324,6 +324,43 @@ int sagen_eval_emd(const float* p, const float* q, int n_maps, int nodes, const 
 int sagen_render_fir(const float* x, int64_t n_hist, int64_t n, int channels, const float* taps, int outputs, int ntaps, const float* rot,
                      int n_rot, int rot_hop, int64_t pos0, int64_t zero_before, float* y, void* stream);
 
+/* ---- power-map overlay: the sound-direction heat map over the video frames ---------------------------------------------
+ * The visual half of myutils.gen_360video(overlay_map=True) (myutils.py:246-279): RMS maps of the decimated stream
+ * (SphericalAmbisonicsVisualizer(ambix[::5], rate / 5, 5 / fps, 5.), pyutils/ambisonics/distance.py:16-59), normalised,
+ * interpolated between consecutive maps, coloured and alpha-blended over the frames.
+ *
+ * sagen_power_map_windows: the maps of a strided stream (distance.py:41-52 over myutils.py:252's ambix[::5]).
+ *   ambi [n_rows][channels] (ACN / SN3D; channels 4 or 9 = orders 1 and 2, SAGEN_ERR_UNSUPPORTED otherwise; a 4-channel ambi is
+ *   16-byte aligned); map m reads the rows (m window + k) stride, k < window; n_maps = ((n_rows + stride - 1) / stride) / window
+ *   (= len(ambix[::stride]) // window, distance.py:30); sh [p][channels] fp32 ('projection' decoding, decoder.py:24-28);
+ *   rms [n_maps][p] = sqrt(max(sh[p]^T S_m sh[p], 0) / window) in fp64, S_m the second moments of window m.  n_maps == 0 returns
+ *   SAGEN_OK and touches nothing.  A map depends on its own window only, so a stream may be cut at any window boundary.
+ *   scratch: >= sagen_power_map_windows_scratch_bytes(n_maps, channels) bytes, 8-byte aligned. */
+size_t sagen_power_map_windows_scratch_bytes(int n_maps, int channels);
+int sagen_power_map_windows(const float* ambi, int64_t n_rows, int channels, int stride, int64_t window, const float* sh, int p, float* rms,
+                            void* scratch, size_t scratch_bytes, void* stream);
+
+/* sagen_overlay_blend: myutils.py:255-279 for a run of frames.  maps [n_maps][mh][mw] raw rms maps in IMAGE orientation (top row
+ * +90 degrees elevation: the flipud of distance.py:52 is folded into the order of the sh rows), maps[0] being map `map0` of the
+ * stream; lut [256][3] fp64 device colour table (plt.cm.YlOrRd(linspace(0, 1, 256))[:, :3], myutils.py:253); frames / out
+ * [n_frames][h][w][3] uint8, frames[0] being frame `frame0` of the stream.  For the frame with absolute index F:
+ *   prev = F / frames_per_map, cur = prev + 1 (absolute map indices), beta = (F % frames_per_map) / (double)frames_per_map
+ *   n(map) = (map - min map) / (max map - min map + 0.005)                                   (myutils.py:256, 262; per map)
+ *   v = (1 - beta) n(prev) + beta n(cur);  v = v 2 - 0.7;  v = 0 where v < 0                 (:270-272)
+ *   idx = min(int(v 255), 255);  dir = resize(lut[idx], (h, w)) 255                          (:273-275)
+ *   alpha = resize(v, (h, w)) 0.6;  out = uint8(alpha dir + (1 - alpha) frame)               (:277-279)
+ * in fp64, in this operation order, without contraction.  resize is scikit-image 0.13.1's (order 1, mode 'constant', cval 0,
+ * clip) restated: source coordinates r = (y + 0.5)(mh / h) - 0.5, c = (x + 0.5)(mw / w) - 0.5; corners floor / ceil, a corner
+ * outside the map reads 0; top = (1 - dc) g(r0, c0) + dc g(r0, c1), bot likewise on r1, val = (1 - dr) top + dr bot; then with
+ * lo / hi the minimum / maximum of the array handed to resize (the three colour channels together; v): lo <= 0 <= hi clips val
+ * into [lo, hi], otherwise an exact 0 stays 0 and everything else is clipped into [lo, hi].
+ * A frame whose two maps are not both inside [map0, map0 + n_maps) is SAGEN_ERR_SHAPE; n_frames == 0 returns SAGEN_OK.
+ * Supported: mh <= 4096, mw <= 1000, h <= 65535, w <= 1048576, n_frames <= 65535.  scratch: >= sagen_overlay_blend_scratch_bytes(...) bytes,
+ * 16-byte aligned. */
+size_t sagen_overlay_blend_scratch_bytes(int n_maps, int mh, int mw, int n_frames);
+int sagen_overlay_blend(const float* maps, int n_maps, int64_t map0, int mh, int mw, const double* lut, const uint8_t* frames, int n_frames,
+                        int64_t frame0, int h, int w, int frames_per_map, uint8_t* out, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- training step (reference train.py:137-236) -------------------------------------------------------
  * Loss of the reference: losses['stft/mse'] = metrics['stft/avg'] (model.py:156-159, 122-127; stft_for_loss myutils.py:151-178).
  * pred / target [B,4800,3]; mask [B,3] channel mask (the Y,Z,X columns of the feeder's [B,4] W,Y,Z,X mask, train.py:127) or NULL;

@@ -82,6 +82,10 @@ SIGNATURES = {
     'sagen_eval_mel_env': (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _SZ, _P]),
     'sagen_eval_emd': (C.c_int, [_P, _P, _I, _I, _P, _P, _P, _P]),
     'sagen_render_fir': (C.c_int, [_P, _I64, _I64, _I, _P, _I, _I, _P, _I, _I, _I64, _I64, _P, _P]),
+    'sagen_power_map_windows_scratch_bytes': (_SZ, [_I, _I]),
+    'sagen_power_map_windows': (C.c_int, [_P, _I64, _I, _I, _I64, _P, _I, _P, _P, _SZ, _P]),
+    'sagen_overlay_blend_scratch_bytes': (_SZ, [_I] * 4),
+    'sagen_overlay_blend': (C.c_int, [_P, _I, _I64, _I, _I, _P, _P, _I, _I64, _I, _I, _I, _P, _P, _SZ, _P]),
     'sagen_stft_loss_grad': (C.c_int, [_P, _P, _P, _I, _P, _P, _P]),
     'sagen_adam_update': (C.c_int, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _P]),
     'sagen_power_map_batched': (C.c_int, [_P, _I, _I64, _P, _I, _P, _P, _P]),

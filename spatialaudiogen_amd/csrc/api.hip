@@ -475,6 +475,58 @@ int sagen_render_fir(const float* x, int64_t n_hist, int64_t n, int channels, co
     return render_fir_launch(x, n_hist, n, channels, taps, outputs, ntaps, rot, n_rot, rot_hop, pos0, zero_before, y, (hipStream_t)stream);
 }
 
+static int64_t overlay_n_maps(int64_t n_rows, int stride, int64_t window) { return ((n_rows + stride - 1) / stride) / window; }
+
+size_t sagen_power_map_windows_scratch_bytes(int n_maps, int channels) {
+    if (n_maps <= 0 || (channels != 4 && channels != 9)) return 0;
+    return (size_t)n_maps * (channels * (channels + 1) / 2) * sizeof(double);
+}
+
+int sagen_power_map_windows(const float* ambi, int64_t n_rows, int channels, int stride, int64_t window, const float* sh, int p, float* rms,
+                            void* scratch, size_t scratch_bytes, void* stream) {
+    if (n_rows < 0 || stride <= 0 || window <= 0 || p <= 0)
+        return fail(SAGEN_ERR_SHAPE, "sagen_power_map_windows: n_rows=%ld stride=%d window=%ld p=%d", (long)n_rows, stride, (long)window, p);
+    if (channels != 4 && channels != 9)
+        return fail(SAGEN_ERR_UNSUPPORTED, "sagen_power_map_windows: channels=%d (supported: 4 and 9, ambisonic orders 1 and 2)", channels);
+    const int64_t n_maps = overlay_n_maps(n_rows, stride, window);
+    if (n_maps == 0) return SAGEN_OK;                  // (before the pointers are looked at: an empty stream has none)
+    if (!ambi || !sh || !rms) return fail(SAGEN_ERR_NULL, "sagen_power_map_windows: null argument");
+    if (n_maps * ((p + 255) / 256) > (int64_t)0x7fffffff)
+        return fail(SAGEN_ERR_UNSUPPORTED, "sagen_power_map_windows: %ld maps of %d nodes in one call", (long)n_maps, p);
+    if (!scratch || scratch_bytes < sagen_power_map_windows_scratch_bytes((int)n_maps, channels))
+        return fail(SAGEN_ERR_WORKSPACE, "sagen_power_map_windows: scratch too small (%ld maps)", (long)n_maps);
+    if (((uintptr_t)scratch) % 8 || (channels == 4 && ((uintptr_t)ambi) % 16))
+        return fail(SAGEN_ERR_SHAPE, "sagen_power_map_windows: scratch must be 8-byte aligned, a 4-channel ambi 16-byte aligned");
+    return power_map_windows_launch(ambi, channels, stride, window, (int)n_maps, sh, p, rms, (double*)scratch, (hipStream_t)stream);
+}
+
+size_t sagen_overlay_blend_scratch_bytes(int n_maps, int mh, int mw, int n_frames) {
+    if (n_maps <= 0 || mh <= 0 || mw <= 0 || n_frames <= 0) return 0;
+    return overlay_blend_grid_bytes(mh, mw, n_frames) + (size_t)n_frames * 4 * sizeof(double);
+}
+
+int sagen_overlay_blend(const float* maps, int n_maps, int64_t map0, int mh, int mw, const double* lut, const uint8_t* frames, int n_frames,
+                        int64_t frame0, int h, int w, int frames_per_map, uint8_t* out, void* scratch, size_t scratch_bytes, void* stream) {
+    if (n_maps < 0 || map0 < 0 || mh <= 0 || mw <= 0 || n_frames < 0 || frame0 < 0 || h <= 0 || w <= 0 || frames_per_map <= 0)
+        return fail(SAGEN_ERR_SHAPE, "sagen_overlay_blend: n_maps=%d map0=%ld map %dx%d n_frames=%d frame0=%ld frame %dx%d frames_per_map=%d", n_maps,
+                    (long)map0, mh, mw, n_frames, (long)frame0, h, w, frames_per_map);
+    if (n_frames == 0) return SAGEN_OK;
+    if (!maps || !lut || !frames || !out) return fail(SAGEN_ERR_NULL, "sagen_overlay_blend: null argument");
+    // prev = F / frames_per_map grows with F: the first and the last frame decide
+    const int64_t first = frame0 / frames_per_map, last = (frame0 + n_frames - 1) / frames_per_map + 1;
+    if (first < map0 || last >= map0 + n_maps)
+        return fail(SAGEN_ERR_SHAPE, "sagen_overlay_blend: frames %ld..%ld need the maps %ld..%ld, given %ld..%ld", (long)frame0,
+                    (long)(frame0 + n_frames - 1), (long)first, (long)last, (long)map0, (long)(map0 + n_maps - 1));
+    if (mw > 1000 || mh > 4096 || h > 65535 || w > (1 << 20) || n_frames > 65535)
+        return fail(SAGEN_ERR_UNSUPPORTED, "sagen_overlay_blend: map %dx%d frame %dx%d n_frames=%d (supported: map <= 4096 x 1000, h, n_frames <= 65535, w <= 1048576)",
+                    mh, mw, h, w, n_frames);
+    if (!scratch || scratch_bytes < sagen_overlay_blend_scratch_bytes(n_maps, mh, mw, n_frames))
+        return fail(SAGEN_ERR_WORKSPACE, "sagen_overlay_blend: scratch too small");
+    if (((uintptr_t)scratch) % 16 || ((uintptr_t)lut) % 8)
+        return fail(SAGEN_ERR_SHAPE, "sagen_overlay_blend: scratch must be 16-byte aligned, lut 8-byte aligned");
+    return overlay_blend_launch(maps, map0, mh, mw, lut, frames, n_frames, frame0, h, w, frames_per_map, out, scratch, (hipStream_t)stream);
+}
+
 int sagen_stft_loss_grad(const float* pred_yzx, const float* target_yzx, const float* mask, int batch, float* grad, double* loss,
                          void* stream) {
     if (!pred_yzx || !target_yzx || (!grad && !loss)) return fail(SAGEN_ERR_NULL, "sagen_stft_loss_grad: null argument");

@@ -368,6 +368,17 @@ int render_fir_launch(const float* x, long long n_hist, long long n, int channel
                       const float* rot, int n_rot, int rot_hop, long long pos0, long long zero_before, float* y, hipStream_t s);
 
 // -----------------------------------------------------------------------------------------
+// power-map overlay (overlay.hip): sagen_power_map_windows / sagen_overlay_blend of include/sagen.h
+// -----------------------------------------------------------------------------------------
+// rms [n_maps][P] of the windows of a strided stream, channels 4 or 9; moments: n_maps * channels (channels + 1) / 2 doubles
+int power_map_windows_launch(const float* ambi, int channels, int stride, long long window, int n_maps, const float* sh, int P, float* rms,
+                             double* moments, hipStream_t s);
+// scratch of the blend: overlay_blend_grid_bytes() of per-node (r, g, b, v), then 4 doubles of clip bounds per frame
+size_t overlay_blend_grid_bytes(int mh, int mw, int n_frames);
+int overlay_blend_launch(const float* maps, long long map0, int mh, int mw, const double* lut, const uint8_t* frames, int n_frames,
+                         long long frame0, int h, int w, int frames_per_map, uint8_t* out, void* scratch, hipStream_t s);
+
+// -----------------------------------------------------------------------------------------
 // training-step pieces (train.hip): stft loss + gradient w.r.t. the prediction, fused Adam over a flat bucket
 // -----------------------------------------------------------------------------------------
 int stft_loss_grad_launch(const float* pred, const float* gt, const float* mask, int B, float* grad, double* loss, hipStream_t s);

@@ -372,6 +372,99 @@ int sagen_render_fir(const float* x, int64_t n_hist, int64_t n, int channels, co
     return SAGEN_OK;
 }
 
+/* The maps of a strided stream (include/sagen.h: sagen_power_map_windows; distance.py:41-52 over myutils.py:252's ambix[::5]): the
+ * definition itself, every node's projection squared and averaged in double */
+size_t sagen_power_map_windows_scratch_bytes(int n_maps, int channels) {
+    return n_maps > 0 && (channels == 4 || channels == 9) ? (size_t)n_maps * (channels * (channels + 1) / 2) * sizeof(double) : 0;
+}
+int sagen_power_map_windows(const float* ambi, int64_t n_rows, int channels, int stride, int64_t window, const float* sh, int p, float* rms,
+                            void*, size_t, void*) {
+    if (n_rows < 0 || stride <= 0 || window <= 0 || p <= 0) return fail(SAGEN_ERR_SHAPE, "sagen_power_map_windows: bad sizes");
+    if (channels != 4 && channels != 9) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_power_map_windows: channels=%d", channels);
+    const int64_t n_maps = ((n_rows + stride - 1) / stride) / window;
+    if (n_maps == 0) return SAGEN_OK;
+    if (!ambi || !sh || !rms) return fail(SAGEN_ERR_NULL, "sagen_power_map_windows: null argument");
+    for (int64_t m = 0; m < n_maps; ++m)
+        for (int d = 0; d < p; ++d) {
+            double s = 0.0;
+            for (int64_t k = 0; k < window; ++k) {
+                const float* row = ambi + (m * window + k) * stride * channels;
+                double v = 0.0;
+                for (int c = 0; c < channels; ++c) v += (double)row[c] * (double)sh[(size_t)d * channels + c];
+                s += v * v;
+            }
+            rms[m * p + d] = (float)std::sqrt(s / (double)window);
+        }
+    return SAGEN_OK;
+}
+
+/* myutils.py:255-279 for a run of frames (include/sagen.h: sagen_overlay_blend): whole arrays at a time, the way the reference's
+ * numpy does it - normalise the maps, mix, colour, resize (the header's restatement of scikit-image 0.13.1), blend, truncate */
+size_t sagen_overlay_blend_scratch_bytes(int n_maps, int mh, int mw, int n_frames) {
+    return n_maps > 0 && mh > 0 && mw > 0 && n_frames > 0 ? 256 : 0;
+}
+namespace {
+// resize of one [mh][mw][nc] array to [h][w][nc]
+std::vector<double> resize_bilinear(const std::vector<double>& a, int mh, int mw, int nc, int h, int w) {
+    const double lo = *std::min_element(a.begin(), a.end()), hi = *std::max_element(a.begin(), a.end());
+    const bool spans_zero = lo <= 0.0 && 0.0 <= hi;
+    auto get = [&](double i, double j, int k) { return i < 0 || i >= mh || j < 0 || j >= mw ? 0.0 : a[((size_t)i * mw + (size_t)j) * nc + k]; };
+    std::vector<double> o((size_t)h * w * nc);
+    for (int y = 0; y < h; ++y) {
+        const double r = (y + 0.5) * ((double)mh / h) - 0.5, r0 = std::floor(r), r1 = std::ceil(r), dr = r - r0;
+        for (int x = 0; x < w; ++x) {
+            const double c = (x + 0.5) * ((double)mw / w) - 0.5, c0 = std::floor(c), c1 = std::ceil(c), dc = c - c0;
+            for (int k = 0; k < nc; ++k) {
+                const double top = (1 - dc) * get(r0, c0, k) + dc * get(r0, c1, k);
+                const double bot = (1 - dc) * get(r1, c0, k) + dc * get(r1, c1, k);
+                double val = (1 - dr) * top + dr * bot;
+                if (spans_zero || val != 0.0) val = std::min(std::max(val, lo), hi);
+                o[((size_t)y * w + x) * nc + k] = val;
+            }
+        }
+    }
+    return o;
+}
+}  // namespace
+int sagen_overlay_blend(const float* maps, int n_maps, int64_t map0, int mh, int mw, const double* lut, const uint8_t* frames, int n_frames,
+                        int64_t frame0, int h, int w, int frames_per_map, uint8_t* out, void*, size_t, void*) {
+    if (n_maps < 0 || map0 < 0 || mh <= 0 || mw <= 0 || n_frames < 0 || frame0 < 0 || h <= 0 || w <= 0 || frames_per_map <= 0)
+        return fail(SAGEN_ERR_SHAPE, "sagen_overlay_blend: bad sizes");
+    if (n_frames == 0) return SAGEN_OK;
+    if (!maps || !lut || !frames || !out) return fail(SAGEN_ERR_NULL, "sagen_overlay_blend: null argument");
+    if (frame0 / frames_per_map < map0 || (frame0 + n_frames - 1) / frames_per_map + 1 >= map0 + n_maps)
+        return fail(SAGEN_ERR_SHAPE, "sagen_overlay_blend: the frames need maps outside %ld..%ld", (long)map0, (long)(map0 + n_maps - 1));
+    const int N = mh * mw;
+    std::vector<double> norm((size_t)std::max(n_maps, 0) * N);
+    for (int m = 0; m < n_maps; ++m) {
+        const float* r = maps + (size_t)m * N;
+        const double lo = *std::min_element(r, r + N), hi = *std::max_element(r, r + N);
+        for (int n = 0; n < N; ++n) norm[(size_t)m * N + n] = ((double)r[n] - lo) / (hi - lo + 0.005);
+    }
+    std::vector<double> v(N), colour((size_t)N * 3);
+    for (int f = 0; f < n_frames; ++f) {
+        const int64_t F = frame0 + f, prev = F / frames_per_map - map0, cur = prev + 1;
+        if (prev < 0 || cur >= n_maps) return fail(SAGEN_ERR_SHAPE, "sagen_overlay_blend: frame %ld needs a map that was not given", (long)F);
+        const double beta = (double)(F % frames_per_map) / (double)frames_per_map;
+        for (int n = 0; n < N; ++n) {
+            double t = (1 - beta) * norm[(size_t)prev * N + n] + beta * norm[(size_t)cur * N + n];
+            t = t * 2. - 0.7;
+            v[n] = t < 0 ? 0.0 : t;
+            const int idx = std::min((int)(v[n] * 255), 255);
+            for (int k = 0; k < 3; ++k) colour[(size_t)n * 3 + k] = lut[idx * 3 + k];
+        }
+        const std::vector<double> dir = resize_bilinear(colour, mh, mw, 3, h, w), al = resize_bilinear(v, mh, mw, 1, h, w);
+        for (size_t px = 0; px < (size_t)h * w; ++px) {
+            const double alpha = al[px] * 0.6;
+            for (int k = 0; k < 3; ++k) {
+                const size_t e = ((size_t)f * h * w + px) * 3 + k;
+                out[e] = (uint8_t)(int)(alpha * (dir[px * 3 + k] * 255) + (1 - alpha) * (double)frames[e]);
+            }
+        }
+    }
+    return SAGEN_OK;
+}
+
 // emd/dir, emd/dir2 (distance.py:100-143): the solver core of the device kernel (csrc/emd_core.h) run by one host "lane"
 int sagen_eval_emd(const float* p, const float* q, int n_maps, int nodes, const double* cost, double* emd, uint32_t* not_converged, void*) {
     if (!p || !q || !cost || !emd || !not_converged) return fail(SAGEN_ERR_NULL, "sagen_eval_emd: null argument");

@@ -104,8 +104,9 @@ class ClipArrays(object):
     preprocessed (x/255-0.5, myutils.py:88-89; flow de-quantised, feeder.py:147-161)."""
 
     def __init__(self, audio, video=None, flow=None, audio_rate=48000, video_rate=10, chunks_t=None, duration=0.1,
-                 context=1.0, start_time=0.5, sample_duration=None):
+                 context=1.0, start_time=0.5, sample_duration=None, frames=None):
         self.audio, self.video, self.flow = audio, video, flow
+        self.frames = frames        # the decoded uint8 frames [n_frames, H, W, 3] (W2XYZ.deploy_and_overlay paints on these), or None
         self.audio_rate, self.video_rate, self.context = audio_rate, video_rate, context
         self.audio_size = int(duration * audio_rate) + int(context * audio_rate) - 1
         if chunks_t is None:   # audio_pow.lst times (scraping/preprocess.py:146-153), one 1-s wav chunk per second
@@ -120,7 +121,7 @@ class ClipArrays(object):
 
     def windowed(self, start_time, sample_duration):
         return ClipArrays(self.audio, self.video, self.flow, self.audio_rate, self.video_rate, None, 0.1, self.context,
-                          start_time, sample_duration)
+                          start_time, sample_duration, self.frames)
 
     def get(self):
         self.head += 1
@@ -204,17 +205,50 @@ class W2XYZ(object):
         renderer.reset()
         return self._deploy(input_folder, deploy_start, deploy_duration, prefetch, renderer)
 
-    def _deploy(self, input_folder, deploy_start, deploy_duration, prefetch, renderer):
+    def deploy_and_overlay(self, input_folder, deploy_start=0., deploy_duration=10., overlay=None, renderer=None, prefetch=True):
+        """deploy() plus the picture the reference's --save_video --overlay_map path ends in (myutils.py:246-279): every forward
+        call's W,Y,Z,X rows and the frames of its windows go through overlay.process (overlay.Overlay) on the device, before the
+        copy to the host.  Frame F of the overlay is the frame the feeder selects for output window F (frame_index(t_F,
+        video_rate), one per 0.1 s window), read as decoded from <input_folder>/video - also for a model that has no video
+        encoder - or from ClipArrays.frames.  Returns (ambi [N, 4] - the bits deploy() returns -, frames [5 (n_maps - 1), H, W, 3]
+        uint8) and, with a renderer, its rendering as a third item."""
+        if overlay is None or overlay.channels != 4:
+            raise ValueError('deploy_and_overlay needs an overlay.Overlay over 4 channels (W,Y,Z,X)')
+        if renderer is not None and renderer.channels != 4:
+            raise ValueError('deploy_and_overlay: the render.Renderer must take 4 channels (W,Y,Z,X)')
+        if self.duration * self.params.video_rate != 1:
+            raise ValueError('deploy_and_overlay needs one frame per output window (duration %g s x video_rate %g != 1)'
+                             % (self.duration, self.params.video_rate))
+        overlay.reset()
+        if renderer is not None:
+            renderer.reset()
+        ambi, rendered, painted = self._deploy(input_folder, deploy_start, deploy_duration, prefetch, renderer, overlay)
+        return (ambi, painted) if renderer is None else (ambi, painted, rendered)
+
+    def _overlay_frames(self, source, reader):
+        """frame(t) -> the decoded uint8 frame of window time t, for deploy_and_overlay."""
+        rate = self.params.video_rate
+        if isinstance(source, ClipArrays):
+            if source.frames is None:
+                raise ValueError('deploy_and_overlay: the ClipArrays holds no decoded frames (frames=...)')
+            return lambda t: np.asarray(source.frames[frame_index(t, rate)])
+        from .feeder import JpgFrames
+        jpgs = JpgFrames(os.path.join(source, 'video'), rate)
+        return lambda t: jpgs.frame(frame_index(t, rate))
+
+    def _deploy(self, input_folder, deploy_start, deploy_duration, prefetch, renderer, overlay=None):
         import torch
         from . import ops
         from .feeder import BatchPrefetcher, frames_to_float
         p, m = self.params, self.model
         reader = self._reader(input_folder, deploy_start, deploy_duration)
         if not reader.chunks_t:
-            return np.zeros((0, 4), np.float32), np.zeros((0, renderer.outputs if renderer else 0), np.float32)
+            empty = np.zeros((0, 4), np.float32), np.zeros((0, renderer.outputs if renderer else 0), np.float32)
+            return empty if overlay is None else empty + (np.zeros((0, 0, 0, 3), np.uint8),)
         dt = reader.chunks_t[0] - deploy_start                           # deploy.py:106-107
         reader.chunks_t = [t - dt for t in reader.chunks_t]
         use_v, use_f = VIDEO in p.encoders, FLOW in p.encoders
+        frame_of = self._overlay_frames(input_folder, reader) if overlay is not None else None
 
         def batches():                                                   # deploy.py:112-139
             while True:
@@ -223,6 +257,8 @@ class W2XYZ(object):
                     chunk = reader.get()
                     if chunk is None:
                         break
+                    if frame_of is not None:
+                        chunk['frame'] = frame_of(reader.chunks_t[reader.head])
                     batch.append(chunk)
                 if not batch:
                     return
@@ -231,6 +267,8 @@ class W2XYZ(object):
                 audio = np.zeros((self.batch_size, self.audio_size, 1), np.float32)   # zero rows = deploy.py:125-127
                 audio[:n] = np.stack([b['ambix'] for b in batch], 0)[:, :, :1]
                 out['audio'] = audio
+                if frame_of is not None:
+                    out['frames'] = np.stack([b['frame'] for b in batch], 0)
                 for key, on in (('video', use_v), ('flow', use_f)):
                     if on:
                         clip = np.stack([b[key] for b in batch], 0)
@@ -243,7 +281,7 @@ class W2XYZ(object):
                 yield out
 
         src = BatchPrefetcher(batches(), depth=2 * max(1, self.groups), pin=True) if prefetch else batches()
-        outs, rendered = [], []
+        outs, rendered, painted = [], [], []
         G = max(1, int(self.groups))
         mg = self._grouped_model(G) if G > 1 else None
 
@@ -257,6 +295,10 @@ class W2XYZ(object):
             if renderer is not None:    # one call for everything this forward produced, in stream order, only the valid windows of a partial batch
                 valid = rows[0] if len(rows) == 1 else (wyzx.reshape(-1, 4) if all(b['n'] == self.batch_size for b in bs) else torch.cat(rows, 0))
                 rendered.append(renderer.process(valid).cpu().numpy())
+            if overlay is not None:     # the same rows, and the frames of exactly these windows
+                valid = rows[0] if len(rows) == 1 else torch.cat(rows, 0)
+                frames = torch.cat([torch.as_tensor(b['frames']) for b in bs], 0).to(m.device, non_blocking=True)
+                painted.append(overlay.process(valid, frames).cpu().numpy())
             for r in rows:
                 outs.append(r.cpu().numpy())
 
@@ -275,7 +317,11 @@ class W2XYZ(object):
             run(m, [b])
         for q in pending:
             run(m, [q])
-        return np.concatenate(outs, 0), (np.concatenate(rendered, 0) if renderer is not None else None)
+        result = np.concatenate(outs, 0), (np.concatenate(rendered, 0) if renderer is not None else None)
+        if overlay is None:
+            return result
+        painted = [f for f in painted if f.shape[0]]
+        return result + (np.concatenate(painted, 0) if painted else np.zeros((0, 0, 0, 3), np.uint8),)
 
     def _grouped_model(self, G):
         """A second facade over the SAME device variables whose native contexts carry G batches per call (SptAudioGen(groups=G))."""
@@ -305,11 +351,17 @@ def parse_arguments(argv=None):
     from .render import add_render_arguments
     add_render_arguments(parser)
     parser.add_argument('--render_fn', default=None, help='Output wav of --render.')
+    parser.add_argument('--overlay_dir', default=None, metavar='DIR',
+                        help='paint the sound-direction heat map over the frames of <input_folder>/video and write them here as %%06d.png (overlay.py)')
+    parser.add_argument('--save_maps', default=None, metavar='FILE.npz', help='with --overlay_dir: also write the raw power maps')
+    parser.add_argument('--overwrite', action='store_true', help='replace frames already in --overlay_dir')
     args = parser.parse_args(argv)
     if args.deploy_duration <= 0:
         args.deploy_duration = None
     if (args.render is None) != (args.render_fn is None):
         parser.error('--render and --render_fn come together')
+    if args.save_maps and not args.overlay_dir:
+        parser.error('--save_maps needs --overlay_dir')
     return args
 
 
@@ -323,11 +375,20 @@ def main(argv=None):
     require_first_order(params.ambi_order, 'deploy')
     render.check_render_arguments(args, 4, 'deploy')
     rendering = render.rendering_from_arguments(args, 4, params.audio_rate, 'deploy') if args.render else None   # host only (HRIR files, refusals)
+    if args.overlay_dir:
+        from . import overlay
+        overlay.prepare_output_dir(args.overlay_dir, args.overwrite, 'deploy')
     torch.cuda.set_device(args.gpu)
     renderer = render.Renderer(*rendering) if rendering else None
     model = W2XYZ(args.model_dir)
     model.groups = max(1, args.groups)
-    if renderer is None:
+    painted = None
+    if args.overlay_dir:
+        ov = overlay.Overlay(4, audio_rate=params.audio_rate, video_rate=params.video_rate)
+        res = model.deploy_and_overlay(args.input_folder, args.deploy_start, args.deploy_duration, ov, renderer)
+        ambi_pred, painted = res[0], res[1]
+        rendered = res[2] if renderer is not None else None
+    elif renderer is None:
         ambi_pred = model.deploy(args.input_folder, args.deploy_start, args.deploy_duration)
     else:
         ambi_pred, rendered = model.deploy_and_render(args.input_folder, args.deploy_start, args.deploy_duration, renderer)
@@ -338,6 +399,11 @@ def main(argv=None):
             rendered = render.normalize_peak(rendered, args.normalize)
         save_wav(args.render_fn, rendered, model.params.audio_rate)
         print('wrote %s: %d samples x %d channels (%s)' % (args.render_fn, rendered.shape[0], rendered.shape[1], args.render))
+    if painted is not None:
+        overlay.save_frames(args.overlay_dir, painted)
+        if args.save_maps:
+            np.savez(args.save_maps, maps=ov.maps().cpu().numpy())
+        print('wrote %d frames to %s (%d maps of %dx%d)' % (painted.shape[0], args.overlay_dir, ov.maps().shape[0], ov.map_shape[0], ov.map_shape[1]))
 
 
 if __name__ == '__main__':

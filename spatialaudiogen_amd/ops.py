@@ -159,6 +159,45 @@ def power_map_batched(ambi_wyzx, sh_matrix):
     return rms
 
 
+def power_map_windows(ambi, sh_matrix, stride, window, out=None):
+    """One RMS map per `window` samples of ambi[::stride] (SphericalAmbisonicsVisualizer over myutils.py:252's ambix[::5];
+    include/sagen.h: sagen_power_map_windows): ambi [n_rows, 4 or 9], sh [P, channels] -> [n_maps, P] with
+    n_maps = len(ambi[::stride]) // window.  out: optional [n_maps, P] tensor to write into."""
+    a, sh = _f32(ambi, 'ambi'), _f32(sh_matrix, 'sh')
+    if a.dim() != 2 or sh.dim() != 2 or sh.shape[1] != a.shape[1]:
+        raise ValueError('power_map_windows: ambi [rows, C] and sh [P, C] expected')
+    n_rows, C_, P = a.shape[0], a.shape[1], sh.shape[0]
+    n_maps = (-(-n_rows // int(stride))) // int(window)
+    l = _lib.lib()
+    rms = _out(out, (n_maps, P), a, 'out')
+    scratch = torch.empty((int(l.sagen_power_map_windows_scratch_bytes(n_maps, C_)) + 7) // 8 + 1, dtype=torch.float64, device=a.device)
+    check(l.sagen_power_map_windows(_ptr(a), n_rows, C_, int(stride), int(window), _ptr(sh), P, _ptr(rms), _ptr(scratch), scratch.numel() * 8, _stream()))
+    return rms
+
+
+def overlay_blend(maps, map0, lut, frames, frame0, frames_per_map):
+    """myutils.py:255-279 for a run of frames (include/sagen.h: sagen_overlay_blend): maps [n_maps, mh, mw] raw rms maps in image
+    orientation from absolute map index map0 on, lut [256, 3] float64, frames [n_frames, h, w, 3] uint8 from absolute frame index
+    frame0 on -> the blended uint8 frames."""
+    maps = _f32(maps, 'maps')
+    dev_ok = lambda t: isinstance(t, torch.Tensor) and t.is_cuda != _twin()
+    if not (dev_ok(lut) and lut.dtype == torch.float64 and tuple(lut.shape) == (256, 3)):
+        raise TypeError('lut must be a [256, 3] float64 tensor on the maps\' device')
+    if not (dev_ok(frames) and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3):
+        raise TypeError('frames must be a [n, h, w, 3] uint8 tensor on the maps\' device')
+    if maps.dim() != 3:
+        raise ValueError('overlay_blend: maps [n_maps, mh, mw] expected')
+    frames, lut = frames.contiguous(), lut.contiguous()
+    n_maps, mh, mw = maps.shape
+    n, h, w = frames.shape[:3]
+    l = _lib.lib()
+    out = torch.empty_like(frames)
+    scratch = torch.empty((int(l.sagen_overlay_blend_scratch_bytes(n_maps, mh, mw, n)) + 7) // 8 + 2, dtype=torch.float64, device=maps.device)
+    check(l.sagen_overlay_blend(_ptr(maps), n_maps, int(map0), mh, mw, _ptr(lut), _ptr(frames), n, int(frame0), h, w, int(frames_per_map),
+                                _ptr(out), _ptr(scratch), scratch.numel() * 8, _stream()))
+    return out
+
+
 def eval_mel_env(pred, target):
     """myutils.compute_lsd_dist / compute_envelope_dist (myutils.py:96-116) per window: pred / target [B, 4800, C] ->
     (mel_lsd [B, C], env_mse [B, C])."""
