@@ -299,7 +299,7 @@ static int launch_cfg(const IgemmDesc& d, hipStream_t s) {
     return SAGEN_OK;
 }
 
-struct TileCfg { int bm, bn, bk; const char* name; bool split = false; bool dw3 = false; bool s2 = false; bool p3 = false; bool g = false; bool h = false; };
+struct TileCfg { int bm, bn, bk; const char* name; bool split = false; bool dw3 = false; bool s2 = false; bool p3 = false; bool g = false; bool h = false; bool s2d = false; };
 static const TileCfg kTiles[TILE_AUTO] = {
     {128, 128, 16, "igemm_kernel<128,128,64,64,3,16>"}, {128, 64, 16, "igemm_kernel<128,64,64,32,3,16>"},
     {256, 64, 16, "igemm_kernel<256,64,64,64,3,16>"},   {64, 64, 16, "igemm_kernel<64,64,32,32,3,16>"},
@@ -342,6 +342,8 @@ static const TileCfg kTiles[TILE_AUTO] = {
     {256, 64, 16, "conv3hr_kernel<256,64,64,64,1>", true, true, false, true, false, true}, {128, 64, 16, "conv3hr_kernel<128,64,64,32,1>", true, true, false, true, false, true},
     {64, 64, 32, "conv3hr_kernel<64,64,32,32,2>", true, true, false, true, false, true},
     {128, 128, 16, "conv3hr_kernel<128,128,64,64,1>", true, true, false, true, false, true},
+    {128, 128, 16, "conv3h_kernel<128,128,64,64,1,2,true>", true, false, false, true, false, true, true}, {128, 64, 16, "conv3h_kernel<128,64,64,32,1,3,true>", true, false, false, true, false, true, true},
+    {256, 64, 16, "conv3h_kernel<256,64,64,64,1,3,true>", true, false, false, true, false, true, true},
 };
 // igemm3s2_kernel: the 7x(7->8)x4 stride-2 stem over a pre-padded dense image
 static bool s2_ok(const IgemmDesc& d) {
@@ -359,8 +361,9 @@ static bool dw3_ok(const IgemmDesc& d) {
 bool igemm_tile_split(IgemmTile t) { return t >= 0 && t < TILE_AUTO && kTiles[t].split; }
 bool igemm_tile_p3(IgemmTile t) { return t >= 0 && t < TILE_AUTO && kTiles[t].p3; }
 // conv3h_kernel tiles can split K by the filter row (dh-split, split-K = 3 exactly); the three-deep-ring variant cannot
+bool igemm_tile_s2d(IgemmTile t) { return t >= 0 && t < TILE_AUTO && kTiles[t].s2d; }
 bool igemm_tile_dh_split(IgemmTile t) {
-    return t >= 0 && t < TILE_AUTO && kTiles[t].p3 && kTiles[t].h && !kTiles[t].g && t != TILE_P3HR_256x64 && t != TILE_P3HR_128x64 && t != TILE_P3HR_64x64_C2 && t != TILE_P3HR_128x128;
+    return t >= 0 && t < TILE_AUTO && kTiles[t].p3 && kTiles[t].h && !kTiles[t].g && !kTiles[t].s2d && t != TILE_P3HR_256x64 && t != TILE_P3HR_128x64 && t != TILE_P3HR_64x64_C2 && t != TILE_P3HR_128x128;
 }
 bool igemm_p3_eligible(const IgemmDesc& d) { return dw3_ok(d) && d.w_split && d.dsh * d.dsw == 1 && d.Cin <= MAX_BN_C; }
 static int tile_bm(IgemmTile t) { return (t >= 0 && t < TILE_AUTO) ? kTiles[t].bm : 0; }
@@ -397,6 +400,7 @@ bool igemm_tile_ok(const IgemmDesc& d, IgemmTile t) {
             return false;
     }
     if (kTiles[t].dw3 && !dw3_ok(d)) return false;
+    if (kTiles[t].s2d) return d.splitk == 1 && d.mm_out == nullptr && conv3s_ok(d);           // (the training step and the other plane formats never provide the operand)
     if (kTiles[t].p3 && (d.xp3 == nullptr || (d.splitk != 1 && !(d.splitk == 3 && igemm_tile_dh_split(t))))) return false;
     if (kTiles[t].p3 && (kTiles[t].h ? (d.xp3_fmt != 1 || d.wh2 == nullptr) : d.xp3_fmt != 0)) return false;   // the planes' format decides the family
     if (!kTiles[t].p3 && d.xp3 != nullptr && d.x == nullptr) return false;      // only the planes were provided
@@ -411,6 +415,7 @@ IgemmTile igemm_pick_tile(const IgemmDesc& d) {
     static const char* force = getenv("SAGEN_FORCE_TILE");               // tuning knob: IgemmTile index
     if (force && d.M > 128 && d.N >= 64 && igemm_tile_ok(d, (IgemmTile)atoi(force))) return (IgemmTile)atoi(force);
     static const bool fp32_only = getenv("SAGEN_FP32_ONLY") != nullptr;
+    if (d.xp3 == nullptr && d.x == nullptr && conv3s_ok(d)) return TILE_P3S_128x128;         // only the space-to-depth planes were provided
     if (d.mm_out != nullptr) return (d.xp3 != nullptr && d.xp3_fmt == 1 && d.wh2 != nullptr && conv3g_ok(d)) ? TILE_P3GH_MM_64x128_K2 : TILE_B3_64x128;
     auto blocks = [&](IgemmTile t) { return (long)cdiv(d.M, tile_bm(t)) * cdiv(d.N, tile_bn(t)) * d.splitk; };
     const long want = 2 * 256;                 // >= 2 workgroups per CU
@@ -463,7 +468,7 @@ int igemm_grid_m(const IgemmDesc& d, IgemmTile tile) {
 
 int igemm_launch(const IgemmDesc& d_in, IgemmTile tile, hipStream_t s) {
     IgemmDesc d = d_in;
-    if ((!d.x && !d.xp3) || !d.w || (!d.y && !d.splitk_ws)) return fail(SAGEN_ERR_NULL, "igemm: null operand");
+    if ((!d.x && !d.xp3 && !d.xs2d) || !d.w || (!d.y && !d.splitk_ws)) return fail(SAGEN_ERR_NULL, "igemm: null operand");
     if (d.M <= 0 || d.N <= 0 || d.K <= 0) return fail(SAGEN_ERR_SHAPE, "igemm: empty problem M=%d N=%d K=%d", d.M, d.N, d.K);
     if (d.Kpad % 16 || d.Kpad < d.K) return fail(SAGEN_ERR_SHAPE, "igemm: Kpad=%d must be a multiple of 16 >= K=%d", d.Kpad, d.K);
     if (d.K % 4 || d.Cin % 4) return fail(SAGEN_ERR_UNSUPPORTED, "igemm: Cin=%d / K=%d must be multiples of 4", d.Cin, d.K);
@@ -500,6 +505,7 @@ int igemm_launch(const IgemmDesc& d_in, IgemmTile tile, hipStream_t s) {
     // wave-uniform tap per K tile: every K tile lies inside one tap (and there is no ragged K tail)
     d.uniform_taps = uniform_taps_for(d, kTiles[tile].bk) ? 1 : 0;
     if (d.ntaps > MAX_TAPS) return fail(SAGEN_ERR_UNSUPPORTED, "igemm: %d taps (max %d)", d.ntaps, MAX_TAPS);
+    if (kTiles[tile].s2d) return conv3s_dispatch(d, tile, s);
     if (kTiles[tile].g) return conv3g_dispatch(d, tile, s);
     if (kTiles[tile].h) return conv3h_dispatch(d, tile, s);
     if (kTiles[tile].p3) return conv3p_dispatch(d, tile, s);

@@ -78,6 +78,12 @@ struct IgemmDesc {
     int p3_np = 0;
     int xp3_fmt = 0;                  // 0: three bf16 planes (96 B per pixel and chunk); 1: two fp16 planes of v * 2^ka (64 B; conv3h.hip)
     int xp3_row0 = 0, xp3_rows = 0;   // conv3g_kernel: the planes hold image rows [xp3_row0, xp3_row0 + xp3_rows) only (xp3_rows = 0: all Hin rows)
+    // the space-to-depth conv3h_kernel (conv3s.hip): the same fp16x2 planes in space-to-depth form for a 3x3 stride-2 SAME conv over even Hin x Win - four
+    // phase images (h & 1, w & 1), image 2 (h & 1) + (w & 1) an ordinary plane tensor [Cin/16][xs2d_np][2][16] over the OUTPUT grid,
+    // xs2d_np = B*Hg*(Wg+1), back to back (p3.hip: p3_pack_launch with s2d = 1)
+    const void* xs2d = nullptr;
+    unsigned xs2d_bytes = 0;
+    int xs2d_np = 0;
     const void* wh2 = nullptr;        // conv3h_kernel: the filter as two fp16 planes of w * 2^kw, [Kpad/16][2][N][16]
     unsigned wh2_bytes = 0;
     const float* h2_a_inv = nullptr;  // device scalars 2^-ka (written by the plane producer) and 2^-kw (written by the filter pack)
@@ -105,7 +111,7 @@ __device__ __forceinline__ void igemm_relocate(IgemmDesc& d, int g) {
     d.bn_in.acc = grp_ptr(d.bn_in.acc, gi, g);
     d.stats = grp_ptr(d.stats, gi, g); d.amax_out = grp_ptr(d.amax_out, gi, g);
     d.splitk_ws = grp_ptr(d.splitk_ws, gi, g); d.sk_ticket = grp_ptr(d.sk_ticket, gi, g);
-    d.xp3 = grp_ptr(d.xp3, gi, g);
+    d.xp3 = grp_ptr(d.xp3, gi, g); d.xs2d = grp_ptr(d.xs2d, gi, g);
     d.h2_a_inv = grp_ptr(d.h2_a_inv, gi, g); d.h2_w_inv = grp_ptr(d.h2_w_inv, gi, g);
     d.mm_coeffs = grp_ptr(d.mm_coeffs, gi, g); d.mm_out = grp_ptr(d.mm_out, gi, g);
 }
@@ -148,6 +154,8 @@ enum IgemmTile {
     // conv3hr_kernel: conv3h_kernel with a three-deep ring of activation images beside the two filter stages (conv3h.hip)
     TILE_P3HR_256x64, TILE_P3HR_128x64, TILE_P3HR_64x64_C2,
     TILE_P3HR_128x128,         // (round 6: the 128x128 tile with the three-deep activation ring - 72 KB of LDS, two workgroups per CU)
+    // the space-to-depth conv3h_kernel: the 3x3 stride-2 SAME conv over space-to-depth fp16x2 planes (IgemmDesc::xs2d), conv3h_kernel's K loop; R = three-deep activation ring
+    TILE_P3S_128x128, TILE_P3SR_128x64, TILE_P3SR_256x64,
     TILE_AUTO
 };
 
@@ -165,6 +173,8 @@ int igemm3s2_dispatch(const IgemmDesc& d, IgemmTile tile, hipStream_t s); // (ig
 int conv3p_dispatch(const IgemmDesc& d, IgemmTile tile, hipStream_t s);   // (conv3p.hip)
 int conv3g_dispatch(const IgemmDesc& d, IgemmTile tile, hipStream_t s);   // (conv3g.hip)
 int conv3h_dispatch(const IgemmDesc& d, IgemmTile tile, hipStream_t s);   // (conv3h.hip)
+int conv3s_dispatch(const IgemmDesc& d, IgemmTile tile, hipStream_t s);   // (conv3s.hip)
+bool conv3s_ok(const IgemmDesc& d);                   // 3x3 stride-2 SAME conv over even sizes with its space-to-depth planes present
 int h2_filter_pack_launch(const float* wp, int N, int Kpad, void* w2, unsigned* scratch, float* w_inv, hipStream_t s);
 struct H2Job {                       // one layer of the batched fp16x2 filter pack (1024 elements per block)
     const float* wp = nullptr;       // fp32 packed filter [N][Kpad]
@@ -179,6 +189,7 @@ constexpr int SK_TICKETS = 8192;                      // tiles an in-launch spli
 inline bool igemm_tile_fused_splitk(IgemmTile) { return true; }     // every kernel that writes split-K partials does it through igemm_epilogue
 bool igemm_tile_p3(IgemmTile t);                      // conv3p_kernel tile (pre-split activation planes, no split-K)?
 bool igemm_tile_grouped(IgemmTile t);                 // does the tile's kernel support the grouped launch (common.h: GroupInfo)?
+bool igemm_tile_s2d(IgemmTile t);                     // the space-to-depth conv3h_kernel tile (contracts IgemmDesc::xs2d)?
 bool igemm_tile_dh_split(IgemmTile t);                // ... except conv3h_kernel's dh-split: split-K = 3 exactly, one filter row per workgroup
 bool igemm_p3_eligible(const IgemmDesc& d);           // dense 3x3 stride-1 SAME conv that conv3p_kernel can run (given planes)
 bool igemm_tile_ok(const IgemmDesc& d, IgemmTile t);   // can this instantiation run the problem?              // instantiation name as rocprofv3 prints it
@@ -310,8 +321,10 @@ struct P3hScale {
     const float* res_a_inv = nullptr;
 };
 int p3_pack_launch(const float* x, const float* scale, const float* shift, const BnRef& bn, const float* residual, int relu,
-                   float* y, void* p3, int B, int H, int W, int C, hipStream_t s, int fmt = 0, const P3hScale* h2 = nullptr);
+                   float* y, void* p3, int B, int H, int W, int C, hipStream_t s, int fmt = 0, const P3hScale* h2 = nullptr,
+                   int s2d = 0);        // s2d (fmt 1, H and W even, not in place): the planes in space-to-depth form (conv3s.hip)
 size_t p3h_bytes(int B, int H, int W, int C);
+size_t p3s_bytes(int B, int H, int W, int C);          // ... in space-to-depth form
 // rows [row0, row0 + R) of every image of an fp32 NHWC tensor (pixel stride ldx, row stride x_rstride, image stride x_bstride, all in
 // floats) -> fp16x2 planes [C/16][B*R*(W+1)][2][16] of v * 2^ka with ka from the EXACT maximum the producers' epilogues published
 // (IgemmDesc::amax_out: H2_AMAX_SLOTS words each; amax1 nullable): nothing can saturate.  2^-ka -> a_inv[0].

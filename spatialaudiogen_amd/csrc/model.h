@@ -141,6 +141,7 @@ struct sagen_ctx {
     bool train_rawpool = true;             // the training forward's stem writes the raw output AND its pooled extremum (SAGEN_TRAIN_NO_RAWPOOL=1: a pool pass of its own)
     bool train_bands = true;               // the training step's decoder on the live rows only, forward and backward (SAGEN_TRAIN_NO_BANDS=1: full tensors)
     int dec_lo[7] = {0, 0, 0, 0, 0, 0, 0}, dec_hi[7] = {0, 0, 0, 0, 0, 0, 0};      // rows of cat_l the last forward's decoder read (the backward of the same step follows them)
+    bool use_s2d = true;                   // lean trunk: a stage's last merge writes its planes in space-to-depth form where the plan runs the next stage's stride-2 conv_1 on the space-to-depth conv3h_kernel (conv3s.hip); SAGEN_NO_S2D=1 / sagen_set_option("plane_s2d", 0): the gathered kernel everywhere
     bool no_scatter = false, no_d1_planes = false, no_lean_trunk = false;      // SAGEN_NO_DECONV_SCATTER / SAGEN_NO_DECONV1_PLANES / SAGEN_NO_LEAN_TRUNK, read when the context is created
     int dec_planes_min_batch = 16;         // the scatter-form decoder contracts fp16x2 planes from this batch size on (sagen_set_option("decoder_planes", 1 / 0): always / never)
     bool use_fcm = false;                  // inference: the skinny FC layers (bottleneck / localisation / fc-feats) run fcm_kernel (fcm.hip) chained through partials; SAGEN_NO_FCM=1: the round-4 contraction + reducer launches
@@ -620,22 +621,27 @@ struct Fwd {
     // batch-norm + ReLU applied to the input on the fly
     void conv_bn(const float* x, int Hin, int Win, int Cin, const std::string& name, int k, int stride, int Cout,
                  const BnRef& bn_in, float* y, int& Hout, int& Wout, int bn_index, const std::string& plan_key = "",
-                 const void* planes = nullptr, const float* planes_a_inv = nullptr) {
+                 const void* planes = nullptr, const float* planes_a_inv = nullptr, const void* s2d_planes = nullptr) {
         if (rc) return;
         IgemmDesc d = conv_desc(x, Hin, Win, Cin, Cin, c->p("pk:" + name + "/weights"), k, k, stride, stride, true, Cout, y,
                                 Cout, Hout, Wout);
-        if (planes) {                       // the input as pre-split planes (p3.hip); x may be null then
+        if (planes || s2d_planes) {         // the input as pre-split planes (p3.hip); x may be null then
             d.xp3 = planes;
-            d.p3_np = c->B * Hin * (Win + 1);
+            d.p3_np = planes ? c->B * Hin * (Win + 1) : 0;
             auto hs = c->h2_slot.find(name);
             if (h2() && (stride == 1 || c->use_p3g) && k == 3 && hs != c->h2_slot.end()) {       // two fp16 planes + the layer's fp16 filter planes
                 d.xp3_fmt = 1;
                 d.xp3_cstride = (unsigned)((size_t)d.p3_np * 64);
-                d.xp3_bytes = (unsigned)p3h_bytes(c->B, Hin, Win, Cin);
+                d.xp3_bytes = planes ? (unsigned)p3h_bytes(c->B, Hin, Win, Cin) : 0u;
                 d.wh2 = c->p("pkh:" + name + "/weights");
                 d.wh2_bytes = (unsigned)((size_t)d.N * d.Kpad * 4);
                 d.h2_a_inv = planes_a_inv ? planes_a_inv : h2_a_inv();
                 d.h2_w_inv = c->p("h2s") + hs->second;
+                if (s2d_planes) {           // ... in space-to-depth form (conv3s.hip): beside the row-padded planes while tuning, alone otherwise
+                    d.xs2d = s2d_planes;
+                    d.xs2d_np = c->B * (Hin / 2) * (Win / 2 + 1);
+                    d.xs2d_bytes = (unsigned)p3s_bytes(c->B, Hin, Win, Cin);
+                }
             } else {
                 d.xp3_cstride = (unsigned)((size_t)d.p3_np * 96);
                 d.xp3_bytes = (unsigned)p3_bytes(c->B, Hin, Win, Cin);
@@ -748,6 +754,9 @@ struct Fwd {
         const int couts[4] = {64, 128, 256, 512};
         bool x_in_planes = pool_planes;        // the pooled tensor exists as planes (p3_pack after the fused uint8 stem, p3_maxpool otherwise)
         int xb_par = 0;                                                 // which h2_xbound slot holds the current block input's bound
+        // the block input ALSO (tuning) or ONLY lies in "p3b" in space-to-depth form: the last merge of a stage wrote it for the stride-2
+        // conv_1 (the space-to-depth conv3h_kernel) and the 1x1/2 shortcut - a dense 1x1 over phase image (0, 0) - of the next stage's first block
+        bool x_in_s2d = false, x_in_rows = true;
         bool x_fp32_valid = !lean;                                      // false: the previous pass wrote the block input as planes only (lean trunk: already the pool)
         for (int st = 0; st < 4; ++st) {
             const int cout = couts[st];
@@ -766,8 +775,30 @@ struct Fwd {
                 const float* const x_ai = lean ? h2_a_inv_x(xb_par) : nullptr;                        // (null: the trunk's one slot)
                 // the block input as planes: written by the previous block's merge (x_in_planes) - stride-1 conv_1 (conv3p_kernel) and,
                 // since round 4, the stride-2 conv_1 + 1x1 shortcut of a stage's first block (conv3g_kernel: gathered operand tiles)
-                const void* in_planes = (p3_here && x_in_planes) ? xplanes : nullptr;
-                if (first) {   // 1x1/2 projection, no bias, no BN (resnet.py:211-212)
+                const void* in_planes = (p3_here && x_in_planes && x_in_rows) ? xplanes : nullptr;
+                const void* const in_s2d = (first && p3_here && x_in_planes && x_in_s2d) ? (void*)c->p("p3b" + sfx) : nullptr;
+                // the projection over space-to-depth planes: phase image (0, 0) IS the tensor it reads - a dense 1x1 over [B, H/2, W/2] planes
+                // (full lines, a quarter of the bytes) on the same conv3g_kernel, planned under its own key
+                auto shortcut_s2d = [&] {
+                    IgemmDesc d = conv_desc(nullptr, H / 2, W / 2, cin, cin, c->p("pk:" + pfx + "/shortcut/weights"), 1, 1, 1, 1, true,
+                                            cout, c->p("rsc" + sfx), cout, Ho, Wo);
+                    d.xp3 = in_s2d;
+                    d.p3_np = B * (H / 2) * (W / 2 + 1);
+                    d.xp3_fmt = 1;
+                    d.xp3_cstride = (unsigned)((size_t)d.p3_np * 64);
+                    d.xp3_bytes = (unsigned)p3h_bytes(B, H / 2, W / 2, cin);
+                    d.wh2 = c->p("pkh:" + pfx + "/shortcut/weights");
+                    d.wh2_bytes = (unsigned)((size_t)d.N * d.Kpad * 4);
+                    d.h2_a_inv = x_ai;
+                    d.h2_w_inv = c->p("h2s") + c->h2_slot.at(pfx + "/shortcut");
+                    d.stats = bn_acc(20 + st);
+                    layer = pfx + "/shortcut#s2d";
+                    gemm(d, 1, false);
+                };
+                if (first && in_s2d && !in_planes) {
+                    shortcut_s2d();
+                    shortcut = c->p("rsc" + sfx);
+                } else if (first) {   // 1x1/2 projection, no bias, no BN (resnet.py:211-212)
                     IgemmDesc d = conv_desc(xin, H, W, cin, cin, c->p("pk:" + pfx + "/shortcut/weights"), 1, 1, 2, 2, true,
                                             cout, c->p("rsc" + sfx), cout, Ho, Wo);
                     if (!x_fp32_valid) d.x = nullptr;                   // the merge wrote this block input as planes only
@@ -791,9 +822,13 @@ struct Fwd {
                     if (h2() && p3_here) d.stats = bn_acc(20 + st);      // (sum, sumsq) of the projection: the residual's magnitude for the merge's fp16 scale
                     layer = pfx + "/shortcut";
                     gemm(d, 1, false);
+                    if (in_s2d && !rc) {    // tuning: both layouts are there - plan the dense form too (it leaves the same sums and statistics)
+                        if (memset_groups(d.stats, (size_t)2 * d.N * sizeof(double)) != hipSuccess) rc = fail(SAGEN_ERR_HIP, "autotune: memset failed");
+                        shortcut_s2d();
+                    }
                     shortcut = c->p("rsc" + sfx);
                 }
-                conv_bn(x_fp32_valid ? xin : nullptr, H, W, cin, pfx + "/conv_1", 3, stride, cout, BnRef(), c->p("ry1" + sfx), Ho, Wo, li, "", in_planes, x_ai);
+                conv_bn(x_fp32_valid ? xin : nullptr, H, W, cin, pfx + "/conv_1", 3, stride, cout, BnRef(), c->p("ry1" + sfx), Ho, Wo, li, "", in_planes, x_ai, in_s2d);
                 const BnRef bn1 = bn_ref(li, pfx + "/conv_1", (long)B * Ho * Wo);
                 ++li;
                 int H2, W2;
@@ -824,7 +859,23 @@ struct Fwd {
                         if (res_planes) { hs2.res_planes = xplanes; hs2.res_a_inv = h2_a_inv_x(xb_par); }
                     }
                     xb_par ^= 1;
-                    timed("p3_pack_kernel", 0.0, [&] { return p3_pack_launch(c->p("ry2" + sfx), nullptr, nullptr, bn2, res_planes ? nullptr : shortcut, 1, y_fp32 ? xout : nullptr, next_p3 ? xplanes : nullptr, B, Ho, Wo, cout, s, p3_fmt(), &hs2); });
+                    // the layout follows the plan entry of the next stage's conv_1: a the space-to-depth conv3h_kernel tile wants the space-to-depth form (in
+                    // "p3b", free between this conv_2 and the next block's bn1-relu: the merge cannot overwrite the block input it reads its
+                    // residual from), anything else today's row-padded planes; while tuning both are written - the space-to-depth form first,
+                    // from the intact residual planes - so that the candidates of both families are timed on real operands
+                    bool s2d_out = false, rows_out = true;
+                    const std::string next_c1 = scope + "/conv" + std::to_string(st + 3) + "_1/conv_1";
+                    if (lean && to_next_stage && c->use_s2d && !(Ho & 1) && !(Wo & 1) && c->h2_slot.count(next_c1) != 0 &&
+                        c->h2_slot.count(scope + "/conv" + std::to_string(st + 3) + "_1/shortcut") != 0) {
+                        auto it = c->plan.find(next_c1);
+                        s2d_out = c->tuning || (it != c->plan.end() && igemm_tile_s2d((IgemmTile)it->second.tile));
+                        rows_out = c->tuning || !s2d_out;
+                    }
+                    if (s2d_out)
+                        timed("p3_pack_kernel", 0.0, [&] { return p3_pack_launch(c->p("ry2" + sfx), nullptr, nullptr, bn2, res_planes ? nullptr : shortcut, 1, nullptr, c->p("p3b" + sfx), B, Ho, Wo, cout, s, p3_fmt(), &hs2, 1); });
+                    if (rows_out)
+                        timed("p3_pack_kernel", 0.0, [&] { return p3_pack_launch(c->p("ry2" + sfx), nullptr, nullptr, bn2, res_planes ? nullptr : shortcut, 1, y_fp32 ? xout : nullptr, next_p3 ? xplanes : nullptr, B, Ho, Wo, cout, s, p3_fmt(), &hs2); });
+                    x_in_s2d = s2d_out; x_in_rows = rows_out;
                     x_in_planes = next_p3;
                     x_fp32_valid = y_fp32;
                     ++li;

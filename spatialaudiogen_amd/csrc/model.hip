@@ -61,6 +61,7 @@ int sagen_create_impl(sagen_ctx** out, const sagen_config* cfg, int groups) {
     c->train_rawpool = getenv("SAGEN_TRAIN_NO_RAWPOOL") == nullptr;
     c->no_d1_planes = getenv("SAGEN_NO_DECONV1_PLANES") != nullptr;
     c->no_lean_trunk = getenv("SAGEN_NO_LEAN_TRUNK") != nullptr;
+    c->use_s2d = getenv("SAGEN_NO_S2D") == nullptr;
     if (getenv("SAGEN_NO_DECODER_PLANES") != nullptr) c->dec_planes_min_batch = 1 << 30;
     // with two fp16 planes a plane pass writes 4 bytes per element - what the fp32 pass it replaces writes - so the planes pay from
     // stage 2 on (measured, same box: 2 034 against 1 943 ambisonic-s/s); with three bf16 planes (6 bytes) only from stage 3
@@ -254,7 +255,9 @@ int sagen_create_impl(sagen_ctx** out, const sagen_config* cfg, int groups) {
         const size_t stage = (size_t)B * 56 * 112 * 64;
         for (const char* nm : {"rx0", "rx1", "ry1", "ry2", "rsc", "ry1n"}) c->alloc(nm + x, stage);
         c->alloc("p3" + x, (p3_bytes(B, 56, 112, 64) + 3) / 4 + 64);   // bf16 planes of the current 3x3 conv input (largest: stage 2)
-        c->alloc("p3b" + x, (p3h_bytes(B, 56, 112, 64) + 3) / 4 + 64); // lean trunk (model.h: resnet): the conv_2 input planes, "p3" then holds block inputs / outputs
+        // lean trunk (model.h: resnet): the conv_2 input planes, "p3" then holds block inputs / outputs; between a stage's last conv_2 and the next
+        // stage's bn1-relu it holds that block output in space-to-depth form (conv3s.hip: 0.9 % larger)
+        c->alloc("p3b" + x, (std::max(p3h_bytes(B, 56, 112, 64), p3s_bytes(B, 56, 112, 64)) + 3) / 4 + 64);
         c->alloc("bnacc" + x, (size_t)24 * 2 * 512 * 2);   // fp64 (sum, sumsq) accumulators per BN layer
         c->alloc("fcred" + x, (size_t)B * 98 * 128);
         // trunk output (block conv5_2) for parity tests: the ping-pong lands in rx0 after the 8 blocks
@@ -950,6 +953,7 @@ int sagen_set_option_impl(sagen_ctx* c, const char* name, int value) {
     if (n == "planes_from_stage") { if (value < 2 || value > 6) return fail(SAGEN_ERR_SHAPE, "planes_from_stage in 2..6"); c->p3_from_stage = value; return SAGEN_OK; }
     if (n == "decoder_planes") { c->dec_planes_min_batch = value ? 1 : (1 << 30); return SAGEN_OK; }
     if (n == "plane_gather") { c->use_p3g = c->use_p3 && value != 0; return SAGEN_OK; }
+    if (n == "plane_s2d") { c->use_s2d = value != 0; return SAGEN_OK; }
     return fail(SAGEN_ERR_UNSUPPORTED, "sagen_set_option: unknown option %s", name);
 }
 

@@ -60,6 +60,9 @@ __device__ __forceinline__ void p3_store(char* p3, long cstride, long pp, int c8
 
 // ---- format 1 ("H2", conv3h.hip): two fp16 planes (hi, lo) of v * 2^ka, [C/16][NP][2][16], 64 B per pixel and chunk ----
 size_t p3h_bytes(int B, int H, int W, int C) { return (size_t)(C / 16) * B * H * (W + 1) * 64; }
+// ... in space-to-depth form (conv3s.hip; H, W even): the four phase images (h & 1, w & 1), each [C/16][B*(H/2)*(W/2 + 1)][2][16], back to
+// back - a tensor consumed only at stride 2.  Every image row of every phase closes with its own zero pixel: 0.9 % more than the row-padded form.
+size_t p3s_bytes(int B, int H, int W, int C) { return (size_t)4 * (C / 16) * B * (H / 2) * (W / 2 + 1) * 64; }
 
 // 2^ka for the tensor this pass writes, from STATISTICS the forward already holds (no extra pass over the data):
 //   * the batch-norm branch: channel c of relu(bn(y)) has mean beta_c and standard deviation |gamma_c| sqrt(var_c / (var_c + eps))
@@ -151,7 +154,7 @@ template <bool H2>
 __global__ __launch_bounds__(256) void p3_pack_kernel(const float* __restrict__ x_, const float* __restrict__ scale_,
                                                       const float* __restrict__ shift_, const BnRef bn_,
                                                       const float* __restrict__ res_, int relu, float* __restrict__ y_,
-                                                      char* p3_, long nrows, int W, int C, const P3hScale h2_, const GroupInfo gi) {       // (p3 may alias h2.res_planes)
+                                                      char* p3_, long nrows, int W, int C, const P3hScale h2_, const GroupInfo gi, int s2d) {       // (p3 may alias h2.res_planes - not with s2d)
     // grouped launch (common.h): this workgroup's group = blockIdx.z, its tensors / accumulators / scales in that group's region
     const float* __restrict__ x = SAGEN_GRP(x_);
     const float* __restrict__ scale = SAGEN_GRP(scale_);
@@ -217,7 +220,17 @@ __global__ __launch_bounds__(256) void p3_pack_kernel(const float* __restrict__ 
             for (int k = 0; k < 8; ++k) v[k] = 0.f;
         }
         if (p3) {
-            if (H2) {
+            if (H2 && s2d) {
+                // space-to-depth form: the same values at another address.  The threads keep the (row, w, channel octet) order - x and the
+                // residual planes are still read in full lines - and pick the phase image per pixel; row = b*H + h with H even, so
+                // row >> 1 = b*(H/2) + ho and row & 1 = h & 1.  The thread of the row's pad pixel closes the row of BOTH column phases.
+                const int Wo = W >> 1;
+                const long cs = (nrows >> 1) * (Wo + 1) * 64, phs = (long)(C >> 4) * cs;
+                const long ps = (row >> 1) * (Wo + 1) + (w < W ? (w >> 1) : Wo);
+                char* const img = p3 + ((row & 1) * 2 + (w < W ? (w & 1) : 0)) * phs;
+                p3h_store(img, cs, ps, c8, v, sa, h2.sat_count);
+                if (w == W) p3h_store(img + phs, cs, ps, c8, v, sa, h2.sat_count);
+            } else if (H2) {
                 p3h_store(p3, cstride, pp, c8, v, sa, h2.sat_count);
             } else {
                 u32x4 hi, mid, lo;
@@ -241,13 +254,15 @@ static int aligned_grid(long total, int unit_threads, int amort = 1) {
 }
 
 int p3_pack_launch(const float* x, const float* scale, const float* shift, const BnRef& bn, const float* residual, int relu,
-                   float* y, void* p3, int B, int H, int W, int C, hipStream_t s, int fmt, const P3hScale* h2) {
+                   float* y, void* p3, int B, int H, int W, int C, hipStream_t s, int fmt, const P3hScale* h2, int s2d) {
     if (C % 16 || C > P3_MAX_C) return fail(SAGEN_ERR_UNSUPPORTED, "p3_pack: C=%d must be a multiple of 16, at most %d", C, P3_MAX_C);
     if (!y && !p3) return fail(SAGEN_ERR_NULL, "p3_pack: no output");
     const long nrows = (long)B * H;
     if (p3_bytes(B, H, W, C) >= (1UL << 31)) return fail(SAGEN_ERR_UNSUPPORTED, "p3_pack: tensor exceeds 2 GiB buffer addressing");
     const long total = nrows * (W + 1) * (C / 8);
     if (fmt == 1 && p3 && !(h2 && h2->a_inv)) return fail(SAGEN_ERR_NULL, "p3_pack: the fp16x2 format needs a slot for its scale");
+    if (s2d && (fmt != 1 || !p3 || (H & 1) || (W & 1) || p3 == (h2 ? h2->res_planes : nullptr)))
+        return fail(SAGEN_ERR_UNSUPPORTED, "p3_pack: the space-to-depth form needs fp16x2 planes of an even-sized tensor, not in place");
     static const int amort_env = getenv("SAGEN_P3_AMORT") ? atoi(getenv("SAGEN_P3_AMORT")) : 0;
     // (measured with three batches in flight, same box, tools/ab_p3_amort.sh: 1 / 2 / 4 items per thread = 2 508-2 524 / 2 519-2 529 / 2 536-2 544
     //  ambisonic-s/s - the pass alone is no faster with fewer workgroups, but it leaves the CUs to the other batches' matrix kernels sooner)
@@ -255,10 +270,10 @@ int p3_pack_launch(const float* x, const float* scale, const float* shift, const
     const GroupInfo gi = cur_group();
     if (fmt == 1)
         hipLaunchKernelGGL(p3_pack_kernel<true>, dim3(aligned_grid(total, C / 8, amort), 1, gi.G), dim3(256), 0, s, x, scale, shift, bn, residual, relu, y,
-                           (char*)p3, nrows, W, C, *h2, gi);
+                           (char*)p3, nrows, W, C, *h2, gi, s2d);
     else
         hipLaunchKernelGGL(p3_pack_kernel<false>, dim3(aligned_grid(total, C / 8, amort), 1, gi.G), dim3(256), 0, s, x, scale, shift, bn, residual, relu, y,
-                           (char*)p3, nrows, W, C, P3hScale(), gi);
+                           (char*)p3, nrows, W, C, P3hScale(), gi, 0);
     SAGEN_LAUNCH_CHECK();
     return SAGEN_OK;
 }
