@@ -361,6 +361,67 @@ size_t sagen_overlay_blend_scratch_bytes(int n_maps, int mh, int mw, int n_frame
 int sagen_overlay_blend(const float* maps, int n_maps, int64_t map0, int mh, int mw, const double* lut, const uint8_t* frames, int n_frames,
                         int64_t frame0, int h, int w, int frames_per_map, uint8_t* out, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- moving point sources: encode to ambisonics, binauralise, track ------------------------------------------------------
+ * The front end of the reference's ambisonics toolbox: AmbiEncoder.encode / encode_frame / encode_v2 (pyutils/ambisonics/
+ * encoder.py:10-55), SourceBinauralizer over VirtualStereoMic and Convolvotron, static and per frame (binauralizer.py:12-121), and
+ * the positions SphericalSourceVisualizer draws (distance.py:62-97), all over MovingSource.tic (position.py:73-102).  The reference
+ * walks these per audio sample in Python; here every sample is independent.  Coordinates: x front, y left, z up; polar
+ * (phi, nu, r); ACN / SN3D.
+ *
+ * Source s: a mono signal sig_s[0 .. N) fp32 at signals + s ld (device; ld >= every nframes), P_s >= 1 control points
+ * (phi_j, nu_j, r_j) fp64 in the rows pt_off[s] .. pt_off[s + 1] - 1 of ctrl [sum P][3] (device), duration[s] = N / float(rate),
+ * nframes[s] = int(duration rate) (position.py:78-82; it can be N - 1).  pt_off [n_sources + 1], nframes and duration [n_sources]
+ * are HOST arrays, read during the call.  n_sources <= 64 (SAGEN_ERR_UNSUPPORTED otherwise).
+ *
+ * Trajectory (MovingSource.tic, fp64, evaluated per sample i < nframes):
+ *   P == 1: the control point.  Otherwise idx = (i == nframes - 1) ? P - 1 : floor(i ((P - 1) / (double)(nframes - 1)))
+ *   (numpy's linspace followed by floor, :85); idx == P - 1: the last control point; otherwise
+ *   t_j = (j == P - 1) ? duration : j (duration / (P - 1)),  alpha = (i (1 / (double)rate) - t_idx) / (t_{idx+1} - t_idx),
+ *   (phi, nu, r) = alpha p_{idx+1} + (1 - alpha) p_idx                                                      (:98-100)
+ *   - linear in polar coordinates with no wrap handling; alpha may be slightly negative at a segment start.
+ *   Unit direction u = sgn(r) (cos phi cos nu, sin phi cos nu, sin nu), u = (1, 0, 0) when r == 0: what set_polar ->
+ *   calc_cartesian -> calc_polar leaves behind (:24-37).  Cartesian position: |r| u.
+ * Harmonics of u = (x, y, z), fp64 (common.py:136-157 in closed form):
+ *   W 1 | Y y | Z z | X x | V sqrt(3) x y | T sqrt(3) y z | R (3 z^2 - 1) / 2 | S sqrt(3) x z | U (sqrt(3) / 2)(x^2 - y^2)
+ *
+ * Every operation takes the WHOLE signals plus an absolute output range [t0, t0 + n): a stream rendered in pieces is bit-identical
+ * to one call.  The largest sample requested must be < min_s nframes[s] (the scripts' `while all(tic())` loop stops at the shortest
+ * source), SAGEN_ERR_SHAPE otherwise.  Trajectory, direction, distance and nearest index are fp64; the sample sums are fp32 with
+ * one accumulator in a fixed order: sources outermost, taps ascending.
+ *
+ * sagen_source_track: the direction, and optionally the nearest index in a direction set, of sample t0 + i stride, i < n.
+ *   unit [n][n_sources][3] fp64 or NULL; nearest [n][n_sources] int32 or NULL (needs dirs [n_dirs][3] fp64 unit vectors, device,
+ *   n_dirs <= 4096): the index with the maximum fp64 dot product with u; every candidate within 1e-12 of the maximum ties and the
+ *   lowest index wins (render.py: HrirSet.closest).  Signals are not read.
+ *
+ * sagen_encode_sources: ambi[t][c] = sum_s g_s(t) sig_s[t - d_s(t)] Y_c(u_s(t)), ambi [n][channels], channels 4 or 9.
+ *   distance_model == 0: g = 1, d = 0 (encode / encode_frame).  distance_model == 1 with radius > 0 (encode_v2, encoder.py:36-55):
+ *   dist = |r| - radius, d = int(dist / 343. rate), g = 1 / (1 + dist); a sample with t - d < 0 contributes 0.  For a static source
+ *   this is the reference, where scipy.ndimage.shift by an integer is an integer delay.  DEVIATION: the reference applies encode_v2
+ *   to static sources only; evaluating it per sample for a moving source is this project's extension.  |r| <= radius is the
+ *   caller's error (the Python layer raises ValueError); here such a sample reads sig at t - d > t, or nothing past nframes.
+ *
+ * sagen_binauralize_sources, y [n][2] (left, right):
+ *   SAGEN_SOURCES_MIC (VirtualStereoMic.binauralize_frame, binauralizer.py:38-55): ears at (0, +-0.1, 0); per ear e
+ *     dist = |pos - ear|, d = int(dist / 343. rate), y[t][e] = (1 / S) sum_s sig_s[t - d] / (1 + dist), terms with t - d < 0 dropped.
+ *   SAGEN_SOURCES_HRIR (Convolvotron, :58-90): near_s(t) = the nearest index of u_s(t) in dirs [n_dirs][3] (as in
+ *     sagen_source_track); y[t][e] = sum_s sum_{k < ntaps, t - k >= 0} hrir[near_s(t)][e][k] sig_s[t - k], hrir [n_dirs][2][ntaps] fp32
+ *     impulse responses in time order; outputs at t < zero_before are written as 0: zero_before = ntaps - 1 gives the static
+ *     binauralize (:63-76), 0 gives binauralize_frame (:78-90).  DEVIATION: the reference's frame form assigns instead of
+ *     accumulating, so only its last source survives; here the sources are summed, as in its static form (one source: the same).
+ *     n_dirs <= 4096, ntaps <= 512 (SAGEN_ERR_UNSUPPORTED otherwise).  dirs / hrir / n_dirs / ntaps / zero_before are ignored by the
+ *     mic mode.
+ * y must be 8-byte aligned, a 4-channel ambi 16-byte aligned. */
+enum { SAGEN_SOURCES_MIC = 0, SAGEN_SOURCES_HRIR = 1 };
+int sagen_source_track(const double* ctrl, const int32_t* pt_off, const int64_t* nframes, const double* duration, int n_sources, double rate,
+                       int64_t t0, int64_t n, int64_t stride, const double* dirs, int n_dirs, double* unit, int32_t* nearest, void* stream);
+int sagen_encode_sources(const float* signals, int64_t ld, const double* ctrl, const int32_t* pt_off, const int64_t* nframes,
+                         const double* duration, int n_sources, double rate, int channels, int distance_model, double radius, int64_t t0,
+                         int64_t n, float* ambi, void* stream);
+int sagen_binauralize_sources(const float* signals, int64_t ld, const double* ctrl, const int32_t* pt_off, const int64_t* nframes,
+                              const double* duration, int n_sources, double rate, int mode, const double* dirs, const float* hrir, int n_dirs,
+                              int ntaps, int64_t zero_before, int64_t t0, int64_t n, float* y, void* stream);
+
 /* ---- training step (reference train.py:137-236) -------------------------------------------------------
  * Loss of the reference: losses['stft/mse'] = metrics['stft/avg'] (model.py:156-159, 122-127; stft_for_loss myutils.py:151-178).
  * pred / target [B,4800,3]; mask [B,3] channel mask (the Y,Z,X columns of the feeder's [B,4] W,Y,Z,X mask, train.py:127) or NULL;

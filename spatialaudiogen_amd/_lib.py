@@ -8,6 +8,7 @@ LIB_PATH = os.environ.get('SAGEN_LIB') or os.path.join(HERE, 'libsagen_hip.so') 
 
 SAGEN_ENC_AUDIO, SAGEN_ENC_VIDEO, SAGEN_ENC_FLOW = 1, 2, 4
 SAGEN_SEP_NONE, SAGEN_SEP_FREQ_MASK = 0, 1
+SAGEN_SOURCES_MIC, SAGEN_SOURCES_HRIR = 0, 1
 
 
 class SagenError(RuntimeError):
@@ -86,6 +87,9 @@ SIGNATURES = {
     'sagen_power_map_windows': (C.c_int, [_P, _I64, _I, _I, _I64, _P, _I, _P, _P, _SZ, _P]),
     'sagen_overlay_blend_scratch_bytes': (_SZ, [_I] * 4),
     'sagen_overlay_blend': (C.c_int, [_P, _I, _I64, _I, _I, _P, _P, _I, _I64, _I, _I, _I, _P, _P, _SZ, _P]),
+    'sagen_source_track': (C.c_int, [_P, _P, _P, _P, _I, C.c_double, _I64, _I64, _I64, _P, _I, _P, _P, _P]),
+    'sagen_encode_sources': (C.c_int, [_P, _I64, _P, _P, _P, _P, _I, C.c_double, _I, _I, C.c_double, _I64, _I64, _P, _P]),
+    'sagen_binauralize_sources': (C.c_int, [_P, _I64, _P, _P, _P, _P, _I, C.c_double, _I, _P, _P, _I, _I, _I64, _I64, _I64, _P, _P]),
     'sagen_stft_loss_grad': (C.c_int, [_P, _P, _P, _I, _P, _P, _P]),
     'sagen_adam_update': (C.c_int, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _P]),
     'sagen_power_map_batched': (C.c_int, [_P, _I, _I64, _P, _I, _P, _P, _P]),

@@ -20,6 +20,7 @@
 
 #include "../../include/sagen.h"
 #include "../csrc/emd_core.h"
+#include "../csrc/sources_core.h"
 
 namespace {
 
@@ -483,6 +484,127 @@ int sagen_eval_emd(const float* p, const float* q, int n_maps, int nodes, const 
             emd[m * 2 + var] = sagen::emd_hat(w, st[0], P.data(), Q.data(), nodes, cost, &conv);
             if (!conv) ++*not_converged;
         }
+    return SAGEN_OK;
+}
+
+/* Moving point sources (include/sagen.h; encoder.py:10-55, binauralizer.py:12-121, distance.py:62-97 over position.py:73-102): a loop
+ * per sample and source over the fp64 core the device uses (csrc/sources_core.h), the sample sums in double */
+namespace {
+struct SrcPoint { double r, u[3]; };
+SrcPoint src_at(const double* ctrl, const sagen::SourceSet& ss, int s, int64_t t) {
+    SrcPoint p;
+    double phi, nu;
+    const int p0 = ss.pt_off[s];
+    sagen::source_polar(ctrl + (size_t)p0 * 3, ss.pt_off[s + 1] - p0, ss.nframes[s], ss.duration[s], ss.rate, t, phi, nu, p.r);
+    sagen::source_unit(phi, nu, p.r, p.u);
+    return p;
+}
+int src_nearest(const double* dirs, int D, const double u[3]) {
+    const int f = sagen::nearest_first(dirs, 0, D, u, sagen::nearest_max(dirs, D, u, -INFINITY), -1);
+    return f < 0 ? 0 : f;
+}
+int src_fill(const char* who, sagen::SourceSet& ss, const double* ctrl, const int32_t* pt_off, const int64_t* nframes, const double* duration,
+             int n_sources, double rate, int64_t t_first, int64_t t_last) {
+    const char* why;
+    const int rc = sagen::source_set_fill(ss, ctrl, pt_off, nframes, duration, n_sources, rate, t_first, t_last, &why);
+    return rc == SAGEN_OK ? rc : fail(rc, "%s: %s", who, why);
+}
+}  // namespace
+
+int sagen_source_track(const double* ctrl, const int32_t* pt_off, const int64_t* nframes, const double* duration, int n_sources, double rate,
+                       int64_t t0, int64_t n, int64_t stride, const double* dirs, int n_dirs, double* unit, int32_t* nearest, void*) {
+    if (!unit && !nearest) return fail(SAGEN_ERR_NULL, "sagen_source_track: null argument (unit and nearest)");
+    if (nearest && !dirs) return fail(SAGEN_ERR_NULL, "sagen_source_track: nearest needs dirs");
+    if (n < 1 || stride < 1 || (nearest && n_dirs < 1)) return fail(SAGEN_ERR_SHAPE, "sagen_source_track: bad sizes");
+    if (nearest && n_dirs > sagen::SRC_MAX_DIRS) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_source_track: n_dirs=%d", n_dirs);
+    sagen::SourceSet ss;
+    const int rc = src_fill("sagen_source_track", ss, ctrl, pt_off, nframes, duration, n_sources, rate, t0, t0 + (n - 1) * stride);
+    if (rc != SAGEN_OK) return rc;
+    for (int64_t i = 0; i < n; ++i)
+        for (int s = 0; s < n_sources; ++s) {
+            const SrcPoint p = src_at(ctrl, ss, s, t0 + i * stride);
+            if (unit)
+                for (int k = 0; k < 3; ++k) unit[(i * n_sources + s) * 3 + k] = p.u[k];
+            if (nearest) nearest[i * n_sources + s] = src_nearest(dirs, n_dirs, p.u);
+        }
+    return SAGEN_OK;
+}
+
+int sagen_encode_sources(const float* signals, int64_t ld, const double* ctrl, const int32_t* pt_off, const int64_t* nframes,
+                         const double* duration, int n_sources, double rate, int channels, int distance_model, double radius, int64_t t0,
+                         int64_t n, float* ambi, void*) {
+    if (!signals || !ambi) return fail(SAGEN_ERR_NULL, "sagen_encode_sources: null argument");
+    if (n < 1 || ld < 1 || channels < 1) return fail(SAGEN_ERR_SHAPE, "sagen_encode_sources: bad sizes");
+    if (channels != 4 && channels != 9) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_encode_sources: channels=%d", channels);
+    if (distance_model != 0 && !(distance_model == 1 && radius > 0.)) return fail(SAGEN_ERR_SHAPE, "sagen_encode_sources: distance_model=%d radius=%g", distance_model, radius);
+    sagen::SourceSet ss;
+    const int rc = src_fill("sagen_encode_sources", ss, ctrl, pt_off, nframes, duration, n_sources, rate, t0, t0 + n - 1);
+    if (rc != SAGEN_OK) return rc;
+    for (int s = 0; s < n_sources; ++s)
+        if (ld < nframes[s]) return fail(SAGEN_ERR_SHAPE, "sagen_encode_sources: ld=%ld is shorter than a source's nframes", (long)ld);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t t = t0 + i;
+        double acc[9] = {0.};
+        for (int s = 0; s < n_sources; ++s) {
+            const SrcPoint p = src_at(ctrl, ss, s, t);
+            double Y[9];
+            if (channels == 4) sagen::source_harmonics<4>(p.u, Y); else sagen::source_harmonics<9>(p.u, Y);
+            double g = 1.;
+            long long d = 0;
+            if (distance_model) {
+                const double dist = std::fabs(p.r) - radius;
+                if (!sagen::source_delay(dist, rate, d)) continue;
+                g = 1. / (1. + dist);
+            }
+            const int64_t j = t - d;
+            if (j < 0 || j >= nframes[s]) continue;
+            for (int c = 0; c < channels; ++c) acc[c] += g * Y[c] * (double)signals[s * ld + j];
+        }
+        for (int c = 0; c < channels; ++c) ambi[i * channels + c] = (float)acc[c];
+    }
+    return SAGEN_OK;
+}
+
+int sagen_binauralize_sources(const float* signals, int64_t ld, const double* ctrl, const int32_t* pt_off, const int64_t* nframes,
+                              const double* duration, int n_sources, double rate, int mode, const double* dirs, const float* hrir, int n_dirs,
+                              int ntaps, int64_t zero_before, int64_t t0, int64_t n, float* y, void*) {
+    if (!signals || !y) return fail(SAGEN_ERR_NULL, "sagen_binauralize_sources: null argument");
+    if (mode != SAGEN_SOURCES_MIC && mode != SAGEN_SOURCES_HRIR) return fail(SAGEN_ERR_SHAPE, "sagen_binauralize_sources: mode=%d", mode);
+    const bool h = mode == SAGEN_SOURCES_HRIR;
+    if (h && (!dirs || !hrir)) return fail(SAGEN_ERR_NULL, "sagen_binauralize_sources: the hrir mode needs dirs and hrir");
+    if (n < 1 || ld < 1 || (h && (n_dirs < 1 || ntaps < 1))) return fail(SAGEN_ERR_SHAPE, "sagen_binauralize_sources: bad sizes");
+    if (h && (n_dirs > sagen::SRC_MAX_DIRS || ntaps > sagen::SRC_MAX_TAPS))
+        return fail(SAGEN_ERR_UNSUPPORTED, "sagen_binauralize_sources: n_dirs=%d ntaps=%d", n_dirs, ntaps);
+    sagen::SourceSet ss;
+    const int rc = src_fill("sagen_binauralize_sources", ss, ctrl, pt_off, nframes, duration, n_sources, rate, t0, t0 + n - 1);
+    if (rc != SAGEN_OK) return rc;
+    for (int s = 0; s < n_sources; ++s)
+        if (ld < nframes[s]) return fail(SAGEN_ERR_SHAPE, "sagen_binauralize_sources: ld=%ld is shorter than a source's nframes", (long)ld);
+    for (int64_t i = 0; i < n; ++i) {
+        const int64_t t = t0 + i;
+        double acc[2] = {0., 0.};
+        for (int s = 0; s < n_sources; ++s) {
+            const SrcPoint p = src_at(ctrl, ss, s, t);
+            const float* sig = signals + s * ld;
+            if (h) {
+                const float* hp = hrir + (size_t)src_nearest(dirs, n_dirs, p.u) * 2 * ntaps;
+                for (int e = 0; e < 2; ++e)
+                    for (int k = 0; k < ntaps && t - k >= 0; ++k) acc[e] += (double)hp[e * ntaps + k] * (double)sig[t - k];
+                continue;
+            }
+            const double ar = std::fabs(p.r);
+            for (int e = 0; e < 2; ++e) {
+                const double dx = ar * p.u[0], dy = ar * p.u[1] - (e == 0 ? sagen::SRC_EAR_Y : -sagen::SRC_EAR_Y), dz = ar * p.u[2];
+                const double dist = std::sqrt(dx * dx + dy * dy + dz * dz);
+                long long d;
+                if (!sagen::source_delay(dist, rate, d) || t - d < 0 || t - d >= nframes[s]) continue;
+                acc[e] += (double)sig[t - d] / (1. + dist) / (double)n_sources;
+            }
+        }
+        const bool z = h && t < zero_before;
+        y[i * 2] = z ? 0.f : (float)acc[0];
+        y[i * 2 + 1] = z ? 0.f : (float)acc[1];
+    }
     return SAGEN_OK;
 }
 

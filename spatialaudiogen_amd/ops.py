@@ -258,6 +258,87 @@ def render_fir(x, n_hist, taps, rot=None, rot_hop=4800, pos0=0, zero_before=0):
     return y
 
 
+# ---- moving point sources (include/sagen.h: sagen_source_track / sagen_encode_sources / sagen_binauralize_sources) ------------------
+class SourceTable(object):
+    """The flat arrays the three entries take: ctrl [sum P, 3] float64 on the device, and pt_off / nframes / duration on the host.
+    control_points: per source a [P >= 1, 3] array of (phi, nu, r); lengths: per source the signal length N; nframes =
+    int((N / float(rate)) * rate) as position.py:78-82 computes it."""
+
+    def __init__(self, control_points, lengths, rate, device):
+        import numpy as np
+        pts = [np.asarray(p, np.float64).reshape(-1, 3) for p in control_points]
+        if not pts or len(pts) != len(lengths) or any(len(p) < 1 for p in pts):
+            raise ValueError('SourceTable: one [P >= 1, 3] control-point array and one length per source expected')
+        self.n_sources, self.rate = len(pts), float(rate)
+        self.pt_off = np.concatenate([[0], np.cumsum([len(p) for p in pts])]).astype(np.int32)
+        self.duration = np.array([int(n) / float(rate) for n in lengths], np.float64)
+        self.nframes = np.array([int(d * rate) for d in self.duration], np.int64)
+        self.ctrl = torch.as_tensor(np.concatenate(pts, 0)).contiguous().to(device)
+
+    def args(self):
+        host = lambda a: C.c_void_p(a.ctypes.data)
+        return (_ptr(self.ctrl), host(self.pt_off), host(self.nframes), host(self.duration), self.n_sources, self.rate)
+
+
+def _f64_dirs(dirs, table):
+    if not (isinstance(dirs, torch.Tensor) and dirs.dtype == torch.float64 and dirs.dim() == 2 and dirs.shape[1] == 3
+            and dirs.device == table.ctrl.device):
+        raise TypeError('dirs must be a [D, 3] float64 tensor on the device of the sources')
+    return dirs.contiguous()
+
+
+def source_track(table, t0, n, stride=1, dirs=None, unit=True):
+    """Direction (unit [n, S, 3] float64) and / or nearest index in dirs [D, 3] (nearest [n, S] int32) of the samples
+    t0 + i stride, i < n, of every source of a SourceTable."""
+    dev = table.ctrl.device
+    u = torch.empty(int(n), table.n_sources, 3, dtype=torch.float64, device=dev) if unit else None
+    near = None
+    if dirs is not None:
+        dirs = _f64_dirs(dirs, table)
+        near = torch.empty(int(n), table.n_sources, dtype=torch.int32, device=dev)
+    check(_lib.lib().sagen_source_track(*(table.args() + (int(t0), int(n), int(stride), _ptr(dirs), 0 if dirs is None else dirs.shape[0],
+                                                       _ptr(u), _ptr(near), _stream()))))
+    return u, near
+
+
+def _source_signals(signals, table):
+    signals = _f32(signals, 'signals')
+    if signals.dim() != 2 or signals.shape[0] != table.n_sources or signals.device != table.ctrl.device:
+        raise ValueError('signals [S = %d, ld] expected, on the device of the sources' % table.n_sources)
+    return signals
+
+
+def encode_sources(signals, table, channels, t0, n, distance_model=False, radius=1.):
+    """ambi [n, channels] = sum_s g_s sig_s[t - d_s] Y(u_s(t)) for t in [t0, t0 + n) (AmbiEncoder.encode / encode_frame;
+    distance_model: encode_v2 per sample)."""
+    signals = _source_signals(signals, table)
+    ambi = torch.empty(max(int(n), 0), int(channels), dtype=torch.float32, device=signals.device)
+    check(_lib.lib().sagen_encode_sources(*((_ptr(signals), signals.shape[1]) + table.args() + (int(channels), int(bool(distance_model)),
+                                                                                               float(radius), int(t0), int(n), _ptr(ambi), _stream()))))
+    return ambi
+
+
+def binauralize_sources(signals, table, mode, t0, n, dirs=None, hrir=None, zero_before=0):
+    """y [n, 2] for t in [t0, t0 + n): mode 'mic' (VirtualStereoMic.binauralize_frame) or 'hrir' (Convolvotron; dirs [D, 3] float64,
+    hrir [D, 2, K] float32, outputs below zero_before written as 0)."""
+    signals = _source_signals(signals, table)
+    if mode not in ('mic', 'hrir'):
+        raise ValueError("binauralize_sources: mode 'mic' or 'hrir' expected")
+    D = K = 0
+    if mode == 'hrir':
+        dirs, hrir = _f64_dirs(dirs, table), _f32(hrir, 'hrir')
+        if hrir.dim() != 3 or hrir.shape[0] != dirs.shape[0] or hrir.shape[1] != 2:
+            raise ValueError('binauralize_sources: hrir [D, 2, K] expected')
+        D, K = hrir.shape[0], hrir.shape[2]
+    else:
+        dirs = hrir = None
+    y = torch.empty(max(int(n), 0), 2, dtype=torch.float32, device=signals.device)
+    check(_lib.lib().sagen_binauralize_sources(*((_ptr(signals), signals.shape[1]) + table.args() + (
+        _lib.SAGEN_SOURCES_HRIR if mode == 'hrir' else _lib.SAGEN_SOURCES_MIC, _ptr(dirs), _ptr(hrir), D, K, int(zero_before), int(t0), int(n), _ptr(y),
+        _stream()))))
+    return y
+
+
 # ---- backward, op level (the gradients tf.gradients builds for the wrappers above; include/sagen.h) -----------------------
 def _out(out, shape, like, name):
     """The caller's output tensor (tests prefill it to see every element written) or a fresh one."""
