@@ -313,10 +313,7 @@ int sagen_fc(const float* x, int m, int k, const float* w_kn, int n, const float
         if (rc) return rc;
         // low-parallelism rows: split K so the weight stream is spread over the chip
         IgemmTile tile = igemm_pick_tile(d);
-        const int bm = tile == TILE_32x128 ? 32 : 64, bn = tile == TILE_32x128 ? 128 : 64;
-        const long blocks = (long)cdiv(m, bm) * cdiv(n, bn);
-        int sk = 1;
-        if (blocks < 384 && d.Kpad / 16 >= 16) sk = (int)std::min<long>({(512 + blocks - 1) / blocks, (long)d.Kpad / 16 / 8, 64L});
+        const int sk = igemm_auto_splitk(d, tile);
         if (sk > 1) {
             d.splitk = sk; d.splitk_ws = ws;
             rc = igemm_launch(d, tile, s);

@@ -371,9 +371,9 @@ int conv3g_dispatch(const IgemmDesc& d_in, IgemmTile tile, hipStream_t s) {
         return fail(SAGEN_ERR_UNSUPPORTED, "conv3g: too many pixels for 32-bit index arithmetic");
     if ((long)d.p3_np * 96 >= (1L << 31) || (long)d.xp3_cstride * (d.Cin / 16) >= (1L << 31) || d.xp3_bytes == 0)
         return fail(SAGEN_ERR_UNSUPPORTED, "conv3g: the activation planes exceed 2 GiB buffer addressing (use a smaller batch)");
-    const bool mm = tile == TILE_P3GH_MM_64x128_K2 || tile == TILE_P3GH_MM_64x128_K4 || tile == TILE_P3GH_MM_128x128_K2 || tile == TILE_P3GH_MM_128x256_K2;
+    const bool mm = igemm_tile_traits(tile) & TF_FUSED_TAIL;
     if (mm != (d.mm_out != nullptr)) return fail(SAGEN_ERR_UNSUPPORTED, "conv3g: the fused decoder tail and the tile do not match");
-    const bool h2 = mm || tile == TILE_P3GH_128x64_K3 || tile == TILE_P3GH_64x64_K4 || tile == TILE_P3GH_128x128_K2 || tile == TILE_P3GH_64x128_K3;
+    const bool h2 = igemm_tile_traits(tile) & TF_FP16X2;
     if (h2 != (d.xp3_fmt == 1)) return fail(SAGEN_ERR_UNSUPPORTED, "conv3g: the planes' format does not match the tile");
     if (h2 && (!d.wh2 || !d.h2_a_inv || !d.h2_w_inv)) return fail(SAGEN_ERR_NULL, "conv3g: the fp16x2 filter planes / scales are missing");
     if (!mm) {
@@ -383,19 +383,11 @@ int conv3g_dispatch(const IgemmDesc& d_in, IgemmTile tile, hipStream_t s) {
     }
     d.p3_magic_wp = (unsigned)((1UL << 32) / (unsigned)d.Wg) + 1u;      // (reused fields: here the divisors are the OUTPUT grid's Wg, Hg)
     d.p3_magic_h = (unsigned)((1UL << 32) / (unsigned)d.Hg) + 1u;
+#define SAGEN_TILE_HAS_P3G ,
+#define SAGEN_TILE_HAS_P3GH ,
+#define SAGEN_TILE_HAS_P3GH_MM ,
     switch (tile) {
-        case TILE_P3G_128x64_K2: return launch_conv3g<128, 64, 64, 32, 2, false>(d, s);
-        case TILE_P3G_64x64_K2: return launch_conv3g<64, 64, 32, 32, 2, false>(d, s);
-        case TILE_P3G_64x128_K2: return launch_conv3g<64, 128, 32, 64, 2, false>(d, s);
-        case TILE_P3G_128x128_K1: return launch_conv3g<128, 128, 64, 64, 1, false>(d, s);
-        case TILE_P3GH_128x64_K3: return launch_conv3g<128, 64, 64, 32, 3, true>(d, s);
-        case TILE_P3GH_64x64_K4: return launch_conv3g<64, 64, 32, 32, 4, true>(d, s);
-        case TILE_P3GH_128x128_K2: return launch_conv3g<128, 128, 64, 64, 2, true>(d, s);
-        case TILE_P3GH_64x128_K3: return launch_conv3g<64, 128, 32, 64, 3, true>(d, s);
-        case TILE_P3GH_MM_64x128_K2: return launch_conv3g<64, 128, 32, 64, 2, true, 1>(d, s);
-        case TILE_P3GH_MM_64x128_K4: return launch_conv3g<64, 128, 32, 64, 4, true, 1>(d, s);
-        case TILE_P3GH_MM_128x128_K2: return launch_conv3g<128, 128, 64, 64, 2, true, 1>(d, s);
-        case TILE_P3GH_MM_128x256_K2: return launch_conv3g<128, 256, 64, 128, 2, true, 1>(d, s);
+        SAGEN_TILES(SAGEN_TILE_CASE)
         default: return fail(SAGEN_ERR_UNSUPPORTED, "conv3g: bad tile id %d", (int)tile);
     }
 }

@@ -85,18 +85,10 @@ int conv3h_dispatch(const IgemmDesc& d_in, IgemmTile tile, hipStream_t s) {
     d.y_bytes = (unsigned)y_bytes;
     d.p3_magic_wp = (unsigned)((1UL << 32) / (unsigned)(d.Win + 1)) + 1u;
     d.p3_magic_h = (unsigned)((1UL << 32) / (unsigned)d.Hin) + 1u;
+#define SAGEN_TILE_HAS_P3H ,
+#define SAGEN_TILE_HAS_P3HR ,
     switch (tile) {
-        case TILE_P3H_128x64: return launch_conv3h<128, 64, 64, 32, 1>(d, s);
-        case TILE_P3H_128x128: return launch_conv3h<128, 128, 64, 64, 1>(d, s);
-        case TILE_P3H_64x64: return launch_conv3h<64, 64, 32, 32, 1>(d, s);
-        case TILE_P3H_256x64: return launch_conv3h<256, 64, 64, 64, 1>(d, s);
-        case TILE_P3H_128x64_C2: return launch_conv3h<128, 64, 64, 32, 2>(d, s);
-        case TILE_P3H_64x64_C2: return launch_conv3h<64, 64, 32, 32, 2>(d, s);
-        case TILE_P3H_64x64_C4: return launch_conv3h<64, 64, 32, 32, 4>(d, s);
-        case TILE_P3HR_256x64: return launch_conv3h<256, 64, 64, 64, 1, 3>(d, s);
-        case TILE_P3HR_128x64: return launch_conv3h<128, 64, 64, 32, 1, 3>(d, s);
-        case TILE_P3HR_64x64_C2: return launch_conv3h<64, 64, 32, 32, 2, 3>(d, s);
-        case TILE_P3HR_128x128: return launch_conv3h<128, 128, 64, 64, 1, 3>(d, s);
+        SAGEN_TILES(SAGEN_TILE_CASE)
         default: return fail(SAGEN_ERR_UNSUPPORTED, "conv3h: bad tile id %d", (int)tile);
     }
 }

@@ -749,12 +749,10 @@ int conv3p_dispatch(const IgemmDesc& d_in, IgemmTile tile, hipStream_t s) {
     if (cdiv(d.p3_np, 62) * (long)cdiv(d.N, 64) >= (1L << 24)) return fail(SAGEN_ERR_UNSUPPORTED, "conv3p: too many tiles");
     d.p3_magic_wp = (unsigned)((1UL << 32) / (unsigned)(d.Win + 1)) + 1u;
     d.p3_magic_h = (unsigned)((1UL << 32) / (unsigned)d.Hin) + 1u;
+#define SAGEN_TILE_HAS_P3 ,
+#define SAGEN_TILE_HAS_P3PP ,
     switch (tile) {
-        case TILE_P3_128x64: return launch_conv3p<128, 64, 64, 32>(d, s);
-        case TILE_P3_128x128: return launch_conv3p<128, 128, 64, 64>(d, s);
-        case TILE_P3_64x64: return launch_conv3p<64, 64, 32, 32>(d, s);
-        case TILE_P3PP_PAIR: return launch_conv3pp<0>(d, s);
-        case TILE_P3PP_SPLITK: return launch_conv3pp<1>(d, s);
+        SAGEN_TILES(SAGEN_TILE_CASE)
         default: return fail(SAGEN_ERR_UNSUPPORTED, "conv3p: bad tile id %d", (int)tile);
     }
 }

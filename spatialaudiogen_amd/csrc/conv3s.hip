@@ -67,10 +67,9 @@ int conv3s_dispatch(const IgemmDesc& d_in, IgemmTile tile, hipStream_t s) {
     d.y_bytes = (unsigned)y_bytes;
     d.p3_magic_wp = (unsigned)((1UL << 32) / (unsigned)(d.Wg + 1)) + 1u;      // (here the divisors are the OUTPUT grid's Wg + 1, Hg)
     d.p3_magic_h = (unsigned)((1UL << 32) / (unsigned)d.Hg) + 1u;
+#define SAGEN_TILE_HAS_P3S ,
     switch (tile) {
-        case TILE_P3S_128x128: return launch_conv3s<128, 128, 64, 64, 1, 2>(d, s);
-        case TILE_P3SR_128x64: return launch_conv3s<128, 64, 64, 32, 1, 3>(d, s);
-        case TILE_P3SR_256x64: return launch_conv3s<256, 64, 64, 64, 1, 3>(d, s);
+        SAGEN_TILES(SAGEN_TILE_CASE)
         default: return fail(SAGEN_ERR_UNSUPPORTED, "conv3s: bad tile id %d", (int)tile);
     }
 }

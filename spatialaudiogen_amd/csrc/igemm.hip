@@ -299,52 +299,20 @@ static int launch_cfg(const IgemmDesc& d, hipStream_t s) {
     return SAGEN_OK;
 }
 
-struct TileCfg { int bm, bn, bk; const char* name; bool split = false; bool dw3 = false; bool s2 = false; bool p3 = false; bool g = false; bool h = false; bool s2d = false; };
-static const TileCfg kTiles[TILE_AUTO] = {
-    {128, 128, 16, "igemm_kernel<128,128,64,64,3,16>"}, {128, 64, 16, "igemm_kernel<128,64,64,32,3,16>"},
-    {256, 64, 16, "igemm_kernel<256,64,64,64,3,16>"},   {64, 64, 16, "igemm_kernel<64,64,32,32,3,16>"},
-    {128, 32, 16, "igemm_kernel<128,32,32,32,2,16>"},   {32, 128, 16, "igemm_kernel<32,128,32,32,2,16>"},
-    {128, 128, 16, "igemm_kernel<128,128,64,64,2,16>"}, {128, 64, 16, "igemm_kernel<128,64,64,32,2,16>"},
-    {256, 64, 16, "igemm_kernel<256,64,64,64,2,16>"},   {64, 64, 16, "igemm_kernel<64,64,32,32,2,16>"},
-    {64, 128, 16, "igemm_kernel<64,128,32,64,3,16>"},   {64, 128, 16, "igemm_kernel<64,128,32,64,2,16>"},
-    {64, 256, 16, "igemm_kernel<64,256,64,64,3,16>"},   {64, 256, 16, "igemm_kernel<64,256,64,64,2,16>"},
-    {256, 32, 16, "igemm_kernel<256,32,64,32,2,16>"},
-    {64, 64, 32, "igemm_kernel<64,64,32,32,2,32>"},     {64, 128, 32, "igemm_kernel<64,128,32,64,2,32>"},
-    {128, 64, 32, "igemm_kernel<128,64,64,32,2,32>"},   {128, 128, 32, "igemm_kernel<128,128,64,64,2,32>"},
-    {32, 128, 32, "igemm_kernel<32,128,32,32,2,32>"},   {128, 32, 32, "igemm_kernel<128,32,32,32,2,32>"},
-    // fp32-equivalent bf16x3 kernels (igemm3.hip)
-    {128, 128, 16, "igemm3_kernel<128,128,64,64,1>", true}, {128, 64, 16, "igemm3_kernel<128,64,64,32,1>", true},
-    {256, 64, 16, "igemm3_kernel<256,64,64,64,1>", true},   {64, 64, 16, "igemm3_kernel<64,64,32,32,1>", true},
-    {64, 128, 16, "igemm3_kernel<64,128,32,64,1>", true},   {64, 256, 16, "igemm3_kernel<64,256,64,64,1>", true},
-    {32, 128, 16, "igemm3_kernel<32,128,32,32,1>", true},   {128, 32, 16, "igemm3_kernel<128,32,32,32,1>", true},
-    {128, 64, 16, "igemm3_kernel<128,64,64,32,2>", true},   {64, 64, 16, "igemm3_kernel<64,64,32,32,2>", true},
-    {64, 128, 16, "igemm3_kernel<64,128,32,64,2>", true},   {32, 128, 16, "igemm3_kernel<32,128,32,32,2>", true},
-    {128, 32, 16, "igemm3_kernel<128,32,32,32,2>", true},
-    {128, 128, 16, "igemm3dw_kernel<128,128,64,64,false>", true, true}, {128, 64, 16, "igemm3dw_kernel<128,64,64,32,false>", true, true},
-    {256, 64, 16, "igemm3dw_kernel<256,64,64,64,false>", true, true},   {64, 128, 16, "igemm3dw_kernel<64,128,32,64,false>", true, true},
-    {64, 64, 16, "igemm3dw_kernel<64,64,32,32,false>", true, true},     {64, 256, 16, "igemm3dw_kernel<64,256,64,64,false>", true, true},
-    {128, 64, 16, "igemm3dw_kernel<128,64,64,32,true>", true, true},    {256, 64, 16, "igemm3dw_kernel<256,64,64,64,true>", true, true},
-    {64, 64, 16, "igemm3dw_kernel<64,64,32,32,true>", true, true},      {64, 128, 16, "igemm3dw_kernel<64,128,32,64,true>", true, true},
-    {256, 64, 16, "igemm3s2_kernel<256,64,64,64>", true, false, true},  {128, 64, 16, "igemm3s2_kernel<128,64,64,32>", true, false, true},
-    {128, 64, 16, "conv3p_kernel<128,64,64,32>", true, true, false, true},   {128, 128, 16, "conv3p_kernel<128,128,64,64>", true, true, false, true},
-    {64, 64, 16, "conv3p_kernel<64,64,32,32>", true, true, false, true},
-    {128, 64, 16, "conv3pp_kernel<0>", true, true, false, true},          {128, 64, 16, "conv3pp_kernel<1>", true, true, false, true},
-    {128, 64, 16, "conv3g_kernel<128,64,64,32,2,false>", true, false, false, true, true}, {64, 64, 16, "conv3g_kernel<64,64,32,32,2,false>", true, false, false, true, true},
-    {64, 128, 16, "conv3g_kernel<64,128,32,64,2,false>", true, false, false, true, true}, {128, 128, 16, "conv3g_kernel<128,128,64,64,1,false>", true, false, false, true, true},
-    {128, 64, 16, "conv3h_kernel<128,64,64,32,1>", true, true, false, true, false, true},   {128, 128, 16, "conv3h_kernel<128,128,64,64,1>", true, true, false, true, false, true},
-    {64, 64, 16, "conv3h_kernel<64,64,32,32,1>", true, true, false, true, false, true},      {256, 64, 16, "conv3h_kernel<256,64,64,64,1>", true, true, false, true, false, true},
-    {128, 64, 16, "conv3g_kernel<128,64,64,32,3,true>", true, false, false, true, true, true},   {64, 64, 16, "conv3g_kernel<64,64,32,32,4,true>", true, false, false, true, true, true},
-    {128, 128, 16, "conv3g_kernel<128,128,64,64,2,true>", true, false, false, true, true, true}, {64, 128, 16, "conv3g_kernel<64,128,32,64,3,true>", true, false, false, true, true, true},
-    {128, 64, 32, "conv3h_kernel<128,64,64,32,2>", true, true, false, true, false, true}, {64, 64, 32, "conv3h_kernel<64,64,32,32,2>", true, true, false, true, false, true},
-    {64, 64, 64, "conv3h_kernel<64,64,32,32,4>", true, true, false, true, false, true},
-    {64, 128, 16, "conv3g_kernel<64,128,32,64,2,true,1>", true, false, false, true, true, true}, {64, 128, 16, "conv3g_kernel<64,128,32,64,4,true,1>", true, false, false, true, true, true},
-    {128, 128, 16, "conv3g_kernel<128,128,64,64,2,true,1>", true, false, false, true, true, true}, {128, 256, 16, "conv3g_kernel<128,256,64,128,2,true,1>", true, false, false, true, true, true},
-    {256, 64, 16, "conv3hr_kernel<256,64,64,64,1>", true, true, false, true, false, true}, {128, 64, 16, "conv3hr_kernel<128,64,64,32,1>", true, true, false, true, false, true},
-    {64, 64, 32, "conv3hr_kernel<64,64,32,32,2>", true, true, false, true, false, true},
-    {128, 128, 16, "conv3hr_kernel<128,128,64,64,1>", true, true, false, true, false, true},
-    {128, 128, 16, "conv3h_kernel<128,128,64,64,1,2,true>", true, false, false, true, false, true, true}, {128, 64, 16, "conv3h_kernel<128,64,64,32,1,3,true>", true, false, false, true, false, true, true},
-    {256, 64, 16, "conv3h_kernel<256,64,64,64,1,3,true>", true, false, false, true, false, true, true},
-};
+// the tile table: one entry per row of the registry (igemm_tiles.h) + one for every id outside it
+struct TileShape { int bm = 0, bn = 0, bk = 0; };
+struct TileCfg { const char* name; unsigned traits; TileShape sh; };
+// BM and BN are the first two template arguments; bk = the BK argument of igemm_kernel, 16 * KC for the conv3h_kernel body (fp16x2, not
+// gathered), else 16.  `given`: the shape of a row whose arguments do not carry it.
+static constexpr TileCfg tile_cfg(const char* name, unsigned traits, std::initializer_list<int> args, TileShape given) {
+    const int* a = args.begin();
+    const int bk = !(traits & (TF_BF16X3 | TF_FP16X2)) ? a[5] : (traits & TF_FP16X2) && !(traits & TF_GATHERED) ? 16 * a[4] : 16;
+    return {name, traits, given.bm ? given : TileShape{a[0], a[1], bk}};
+}
+#define SAGEN_TILE_CFG_USE(id, name, traits, ...) name, traits
+#define SAGEN_TILE_CFG(id, fam, args, ...) tile_cfg(SAGEN_TILE_FAM_##fam(SAGEN_TILE_CFG_USE, id, SAGEN_TILE_UNWRAP args), {SAGEN_TILE_UNWRAP args}, {__VA_ARGS__}),
+static constexpr TileCfg kTiles[TILE_AUTO + 1] = {SAGEN_TILES(SAGEN_TILE_CFG) {"igemm_kernel<?>", 0, {}}};
+static const TileCfg& cfg_of(IgemmTile t) { return kTiles[(t >= 0 && t < TILE_AUTO) ? t : TILE_AUTO]; }
 // igemm3s2_kernel: the 7x(7->8)x4 stride-2 stem over a pre-padded dense image
 static bool s2_ok(const IgemmDesc& d) {
     return d.Cin == 4 && d.ldx == 4 && d.ntaps == 56 && d.TW == 8 && d.in_sh == 2 && d.in_sw == 2 && d.tap_sh == 1 && d.tap_sw == 1 &&
@@ -358,55 +326,49 @@ static bool dw3_ok(const IgemmDesc& d) {
            d.in_sw == 1 && d.dsh * d.dsw == 1 && d.Hin == d.Hg && d.Win == d.Wg && d.g_h0 == 0 && d.g_w0 == 0 && d.Cin % 16 == 0 &&
            d.K == 9 * d.Cin && d.Kpad == d.K && d.x_bstride == (long)d.Hin * d.Win * d.ldx && d.Hin >= 2 && d.Win >= 8;
 }
-bool igemm_tile_split(IgemmTile t) { return t >= 0 && t < TILE_AUTO && kTiles[t].split; }
-bool igemm_tile_p3(IgemmTile t) { return t >= 0 && t < TILE_AUTO && kTiles[t].p3; }
+unsigned igemm_tile_traits(IgemmTile t) { return cfg_of(t).traits; }
+bool igemm_tile_split(IgemmTile t) { return cfg_of(t).traits & (TF_BF16X3 | TF_FP16X2); }
+bool igemm_tile_p3(IgemmTile t) { return cfg_of(t).traits & TF_PLANES; }
+bool igemm_tile_s2d(IgemmTile t) { return cfg_of(t).traits & TF_S2D; }
 // conv3h_kernel tiles can split K by the filter row (dh-split, split-K = 3 exactly); the three-deep-ring variant cannot
-bool igemm_tile_s2d(IgemmTile t) { return t >= 0 && t < TILE_AUTO && kTiles[t].s2d; }
-bool igemm_tile_dh_split(IgemmTile t) {
-    return t >= 0 && t < TILE_AUTO && kTiles[t].p3 && kTiles[t].h && !kTiles[t].g && !kTiles[t].s2d && t != TILE_P3HR_256x64 && t != TILE_P3HR_128x64 && t != TILE_P3HR_64x64_C2 && t != TILE_P3HR_128x128;
-}
+bool igemm_tile_dh_split(IgemmTile t) { return cfg_of(t).traits & TF_DH_SPLIT; }
+// kernels that take the group index of a grouped launch from their grid (common.h): igemm_kernel, igemm3_kernel, conv3h_kernel, conv3hr_kernel, conv3g_kernel
+bool igemm_tile_grouped(IgemmTile t) { return cfg_of(t).traits & TF_GROUPED; }
 bool igemm_p3_eligible(const IgemmDesc& d) { return dw3_ok(d) && d.w_split && d.dsh * d.dsw == 1 && d.Cin <= MAX_BN_C; }
-static int tile_bm(IgemmTile t) { return (t >= 0 && t < TILE_AUTO) ? kTiles[t].bm : 0; }
-static int tile_bn(IgemmTile t) { return (t >= 0 && t < TILE_AUTO) ? kTiles[t].bn : 0; }
-int igemm_tile_bm(IgemmTile t) { return tile_bm(t); }
-int igemm_tile_bn(IgemmTile t) { return tile_bn(t); }
-int igemm_tile_bk(IgemmTile t) { return (t >= 0 && t < TILE_AUTO) ? kTiles[t].bk : 0; }
-const char* igemm_tile_name(IgemmTile t) { return (t >= 0 && t < TILE_AUTO) ? kTiles[t].name : "igemm_kernel<?>"; }
+int igemm_tile_bm(IgemmTile t) { return cfg_of(t).sh.bm; }
+int igemm_tile_bn(IgemmTile t) { return cfg_of(t).sh.bn; }
+int igemm_tile_bk(IgemmTile t) { return cfg_of(t).sh.bk; }
+const char* igemm_tile_name(IgemmTile t) { return cfg_of(t).name; }
 
 static bool uniform_taps_for(const IgemmDesc& d, int bk) {
     return (d.ntaps > 1 ? (d.Cin % bk == 0) : true) && (d.K % bk == 0);
 }
-// kernels that take the group index of a grouped launch from their grid (common.h): igemm_kernel, igemm3_kernel, conv3h_kernel, conv3hr_kernel, conv3g_kernel
-bool igemm_tile_grouped(IgemmTile t) {
-    if (t < 0 || t >= TILE_AUTO) return false;
-    const TileCfg& k = kTiles[t];
-    if (k.s2 || (k.dw3 && !k.p3)) return false;                       // igemm3s2_kernel, igemm3dw_kernel
-    if (k.p3 && !k.h && !k.g) return false;                            // conv3p_kernel / conv3pp_kernel
-    return true;
-}
 bool igemm_tile_ok(const IgemmDesc& d, IgemmTile t) {
     if (t < 0 || t >= TILE_AUTO) return false;
     if (cur_group().G > 1 && !igemm_tile_grouped(t)) return false;
-    const int bk = kTiles[t].bk;
+    const TileShape& k = kTiles[t].sh;
+    const unsigned f = kTiles[t].traits;
+    const bool split = f & (TF_BF16X3 | TF_FP16X2), planes = f & TF_PLANES;
+    const int bk = k.bk;
     if (d.Kpad % bk) return false;
-    if (kTiles[t].split && !d.w_split) return false;
-    const bool mm_tile = t == TILE_P3GH_MM_64x128_K2 || t == TILE_P3GH_MM_64x128_K4 || t == TILE_P3GH_MM_128x128_K2 || t == TILE_P3GH_MM_128x256_K2;      // conv3g_kernel with the fused decoder tail as epilogue
-    if (mm_tile != (d.mm_out != nullptr && kTiles[t].g)) return false;
-    if (mm_tile && (d.Wg % kTiles[t].bm || (d.dsw * d.Cout) % kTiles[t].bn)) return false;          // a tile = one mask frame of one window
+    if (split && !d.w_split) return false;
+    const bool mm_tile = f & TF_FUSED_TAIL;      // conv3g_kernel with the fused decoder tail as epilogue
+    if (mm_tile != (d.mm_out != nullptr && (f & TF_GATHERED))) return false;
+    if (mm_tile && (d.Wg % k.bm || (d.dsw * d.Cout) % k.bn)) return false;          // a tile = one mask frame of one window
     if (d.mm_out != nullptr && !mm_tile) {  // fused decoder tail: igemm3_kernel tiles holding one mask frame of one window
-        const bool b3 = kTiles[t].split && !kTiles[t].dw3 && !kTiles[t].s2 && !kTiles[t].p3;
-        if (!b3 || kTiles[t].bm > 128 || kTiles[t].bn > 128 || d.Cout != 32 || d.dsh * d.dsw <= 1 || d.Wg % kTiles[t].bm ||
-            (d.dsw * d.Cout) % kTiles[t].bn || d.splitk != 1 || d.in_scale || d.bn_in.acc || !d.mm_coeffs)
+        const bool b3 = split && !(f & TF_SHARED_TAPS) && !(f & TF_STEM) && !planes;
+        if (!b3 || k.bm > 128 || k.bn > 128 || d.Cout != 32 || d.dsh * d.dsw <= 1 || d.Wg % k.bm ||
+            (d.dsw * d.Cout) % k.bn || d.splitk != 1 || d.in_scale || d.bn_in.acc || !d.mm_coeffs)
             return false;
     }
-    if (kTiles[t].dw3 && !dw3_ok(d)) return false;
-    if (kTiles[t].s2d) return d.splitk == 1 && d.mm_out == nullptr && conv3s_ok(d);           // (the training step and the other plane formats never provide the operand)
-    if (kTiles[t].p3 && (d.xp3 == nullptr || (d.splitk != 1 && !(d.splitk == 3 && igemm_tile_dh_split(t))))) return false;
-    if (kTiles[t].p3 && (kTiles[t].h ? (d.xp3_fmt != 1 || d.wh2 == nullptr) : d.xp3_fmt != 0)) return false;   // the planes' format decides the family
-    if (!kTiles[t].p3 && d.xp3 != nullptr && d.x == nullptr) return false;      // only the planes were provided
-    if (kTiles[t].g) return conv3g_ok(d);                                        // gathered operand tiles: any stride / tap set on the plane rows
-    if (kTiles[t].p3) return true;                                               // (the producer's BN+ReLU is already in the planes)
-    if (kTiles[t].s2 && !s2_ok(d)) return false;
+    if ((f & TF_SHARED_TAPS) && !dw3_ok(d)) return false;
+    if (f & TF_S2D) return d.splitk == 1 && d.mm_out == nullptr && conv3s_ok(d);           // (the training step and the other plane formats never provide the operand)
+    if (planes && (d.xp3 == nullptr || (d.splitk != 1 && !(d.splitk == 3 && (f & TF_DH_SPLIT))))) return false;
+    if (planes && ((f & TF_FP16X2) ? (d.xp3_fmt != 1 || d.wh2 == nullptr) : d.xp3_fmt != 0)) return false;   // the planes' format decides the family
+    if (!planes && d.xp3 != nullptr && d.x == nullptr) return false;      // only the planes were provided
+    if (f & TF_GATHERED) return conv3g_ok(d);                              // gathered operand tiles: any stride / tap set on the plane rows
+    if (planes) return true;                                               // (the producer's BN+ReLU is already in the planes)
+    if ((f & TF_STEM) && !s2_ok(d)) return false;
     if ((d.in_scale || d.bn_in.acc) && !uniform_taps_for(d, bk)) return false;
     return true;
 }
@@ -417,7 +379,7 @@ IgemmTile igemm_pick_tile(const IgemmDesc& d) {
     static const bool fp32_only = getenv("SAGEN_FP32_ONLY") != nullptr;
     if (d.xp3 == nullptr && d.x == nullptr && conv3s_ok(d)) return TILE_P3S_128x128;         // only the space-to-depth planes were provided
     if (d.mm_out != nullptr) return (d.xp3 != nullptr && d.xp3_fmt == 1 && d.wh2 != nullptr && conv3g_ok(d)) ? TILE_P3GH_MM_64x128_K2 : TILE_B3_64x128;
-    auto blocks = [&](IgemmTile t) { return (long)cdiv(d.M, tile_bm(t)) * cdiv(d.N, tile_bn(t)) * d.splitk; };
+    auto blocks = [&](IgemmTile t) { return (long)cdiv(d.M, igemm_tile_bm(t)) * cdiv(d.N, igemm_tile_bn(t)) * d.splitk; };
     const long want = 2 * 256;                 // >= 2 workgroups per CU
     if (d.w_split && !fp32_only) {             // the bf16x3 kernels are the faster family wherever their planes exist
         const bool pro = d.in_scale != nullptr || d.bn_in.acc != nullptr;
@@ -463,7 +425,16 @@ IgemmTile igemm_pick_tile(const IgemmDesc& d) {
 
 int igemm_grid_m(const IgemmDesc& d, IgemmTile tile) {
     if (tile == TILE_AUTO) tile = igemm_pick_tile(d);
-    return cdiv(d.M, tile_bm(tile));
+    return cdiv(d.M, igemm_tile_bm(tile));
+}
+
+int igemm_auto_splitk(const IgemmDesc& d, IgemmTile tile) {
+    const int bm = (tile == TILE_32x128) ? 32 : 64, bn = (tile == TILE_32x128) ? 128 : 64;
+    const long blocks = (long)cdiv(d.M, bm) * cdiv(d.N, bn);
+    const int nk = d.Kpad / 16;
+    if (blocks >= 384 || nk < 16) return 1;
+    int sk = (int)std::min<long>({(512 + blocks - 1) / blocks, (long)nk / 8, 64L});
+    return std::max(sk, 1);
 }
 
 int igemm_launch(const IgemmDesc& d_in, IgemmTile tile, hipStream_t s) {
@@ -503,36 +474,18 @@ int igemm_launch(const IgemmDesc& d_in, IgemmTile tile, hipStream_t s) {
     if (d.grp.G > 1 && !igemm_tile_grouped(tile)) return fail(SAGEN_ERR_UNSUPPORTED, "igemm: %s has no grouped launch", igemm_tile_name(tile));
     if (!igemm_tile_ok(d, tile)) return fail(SAGEN_ERR_UNSUPPORTED, "igemm: %s cannot run this problem (Kpad=%d Cin=%d)", igemm_tile_name(tile), d.Kpad, d.Cin);
     // wave-uniform tap per K tile: every K tile lies inside one tap (and there is no ragged K tail)
-    d.uniform_taps = uniform_taps_for(d, kTiles[tile].bk) ? 1 : 0;
+    d.uniform_taps = uniform_taps_for(d, kTiles[tile].sh.bk) ? 1 : 0;
     if (d.ntaps > MAX_TAPS) return fail(SAGEN_ERR_UNSUPPORTED, "igemm: %d taps (max %d)", d.ntaps, MAX_TAPS);
-    if (kTiles[tile].s2d) return conv3s_dispatch(d, tile, s);
-    if (kTiles[tile].g) return conv3g_dispatch(d, tile, s);
-    if (kTiles[tile].h) return conv3h_dispatch(d, tile, s);
-    if (kTiles[tile].p3) return conv3p_dispatch(d, tile, s);
-    if (kTiles[tile].s2) return igemm3s2_dispatch(d, tile, s);
-    if (kTiles[tile].split) return igemm3_dispatch(d, tile, s);
+    const unsigned f = kTiles[tile].traits;
+    if (f & TF_S2D) return conv3s_dispatch(d, tile, s);
+    if (f & TF_GATHERED) return conv3g_dispatch(d, tile, s);
+    if (f & TF_FP16X2) return conv3h_dispatch(d, tile, s);
+    if (f & TF_PLANES) return conv3p_dispatch(d, tile, s);
+    if (f & TF_STEM) return igemm3s2_dispatch(d, tile, s);
+    if (f & TF_BF16X3) return igemm3_dispatch(d, tile, s);
+#define SAGEN_TILE_HAS_F32 ,
     switch (tile) {
-        case TILE_128x128: return launch_cfg<128, 128, 64, 64, 3, 16>(d, s);
-        case TILE_128x64: return launch_cfg<128, 64, 64, 32, 3, 16>(d, s);
-        case TILE_256x64: return launch_cfg<256, 64, 64, 64, 3, 16>(d, s);
-        case TILE_64x64: return launch_cfg<64, 64, 32, 32, 3, 16>(d, s);
-        case TILE_128x32: return launch_cfg<128, 32, 32, 32, 2, 16>(d, s);
-        case TILE_32x128: return launch_cfg<32, 128, 32, 32, 2, 16>(d, s);
-        case TILE_128x128_S2: return launch_cfg<128, 128, 64, 64, 2, 16>(d, s);
-        case TILE_128x64_S2: return launch_cfg<128, 64, 64, 32, 2, 16>(d, s);
-        case TILE_256x64_S2: return launch_cfg<256, 64, 64, 64, 2, 16>(d, s);
-        case TILE_64x64_S2: return launch_cfg<64, 64, 32, 32, 2, 16>(d, s);
-        case TILE_64x128: return launch_cfg<64, 128, 32, 64, 3, 16>(d, s);
-        case TILE_64x128_S2: return launch_cfg<64, 128, 32, 64, 2, 16>(d, s);
-        case TILE_64x256: return launch_cfg<64, 256, 64, 64, 3, 16>(d, s);
-        case TILE_64x256_S2: return launch_cfg<64, 256, 64, 64, 2, 16>(d, s);
-        case TILE_256x32: return launch_cfg<256, 32, 64, 32, 2, 16>(d, s);
-        case TILE_64x64_K32: return launch_cfg<64, 64, 32, 32, 2, 32>(d, s);
-        case TILE_64x128_K32: return launch_cfg<64, 128, 32, 64, 2, 32>(d, s);
-        case TILE_128x64_K32: return launch_cfg<128, 64, 64, 32, 2, 32>(d, s);
-        case TILE_128x128_K32: return launch_cfg<128, 128, 64, 64, 2, 32>(d, s);
-        case TILE_32x128_K32: return launch_cfg<32, 128, 32, 32, 2, 32>(d, s);
-        case TILE_128x32_K32: return launch_cfg<128, 32, 32, 32, 2, 32>(d, s);
+        SAGEN_TILES(SAGEN_TILE_CASE)
         default: return fail(SAGEN_ERR_UNSUPPORTED, "igemm: bad tile id %d", (int)tile);
     }
 }

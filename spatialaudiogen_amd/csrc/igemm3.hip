@@ -360,20 +360,9 @@ static int launch_cfg3(const IgemmDesc& d, hipStream_t s) {
 
 // called by igemm_launch (igemm.hip) after the shared validation
 int igemm3_dispatch(const IgemmDesc& d, IgemmTile tile, hipStream_t s) {
+#define SAGEN_TILE_HAS_B3 ,
     switch (tile) {
-        case TILE_B3_128x128: return launch_cfg3<128, 128, 64, 64, 1>(d, s);
-        case TILE_B3_128x64: return launch_cfg3<128, 64, 64, 32, 1>(d, s);
-        case TILE_B3_256x64: return launch_cfg3<256, 64, 64, 64, 1>(d, s);
-        case TILE_B3_64x64: return launch_cfg3<64, 64, 32, 32, 1>(d, s);
-        case TILE_B3_64x128: return launch_cfg3<64, 128, 32, 64, 1>(d, s);
-        case TILE_B3_64x256: return launch_cfg3<64, 256, 64, 64, 1>(d, s);
-        case TILE_B3_32x128: return launch_cfg3<32, 128, 32, 32, 1>(d, s);
-        case TILE_B3_128x32: return launch_cfg3<128, 32, 32, 32, 1>(d, s);
-        case TILE_B3_128x64_K2: return launch_cfg3<128, 64, 64, 32, 2>(d, s);
-        case TILE_B3_64x64_K2: return launch_cfg3<64, 64, 32, 32, 2>(d, s);
-        case TILE_B3_64x128_K2: return launch_cfg3<64, 128, 32, 64, 2>(d, s);
-        case TILE_B3_32x128_K2: return launch_cfg3<32, 128, 32, 32, 2>(d, s);
-        case TILE_B3_128x32_K2: return launch_cfg3<128, 32, 32, 32, 2>(d, s);
+        SAGEN_TILES(SAGEN_TILE_CASE)
         default: return igemm3dw_dispatch(d, tile, s);
     }
 }

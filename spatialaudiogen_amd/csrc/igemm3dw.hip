@@ -389,17 +389,9 @@ static int launch_cfg3dw(const IgemmDesc& d, hipStream_t s) {
 }
 
 int igemm3dw_dispatch(const IgemmDesc& d, IgemmTile tile, hipStream_t s) {
+#define SAGEN_TILE_HAS_B3DW ,
     switch (tile) {
-        case TILE_B3DW_128x128: return launch_cfg3dw<128, 128, 64, 64, false>(d, s);
-        case TILE_B3DW_128x64: return launch_cfg3dw<128, 64, 64, 32, false>(d, s);
-        case TILE_B3DW_256x64: return launch_cfg3dw<256, 64, 64, 64, false>(d, s);
-        case TILE_B3DW_64x128: return launch_cfg3dw<64, 128, 32, 64, false>(d, s);
-        case TILE_B3DW_64x64: return launch_cfg3dw<64, 64, 32, 32, false>(d, s);
-        case TILE_B3DW_64x256: return launch_cfg3dw<64, 256, 64, 64, false>(d, s);
-        case TILE_B3DWM_128x64: return launch_cfg3dw<128, 64, 64, 32, true>(d, s);
-        case TILE_B3DWM_256x64: return launch_cfg3dw<256, 64, 64, 64, true>(d, s);
-        case TILE_B3DWM_64x64: return launch_cfg3dw<64, 64, 32, 32, true>(d, s);
-        case TILE_B3DWM_64x128: return launch_cfg3dw<64, 128, 32, 64, true>(d, s);
+        SAGEN_TILES(SAGEN_TILE_CASE)
         default: return fail(SAGEN_ERR_UNSUPPORTED, "igemm3dw: bad tile id %d", (int)tile);
     }
 }

@@ -250,9 +250,9 @@ static int launch_cfg3s2(const IgemmDesc& d, hipStream_t s) {
 }
 
 int igemm3s2_dispatch(const IgemmDesc& d, IgemmTile tile, hipStream_t s) {
+#define SAGEN_TILE_HAS_B3S2 ,
     switch (tile) {
-        case TILE_B3S2_256x64: return launch_cfg3s2<256, 64, 64, 64>(d, s);
-        case TILE_B3S2_128x64: return launch_cfg3s2<128, 64, 64, 32>(d, s);
+        SAGEN_TILES(SAGEN_TILE_CASE)
         default: return fail(SAGEN_ERR_UNSUPPORTED, "igemm3s2: bad tile id %d", (int)tile);
     }
 }

@@ -2,6 +2,7 @@
 #pragma once
 #include "common.h"
 #include "wave_reduce.h"
+#include "igemm_tiles.h"
 
 namespace sagen {
 
@@ -117,56 +118,20 @@ __device__ __forceinline__ void igemm_relocate(IgemmDesc& d, int g) {
 }
 // grid.z of an IgemmDesc launch: groups x split-K for igemm_kernel / igemm3_kernel (blockIdx.z = g * splitk + z), groups for the others
 
-// tile configurations (BM x BN, 4 waves)
-// The first six are the shape-heuristic set; the rest exist for the autotuner (2-stage LDS ring = less LDS,
-// more resident workgroups; extra aspect ratios).
-enum IgemmTile {
-    TILE_128x128 = 0, TILE_128x64, TILE_256x64, TILE_64x64, TILE_128x32, TILE_32x128,
-    TILE_128x128_S2, TILE_128x64_S2, TILE_256x64_S2, TILE_64x64_S2,
-    TILE_64x128, TILE_64x128_S2, TILE_64x256, TILE_64x256_S2, TILE_256x32,
-    // K tile of 32 (half the barriers per MFMA; needs Kpad % 32 == 0)
-    TILE_64x64_K32, TILE_64x128_K32, TILE_128x64_K32, TILE_128x128_K32, TILE_32x128_K32, TILE_128x32_K32,
-    // fp32-equivalent bf16x3 operand split on the bf16 matrix cores (needs IgemmDesc::w_split)
-    TILE_B3_128x128, TILE_B3_128x64, TILE_B3_256x64, TILE_B3_64x64, TILE_B3_64x128, TILE_B3_64x256, TILE_B3_32x128,
-    TILE_B3_128x32,
-    // ... with two K tiles of 16 per barrier step
-    TILE_B3_128x64_K2, TILE_B3_64x64_K2, TILE_B3_64x128_K2, TILE_B3_32x128_K2, TILE_B3_128x32_K2,
-    // bf16x3 for dense 3x3 stride-1 SAME convs: the three horizontal taps share one activation tile (igemm3dw_kernel)
-    TILE_B3DW_128x128, TILE_B3DW_128x64, TILE_B3DW_256x64, TILE_B3DW_64x128, TILE_B3DW_64x64, TILE_B3DW_64x256,
-    // ... the three taps also share one barrier step (narrow N)
-    TILE_B3DWM_128x64, TILE_B3DWM_256x64, TILE_B3DWM_64x64, TILE_B3DWM_64x128,
-    // bf16x3 for the 7x7 stride-2 stem over the padded 4-channel image, K ordered (dh, dw padded to 8, c) (igemm3s2_kernel)
-    TILE_B3S2_256x64, TILE_B3S2_128x64,
-    // bf16x3 for dense 3x3 stride-1 SAME convs over pre-split activation planes (conv3p_kernel; needs IgemmDesc::xp3)
-    TILE_P3_128x64, TILE_P3_128x128, TILE_P3_64x64,
-    // ... two phase-locked 4-wave teams per workgroup (conv3pp_kernel): two 128x64 tiles / the two K halves of one
-    TILE_P3PP_PAIR, TILE_P3PP_SPLITK,
-    // bf16x3 for ANY strided / multi-tap conv over pre-split activation planes, operand tiles gathered by LDS-DMA (conv3g_kernel)
-    TILE_P3G_128x64_K2, TILE_P3G_64x64_K2, TILE_P3G_64x128_K2, TILE_P3G_128x128_K1,
-    // fp16x2 for dense 3x3 stride-1 SAME convs over TWO fp16 planes per operand: three products per multiply (conv3h_kernel)
-    TILE_P3H_128x64, TILE_P3H_128x128, TILE_P3H_64x64, TILE_P3H_256x64,
-    // ... and for any strided / multi-tap conv over them (conv3g_kernel, gathered operand tiles)
-    TILE_P3GH_128x64_K3, TILE_P3GH_64x64_K4, TILE_P3GH_128x128_K2, TILE_P3GH_64x128_K3,
-    // conv3h_kernel with two / four 16-channel chunks per barrier step (the deep, latency-bound layers)
-    TILE_P3H_128x64_C2, TILE_P3H_64x64_C2, TILE_P3H_64x64_C4,
-    // conv3g_kernel on fp16x2 planes with the fused decoder tail as its epilogue (deconv1 at inference: IgemmDesc::mm_out), 2 / 4 K tiles per group
-    TILE_P3GH_MM_64x128_K2, TILE_P3GH_MM_64x128_K4, TILE_P3GH_MM_128x128_K2, TILE_P3GH_MM_128x256_K2,
-    // conv3hr_kernel: conv3h_kernel with a three-deep ring of activation images beside the two filter stages (conv3h.hip)
-    TILE_P3HR_256x64, TILE_P3HR_128x64, TILE_P3HR_64x64_C2,
-    TILE_P3HR_128x128,         // (round 6: the 128x128 tile with the three-deep activation ring - 72 KB of LDS, two workgroups per CU)
-    // the space-to-depth conv3h_kernel: the 3x3 stride-2 SAME conv over space-to-depth fp16x2 planes (IgemmDesc::xs2d), conv3h_kernel's K loop; R = three-deep activation ring
-    TILE_P3S_128x128, TILE_P3SR_128x64, TILE_P3SR_256x64,
-    TILE_AUTO
-};
+// tile configurations (BM x BN, 4 waves): one enumerator per row of the registry (igemm_tiles.h), in its order
+#define SAGEN_TILE_ENUM(id, ...) TILE_##id,
+enum IgemmTile { SAGEN_TILES(SAGEN_TILE_ENUM) TILE_AUTO };
 
 int igemm_launch(const IgemmDesc& d, IgemmTile tile, hipStream_t s);
 int igemm_grid_m(const IgemmDesc& d, IgemmTile tile);       // number of M tiles (stats rows)
 IgemmTile igemm_pick_tile(const IgemmDesc& d);
-const char* igemm_tile_name(IgemmTile t);
+const char* igemm_tile_name(IgemmTile t);              // instantiation name as rocprofv3 prints it
+unsigned igemm_tile_traits(IgemmTile t);               // the TileTrait bits of the tile's family (igemm_tiles.h); 0 for an id outside the table
 int igemm_tile_bm(IgemmTile t);
 int igemm_tile_bn(IgemmTile t);
 int igemm_tile_bk(IgemmTile t);
-bool igemm_tile_split(IgemmTile t);                   // bf16x3 variant (igemm3.hip)?
+bool igemm_tile_split(IgemmTile t);                   // bf16x3 / fp16x2 operands (needs IgemmDesc::w_split)?
+int igemm_auto_splitk(const IgemmDesc& d, IgemmTile tile);   // split-K factor for low-parallelism contractions (>= ~2 workgroups per CU, >= 8 K tiles per split)
 int igemm3_dispatch(const IgemmDesc& d, IgemmTile tile, hipStream_t s);   // launch only; igemm_launch validates
 int igemm3dw_dispatch(const IgemmDesc& d, IgemmTile tile, hipStream_t s); // (igemm3dw.hip)
 int igemm3s2_dispatch(const IgemmDesc& d, IgemmTile tile, hipStream_t s); // (igemm3s2.hip)
@@ -186,13 +151,12 @@ struct H2Job {                       // one layer of the batched fp16x2 filter p
 int h2_filter_pack_multi_launch(const H2Job* jobs_dev, int njobs, int nblocks, unsigned* amax, hipStream_t s);
 bool conv3g_ok(const IgemmDesc& d);                   // geometry conv3g_kernel can run (given planes)
 constexpr int SK_TICKETS = 8192;                      // tiles an in-launch split-K combine can track (IgemmDesc::sk_ticket)
-inline bool igemm_tile_fused_splitk(IgemmTile) { return true; }     // every kernel that writes split-K partials does it through igemm_epilogue
-bool igemm_tile_p3(IgemmTile t);                      // conv3p_kernel tile (pre-split activation planes, no split-K)?
+bool igemm_tile_p3(IgemmTile t);                      // plane-fed tile (pre-split activation planes, no split-K)?
 bool igemm_tile_grouped(IgemmTile t);                 // does the tile's kernel support the grouped launch (common.h: GroupInfo)?
 bool igemm_tile_s2d(IgemmTile t);                     // the space-to-depth conv3h_kernel tile (contracts IgemmDesc::xs2d)?
 bool igemm_tile_dh_split(IgemmTile t);                // ... except conv3h_kernel's dh-split: split-K = 3 exactly, one filter row per workgroup
 bool igemm_p3_eligible(const IgemmDesc& d);           // dense 3x3 stride-1 SAME conv that conv3p_kernel can run (given planes)
-bool igemm_tile_ok(const IgemmDesc& d, IgemmTile t);   // can this instantiation run the problem?              // instantiation name as rocprofv3 prints it
+bool igemm_tile_ok(const IgemmDesc& d, IgemmTile t);   // can this instantiation run the problem?
 // out[(m*rep + r)*ldy + n] = act(sum_z ws[z][m][n] + bias[n]),  r in [0,rep); with `stats` also the
 // per-channel (sum, sumsq) of the raw sums, accumulated into stats[2][N] (fp64 atomics)
 constexpr int SPLITK_RB = 16;
@@ -214,7 +178,7 @@ struct DeconvGather {
 };
 int deconv_gather_launch(const float* ws, int splitk, const DeconvGather& g, hipStream_t s);
 
-// filter repacking (pack.hip).  All produce [Npad][Kpad] with zero padding.
+// filter repacking (igemm.hip).  All produce [Npad][Kpad] with zero padding.
 // conv  : Wp[n][(tap, c)] = W_hwio[tap][c][n],  c < cin_src (cin_pad >= cin_src).  With tw_pad > tw_src > 0 the packed
 //         taps are rows of tw_pad (tap = th*tw_pad + tw) over a source of tw_src taps per row; tw >= tw_src packs zeros.
 int pack_conv_launch(const float* w_hwio, int ntaps, int cin_src, int cin_pad, int cout,

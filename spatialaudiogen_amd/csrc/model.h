@@ -240,16 +240,6 @@ static inline bool conv3g_ok_desc(const IgemmDesc& d, int cin) {
 
 static inline size_t packed_floats(long N, long K) { return (size_t)N * ((K + 15) / 16 * 16); }
 
-// choose a split-K factor for low-parallelism contractions (>= ~2 workgroups per CU, >= 8 K tiles per split)
-static inline int auto_splitk(const IgemmDesc& d, IgemmTile tile) {
-    const int bm = (tile == TILE_32x128) ? 32 : 64, bn = (tile == TILE_32x128) ? 128 : 64;
-    const long blocks = (long)cdiv(d.M, bm) * cdiv(d.N, bn);
-    const int nk = d.Kpad / 16;
-    if (blocks >= 384 || nk < 16) return 1;
-    int sk = (int)std::min<long>({(512 + blocks - 1) / blocks, (long)nk / 8, 64L});
-    return std::max(sk, 1);
-}
-
 }  // namespace sagen
 
 
@@ -332,7 +322,7 @@ struct Fwd {
             // the partials are combined by the contraction itself (last-arriver, igemm_epilogue) unless statistics ride on the reducer
             const long tiles = (long)cdiv(d.M, igemm_tile_bm(tile)) * cdiv(d.N, igemm_tile_bn(tile));
             if (c->sk_fused && sk > 1 && !d.stats && !d.amax_out && d.N % 4 == 0 && d.ldy % 4 == 0 && ((uintptr_t)d.y % 16) == 0 && (!d.bias || ((uintptr_t)d.bias % 16) == 0) &&
-                tiles <= SK_TICKETS && igemm_tile_fused_splitk(tile) && c->bufs.count(wsname + ":tk")) {
+                tiles <= SK_TICKETS && c->bufs.count(wsname + ":tk")) {
                 e.sk_ticket = reinterpret_cast<int*>(c->ws + c->bufs.at(wsname + ":tk").off);
                 e.sk_rep = rep;
                 e.stats = nullptr;
@@ -354,7 +344,7 @@ struct Fwd {
         const IgemmTile tile = igemm_pick_tile(d);
         ch.tile = (int)tile;
         const bool can_split = allow_split && dense_out(d) && !d.stats && !igemm_tile_p3(tile);     // (the plane-fed kernels do not split K)
-        ch.splitk = can_split ? auto_splitk(d, tile) : 1;
+        ch.splitk = can_split ? igemm_auto_splitk(d, tile) : 1;
         while (ch.splitk > 1 && (size_t)ch.splitk * d.M * d.N > ws_capacity()) --ch.splitk;
         return ch;
     }
@@ -399,13 +389,13 @@ struct Fwd {
             // forward gets slower (1 560 vs 1 610-1 637 ambisonic-s/s) - a candidate only for the training step, which has one batch in
             // flight (7.27 -> 7.23 ms per step on one box), or when asked for (SAGEN_P3PP=1)
             static const bool p3pp = getenv("SAGEN_P3PP") != nullptr;
-            if (!p3pp && !c->train_mode && (tile == TILE_P3PP_PAIR || tile == TILE_P3PP_SPLITK)) continue;
+            if (!p3pp && !c->train_mode && (igemm_tile_traits(tile) & TF_TWO_TEAM)) continue;
             // conv3hr_kernel (three-deep activation ring) measured equal to conv3h_kernel on every layer: left out of
             // the tuner so that equal candidates do not split a layer family over two kernel names from run to run (SAGEN_P3HR=1 adds it)
             static const bool p3hr = getenv("SAGEN_P3HR") != nullptr;
             // (round 6: with ten batches per launch the wait for the activation images is no longer hidden - tools/trace_conv3h.py: 500 - 1 400 of a
             //  2 000 - 3 000-cycle group - and the deeper ring measures 0 - 2 % ahead on the headline, same box: a candidate of grouped contexts)
-            if (!p3hr && c->G == 1 && (tile == TILE_P3HR_256x64 || tile == TILE_P3HR_128x64 || tile == TILE_P3HR_64x64_C2 || tile == TILE_P3HR_128x128)) continue;
+            if (!p3hr && c->G == 1 && (igemm_tile_traits(tile) & TF_RING3)) continue;
             const int nk = d.Kpad / igemm_tile_bk(tile);
             if (bn > 32 && bn >= 2 * d.N) continue;                     // mostly-empty N tile
             if (bm > 32 && bm >= 4 * d.M) continue;

@@ -106,3 +106,9 @@ def test_tile_table_is_exposed_and_consistent():
     assert names == SptAudioGen.tile_names()
     fams = {nm.split('<')[0] for nm in names}
     assert fams == {'igemm_kernel', 'igemm3_kernel', 'igemm3dw_kernel', 'igemm3s2_kernel', 'conv3p_kernel', 'conv3pp_kernel', 'conv3g_kernel', 'conv3h_kernel', 'conv3hr_kernel'}
+    # the table is frozen: plan files, SAGEN_FORCE_TILE and the forced-tile tests index it, the profile rows and the benchmark's
+    # per-family accounting read its names (tests/golden/tile_names_v1.txt: one name per line, in index order)
+    golden = open(os.path.join(ROOT, 'tests', 'golden', 'tile_names_v1.txt')).read().split('\n')
+    assert names == golden
+    import test_gpu_model
+    assert test_gpu_model.ALL_TILES_FALLBACK == n

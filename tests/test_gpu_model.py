@@ -228,13 +228,17 @@ def test_autotuned_plan_keeps_parity(T):
     check_out(net.inference_ops(inp['audio'], inp['video']).cpu().numpy(), ref)
 
 
+# the size of the tile table, for collection on a fresh checkout (tests/test_abi.py holds it equal to sagen_num_tiles())
+ALL_TILES_FALLBACK = 77
+
+
 def _all_tiles():
     """Every contraction-kernel instantiation of the library (host-only ABI calls) with a rotating split-K factor."""
     try:
         from spatialaudiogen_amd import _lib
         n = _lib.lib().sagen_num_tiles()
-    except Exception:          # library not built yet (collection on a fresh checkout): the table size at the time of writing
-        n = 46
+    except Exception:          # library not built yet (collection on a fresh checkout)
+        n = ALL_TILES_FALLBACK
     sks = [1, 2, 1, 3, 1, 4, 1]
     return [(t, sks[t % len(sks)]) for t in range(n)] + [(0, 2), (21, 2), (34, 2), (40, 1)]
 
