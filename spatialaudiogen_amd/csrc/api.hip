@@ -254,10 +254,7 @@ int sagen_conv2d(const float* x, int batch, int h, int w, int cin, const float* 
             // dense 3x3 stride-1 SAME: one elementwise pass applies the input BN+ReLU (if any) and writes the three bf16
             // planes; the contraction then runs LDS-DMA -> MFMA only (conv3p.hip)
             IgemmDesc e = d;
-            e.xp3 = (char*)scratch + pk_bytes(cout, (long)kh * kw * cin);
-            e.p3_np = batch * h * (w + 1);
-            e.xp3_cstride = (unsigned)((size_t)e.p3_np * 96);
-            e.xp3_bytes = (unsigned)p3_bytes(batch, h, w, cin);
+            igemm_set_p3_planes(e, (char*)scratch + pk_bytes(cout, (long)kh * kw * cin), batch, h, w, cin);
             const IgemmTile t = igemm_pick_tile(e);
             if (igemm_tile_p3(t)) {
                 rc = p3_pack_launch(x, in_scale, in_shift, BnRef(), nullptr, in_scale ? 1 : 0, nullptr, (void*)e.xp3, batch, h, w, cin, s);

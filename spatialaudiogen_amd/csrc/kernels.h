@@ -118,6 +118,33 @@ __device__ __forceinline__ void igemm_relocate(IgemmDesc& d, int g) {
 }
 // grid.z of an IgemmDesc launch: groups x split-K for igemm_kernel / igemm3_kernel (blockIdx.z = g * splitk + z), groups for the others
 
+// How a contraction takes its operand from pre-split planes (p3.hip): the ONE place these fields are written.  Null planes leave a zero
+// extent.  The extents equal p3_bytes / p3h_bytes / p3s_bytes of the same tensor: channel chunks x pixels (one zero pixel closes a row) x 96 | 64 B.
+// three bf16 planes [C/16][B*H*(W+1)][3][16]
+inline void igemm_set_p3_planes(IgemmDesc& d, const void* planes, int B, int H, int W, int C) {
+    d.xp3 = planes;
+    d.p3_np = planes ? B * H * (W + 1) : 0;
+    d.xp3_cstride = (unsigned)((size_t)d.p3_np * 96);
+    d.xp3_bytes = (unsigned)((size_t)d.xp3_cstride * (C / 16));
+}
+// two fp16 planes [C/16][B*rows*(W+1)][2][16] of v / a_inv - all `rows` image rows, or the band [row0, row0 + band) of a taller image
+// (conv3g_kernel) - against the layer's fp16x2 filter `wh2` [Kpad/16][2][N][16] of w / w_inv (d.N and d.Kpad are set)
+inline void igemm_set_h2_planes(IgemmDesc& d, const void* planes, int B, int rows, int W, int C, const void* wh2, const float* a_inv,
+                                const float* w_inv, int row0 = 0, int band = 0) {
+    d.xp3 = planes; d.xp3_fmt = 1; d.xp3_row0 = row0; d.xp3_rows = band;
+    d.p3_np = planes ? B * rows * (W + 1) : 0;
+    d.xp3_cstride = (unsigned)((size_t)d.p3_np * 64);
+    d.xp3_bytes = (unsigned)((size_t)d.xp3_cstride * (C / 16));
+    d.wh2 = wh2; d.wh2_bytes = (unsigned)((size_t)d.N * d.Kpad * 4);
+    d.h2_a_inv = a_inv; d.h2_w_inv = w_inv;
+}
+// the fp16x2 planes of an even H x W tensor in space-to-depth form (conv3s.hip: four phase images back to back), beside the row planes or alone
+inline void igemm_set_s2d_planes(IgemmDesc& d, const void* planes, int B, int H, int W, int C) {
+    d.xs2d = planes;
+    d.xs2d_np = B * (H / 2) * (W / 2 + 1);
+    d.xs2d_bytes = (unsigned)((size_t)4 * d.xs2d_np * 64 * (C / 16));
+}
+
 // tile configurations (BM x BN, 4 waves): one enumerator per row of the registry (igemm_tiles.h), in its order
 #define SAGEN_TILE_ENUM(id, ...) TILE_##id,
 enum IgemmTile { SAGEN_TILES(SAGEN_TILE_ENUM) TILE_AUTO };
@@ -262,6 +289,7 @@ size_t p3_bytes(int B, int H, int W, int C);
 // fmt 0: three bf16 planes (conv3p / conv3g); fmt 1: two fp16 planes of v * 2^ka (conv3h.hip) - ka from the statistics in `h2`
 // h2s (256 floats) layout: [0], [1] trunk plane 2^-ka; [2..5] tracked block-input bounds; [6] scratch; [7] saturation counter;
 // [H2S_FILTER_FIRST .. H2S_FIXED_FIRST) 2^-kw per fp16x2 filter; then the hard-wired a_inv slots; [2 + H2_RIG_OFF ..] rigorous bounds
+constexpr int H2S_SAT_COUNT = 7;
 constexpr int H2S_FILTER_FIRST = 8;
 constexpr int H2S_FIXED_FIRST = 232;    // first slot that is NOT a filter scale: filter slots must stay below (model.hip checks)
 constexpr int H2S_A_INV_X = 232;        // [232..235] lean trunk: 2^-ka of the block-input planes, two alternating slots x (video, flow)

@@ -39,6 +39,49 @@ static const int AENC_F[5] = {32, 64, 128, 256, 512};
 static const int AENC_K[5][2] = {{7, 16}, {3, 7}, {3, 5}, {3, 5}, {3, 5}};
 static const int AENC_S[5][2] = {{4, 8}, {2, 4}, {2, 2}, {1, 1}, {1, 1}};
 
+static inline bool is_weights(const std::string& n) { return n.size() >= 8 && n.compare(n.size() - 8, 8, "/weights") == 0; }
+
+// How the forward packs a "/weights" variable: the ONE description the workspace carving and both job tables (model.hip) are built from
+struct PkSpec {
+    int kind = PACK_CONV;            // of the "pk:" pack [N][Kpad] (+ its bf16x3 planes), with PackJob::p
+    int N = 0, K = 0, Kpad = 0;
+    int p[7] = {0, 0, 0, 0, 0, 0, 0};
+    bool stem = false;               // a trunk's 7x7/2 conv: tap rows padded 7 -> 8, channels 3 -> 4 (igemm3s2.hip)
+    int dec_l = -1, sh = 1, sw = 1;  // "/deconv": decoder layer index and strides - packed as a depth-to-space conv, N = (ry, rx, o), K = (dp, dq, c)
+    int Ns = 0, Ks = 0;              // deconv5 .. deconv2 also in scatter form [(p, q, o)][c] ("pks:", and "pkhs:" as fp16x2 planes); Ns = 0: none
+    bool h2 = false;                 // "pkh:": the pack also as two fp16 planes of w * 2^kw, the same [N][Kpad] (K % 16 == 0 for all of them)
+};
+static inline PkSpec pk_spec(const VarSpec& vs) {
+    PkSpec k;
+    const int64_t* sp = vs.shape;
+    const size_t dec = vs.name.find("/deconv");
+    if (dec != std::string::npos) {                        // [kh, kw, Cout, Cin]
+        k.kind = PACK_DECONV;
+        k.dec_l = vs.name[dec + 7] - '1'; k.sh = AENC_S[k.dec_l][0]; k.sw = AENC_S[k.dec_l][1];
+        const int ntw = cdiv((int)sp[1], k.sw);
+        k.N = k.sh * k.sw * (int)sp[2]; k.K = cdiv((int)sp[0], k.sh) * ntw * (int)sp[3];
+        for (int i = 0; i < 4; ++i) k.p[i] = (int)sp[i];
+        k.p[4] = k.sh; k.p[5] = k.sw; k.p[6] = ntw;
+        if (k.dec_l >= 1 && sp[3] % 16 == 0) { k.Ns = (int)(sp[0] * sp[1] * sp[2]); k.Ks = (int)sp[3]; }
+        k.h2 = k.dec_l == 0;                               // deconv1 on planes of cat1 (conv3g_kernel with the fused decoder tail)
+    } else if (vs.ndim == 4) {                             // HWIO
+        int cin = (int)sp[2], cinp = cin, taps = (int)(sp[0] * sp[1]);
+        k.stem = cin == 3;
+        if (k.stem) { cinp = 4; taps = (int)(sp[0] * (sp[1] + 1)); k.p[4] = (int)sp[1]; k.p[5] = (int)sp[1] + 1; }
+        if (cin == 1) { cin = cinp = (int)sp[1]; taps = (int)sp[0]; }       // audio conv1 at order 1: kw acts as channels
+        k.N = (int)sp[3]; k.K = taps * cinp;
+        k.p[0] = taps; k.p[1] = cin; k.p[2] = cinp; k.p[3] = k.N;
+        // the trunks' 3x3 convs and 1x1 projections (conv3h.hip), their stems (stem8.hip) and conv2 .. conv5 of the audio encoder (conv3g_kernel)
+        const bool trunk = vs.name.find("_encoder/conv") != std::string::npos && ((sp[0] == 3 && sp[1] == 3) || (sp[0] == 1 && sp[1] == 1));
+        k.h2 = k.stem || (sp[2] % 16 == 0 && (trunk || vs.name.compare(0, 18, "audio_encoder/conv") == 0));
+    } else {                                               // fully connected [K][N]
+        k.N = (int)sp[1]; k.K = (int)sp[0];
+        k.p[0] = 1; k.p[1] = k.K; k.p[2] = k.K; k.p[3] = k.N;
+    }
+    k.Kpad = (k.K + 15) / 16 * 16;
+    return k;
+}
+
 }  // namespace sagen
 
 using namespace sagen;
@@ -97,6 +140,10 @@ struct sagen_ctx {
     int tune_groups = 0;                   // groups a tuning pass launches per candidate (SAGEN_TUNE_GROUPS; 0 = all, the default: same box, 15 per call: tuned on all 3 153 - 3 160 ambisonic-s/s in a 14 s process, on 4 groups 3 122 - 3 136 in 10 s, on 2 3 063 - 3 073)
     int inter_group = 0;                   // sagen_set_option("intermediate_group"): the group sagen_get_intermediate reads
     size_t grp_off = 0, grp_floats = 0;
+    // did an option move the path off the kernels that take a group dimension?  (the forward adds what it alone knows: the stems, the decoder)
+    static bool off_grouped(const sagen_ctx* c) {
+        return c->use_fcm || c->sk_fused || c->fp32_only || !c->use_h2 || !c->use_p3 || !c->use_p3g || c->p3_from_stage > 2 || c->no_lean_trunk;
+    }
     GroupInfo group_info() const {
         GroupInfo gi;
         if (G > 1 && ws) {
@@ -562,13 +609,9 @@ struct Fwd {
             void* planes = c->p("catp");
             timed("h2_pack_rows_kernel", 0.0, [&] {
                 return h2_pack_rows_launch(x, (long)Hin * Win * Cin, (long)Win * Cin, Cin, in_row0, c->B, R, Win, Cin, cat_amax(lx, 0), cat_amax(lx, 1), planes,
-                                           cat_a_inv(lx), reinterpret_cast<unsigned*>(c->p("h2s") + 7), s); });
-            d.xp3 = planes; d.xp3_fmt = 1; d.xp3_row0 = 0; d.xp3_rows = R;
-            d.p3_np = c->B * R * (Win + 1);
-            d.xp3_cstride = (unsigned)((size_t)d.p3_np * 64);
-            d.xp3_bytes = (unsigned)((size_t)d.xp3_cstride * (Cin / 16));
-            d.wh2 = c->p("pkhs:" + name + "/weights"); d.wh2_bytes = (unsigned)((size_t)d.N * d.Kpad * 4);
-            d.h2_a_inv = cat_a_inv(lx); d.h2_w_inv = c->p("h2s") + c->h2_slot.at("pks:" + name);
+                                           cat_a_inv(lx), h2_sat_count(), s); });
+            const H2Filter w = h2_filter(name, true);
+            igemm_set_h2_planes(d, planes, c->B, R, Win, Cin, w.w2, cat_a_inv(lx), w.w_inv, 0, R);
         }
         custom_reduce_name = "deconv_gather_kernel";
         custom_reduce = [gd](const float* ws, int sk, hipStream_t st) { return deconv_gather_launch(ws, sk, gd, st); };
@@ -579,6 +622,13 @@ struct Fwd {
     // fp16x2 planes (conv3h.hip) for this forward?  (the training step's forward too, unless SAGEN_TRAIN_NO_H2=1: its backward reads the
     // retained fp32 activations, not the planes)
     bool h2() const { return c->use_h2 && c->use_p3 && !c->fp32_only && (!c->train_mode || c->train_h2); }
+    // a layer's fp16x2 filter planes ("pkh:"; scatter: "pkhs:", the scatter form of a transposed conv) and where the pack wrote their 2^-kw
+    struct H2Filter { const void* w2; const float* w_inv; };
+    bool has_h2_filter(const std::string& name) const { return c->h2_slot.count(name) != 0; }
+    H2Filter h2_filter(const std::string& name, bool scatter = false) const {
+        return {c->p((scatter ? "pkhs:" : "pkh:") + name + "/weights"), c->p("h2s") + c->h2_slot.at((scatter ? "pks:" : "") + name)};
+    }
+    unsigned* h2_sat_count() const { return reinterpret_cast<unsigned*>(c->p("h2s") + H2S_SAT_COUNT); }
     int p3_fmt() const { return h2() ? 1 : 0; }
     float* h2_a_inv() { return c->p("h2s") + (sfx.empty() ? 0 : 1); }        // 2^-ka of the planes currently in this trunk's plane buffer
     // lean trunk (round 5, resnet()): the block input / output planes live in buffer "p3" with two alternating scale slots (a merge reads
@@ -591,7 +641,7 @@ struct Fwd {
     P3hScale h2_scale(float* bound_out = nullptr, const float* res_bound = nullptr, const double* res_acc = nullptr, double res_inv_count = 0.0) {
         P3hScale h;
         h.a_inv = h2_a_inv(); h.bound_out = bound_out; h.res_bound = res_bound; h.res_acc = res_acc; h.res_inv_count = res_inv_count;
-        h.sat_count = reinterpret_cast<unsigned*>(c->p("h2s") + 7);
+        h.sat_count = h2_sat_count();
         return h;
     }
 
@@ -616,31 +666,37 @@ struct Fwd {
         IgemmDesc d = conv_desc(x, Hin, Win, Cin, Cin, c->p("pk:" + name + "/weights"), k, k, stride, stride, true, Cout, y,
                                 Cout, Hout, Wout);
         if (planes || s2d_planes) {         // the input as pre-split planes (p3.hip); x may be null then
-            d.xp3 = planes;
-            d.p3_np = planes ? c->B * Hin * (Win + 1) : 0;
-            auto hs = c->h2_slot.find(name);
-            if (h2() && (stride == 1 || c->use_p3g) && k == 3 && hs != c->h2_slot.end()) {       // two fp16 planes + the layer's fp16 filter planes
-                d.xp3_fmt = 1;
-                d.xp3_cstride = (unsigned)((size_t)d.p3_np * 64);
-                d.xp3_bytes = planes ? (unsigned)p3h_bytes(c->B, Hin, Win, Cin) : 0u;
-                d.wh2 = c->p("pkh:" + name + "/weights");
-                d.wh2_bytes = (unsigned)((size_t)d.N * d.Kpad * 4);
-                d.h2_a_inv = planes_a_inv ? planes_a_inv : h2_a_inv();
-                d.h2_w_inv = c->p("h2s") + hs->second;
-                if (s2d_planes) {           // ... in space-to-depth form (conv3s.hip): beside the row-padded planes while tuning, alone otherwise
-                    d.xs2d = s2d_planes;
-                    d.xs2d_np = c->B * (Hin / 2) * (Win / 2 + 1);
-                    d.xs2d_bytes = (unsigned)p3s_bytes(c->B, Hin, Win, Cin);
-                }
+            if (h2() && (stride == 1 || c->use_p3g) && k == 3 && has_h2_filter(name)) {       // two fp16 planes + the layer's fp16 filter planes
+                const H2Filter w = h2_filter(name);
+                igemm_set_h2_planes(d, planes, c->B, Hin, Win, Cin, w.w2, planes_a_inv ? planes_a_inv : h2_a_inv(), w.w_inv);
+                // ... in space-to-depth form (conv3s.hip): beside the row-padded planes while tuning, alone otherwise
+                if (s2d_planes) igemm_set_s2d_planes(d, s2d_planes, c->B, Hin, Win, Cin);
             } else {
-                d.xp3_cstride = (unsigned)((size_t)d.p3_np * 96);
-                d.xp3_bytes = (unsigned)p3_bytes(c->B, Hin, Win, Cin);
+                igemm_set_p3_planes(d, planes, c->B, Hin, Win, Cin);
             }
         }
         d.bn_in = bn_in;
         d.stats = bn_acc(bn_index);
         layer = plan_key.empty() ? name : plan_key;
         contract(d);
+    }
+
+    // the 1x1/2 projection of the first block `pfx` of stage st + 2 (no bias, no BN: resnet.py:211-212) -> "rsc".  `planes`: the block
+    // input as row planes (null: none) - fp16x2 under the scale `planes_a_inv`, bf16x3 without one; x_fp32: does the fp32 input exist?
+    // stats: leave (sum, sumsq) of the projection - the residual's magnitude for the merge's fp16 scale
+    void projection(const std::string& pfx, int st, const float* x, bool x_fp32, int H, int W, int cin, int cout, const void* planes,
+                    const float* planes_a_inv, bool stats, int& Ho, int& Wo) {
+        IgemmDesc d = conv_desc(x_fp32 ? x : nullptr, H, W, cin, cin, c->p("pk:" + pfx + "/shortcut/weights"), 1, 1, 2, 2, true, cout,
+                                c->p("rsc" + sfx), cout, Ho, Wo);
+        if (planes && planes_a_inv) {
+            const H2Filter w = h2_filter(pfx + "/shortcut");
+            igemm_set_h2_planes(d, planes, c->B, H, W, cin, w.w2, planes_a_inv, w.w_inv);
+        } else if (planes) {
+            igemm_set_p3_planes(d, planes, c->B, H, W, cin);
+        }
+        if (stats) d.stats = bn_acc(20 + st);
+        layer = pfx + "/shortcut";
+        gemm(d, 1, false);
     }
 
     // ResNet18 -> conv5_2 in training-mode BN (resnet.py:123-236); returns the [B,7,14,512] output
@@ -652,10 +708,10 @@ struct Fwd {
         const bool tune_general = c->tuning && c->G == 1;
         const bool fast8 = c->video_u8 && scope == "video_encoder" && c->stem8 && !tune_general && !c->fp32_only && !c->train_mode;
         // ... with the filter as two fp16 planes where they exist: two products per multiply instead of three (stem8.hip, MODE 2)
-        const bool fast8h = fast8 && c->stem8h && h2() && c->h2_slot.count(scope + "/conv1/conv") != 0;
+        const bool fast8h = fast8 && c->stem8h && h2() && has_h2_filter(scope + "/conv1/conv");
         // float frames (the flow encoder; video handed over as float32): the same kernel on two fp16 planes of the frame (stem8.hip, F16)
         const bool fast16 = !fast8 && !(c->video_u8 && scope == "video_encoder") && c->stem16 && !tune_general && !c->fp32_only && !c->train_mode && h2() &&
-                            c->use_p3 && c->p3_from_stage <= 2 && c->bufs.count("s16:part" + sfx) != 0 && c->h2_slot.count(scope + "/conv1/conv") != 0;
+                            c->use_p3 && c->p3_from_stage <= 2 && c->bufs.count("s16:part" + sfx) != 0 && has_h2_filter(scope + "/conv1/conv");
         // the batch-norm accumulators start at zero: cleared by the trunk's first kernel where that is stem8_prep / stem16_amax, else by a fill
         if (!fast8 && !fast16 && !rc && hipMemsetAsync(c->p("bnacc" + sfx), 0, c->bufs.at("bnacc" + sfx).n * sizeof(float), s) != hipSuccess)
             rc = fail(SAGEN_ERR_HIP, "hipMemsetAsync(bn accumulators) failed");
@@ -692,11 +748,11 @@ struct Fwd {
                 layer = name + "+pool";
                 if (fast16)
                     timed("stem8pool_kernel<f16>", 2.0 * B * H * W * 64 * 224, [&] {
-                        return stem16pool_launch(c->p("xpad" + sfx), c->p("pkh:" + name + "/weights"), c->v(name + "/bn/gamma"), c->p("rx0" + sfx), bn_acc(li),
-                                                 s16_a_inv, c->p("h2s") + c->h2_slot.at(name), B, s); });
+                        return stem16pool_launch(c->p("xpad" + sfx), h2_filter(name).w2, c->v(name + "/bn/gamma"), c->p("rx0" + sfx), bn_acc(li),
+                                                 s16_a_inv, h2_filter(name).w_inv, B, s); });
                 else if (fast8h)
                     timed("stem8pool_kernel<h2>", 2.0 * B * H * W * 64 * 224, [&] {
-                        return stem8pool_h2_launch(c->p("xpad" + sfx), c->p("pk:" + name + "/weights"), c->p("pkh:" + name + "/weights"), c->p("h2s") + c->h2_slot.at(name),
+                        return stem8pool_h2_launch(c->p("xpad" + sfx), c->p("pk:" + name + "/weights"), h2_filter(name).w2, h2_filter(name).w_inv,
                                                    c->v(name + "/bn/gamma"), c->p("rx0" + sfx), bn_acc(li), B, s); });
                 else
                 timed("stem8pool_kernel", 2.0 * B * H * W * 64 * 224, [&] {
@@ -772,15 +828,8 @@ struct Fwd {
                 auto shortcut_s2d = [&] {
                     IgemmDesc d = conv_desc(nullptr, H / 2, W / 2, cin, cin, c->p("pk:" + pfx + "/shortcut/weights"), 1, 1, 1, 1, true,
                                             cout, c->p("rsc" + sfx), cout, Ho, Wo);
-                    d.xp3 = in_s2d;
-                    d.p3_np = B * (H / 2) * (W / 2 + 1);
-                    d.xp3_fmt = 1;
-                    d.xp3_cstride = (unsigned)((size_t)d.p3_np * 64);
-                    d.xp3_bytes = (unsigned)p3h_bytes(B, H / 2, W / 2, cin);
-                    d.wh2 = c->p("pkh:" + pfx + "/shortcut/weights");
-                    d.wh2_bytes = (unsigned)((size_t)d.N * d.Kpad * 4);
-                    d.h2_a_inv = x_ai;
-                    d.h2_w_inv = c->p("h2s") + c->h2_slot.at(pfx + "/shortcut");
+                    const H2Filter w = h2_filter(pfx + "/shortcut");
+                    igemm_set_h2_planes(d, in_s2d, B, H / 2, W / 2, cin, w.w2, x_ai, w.w_inv);
                     d.stats = bn_acc(20 + st);
                     layer = pfx + "/shortcut#s2d";
                     gemm(d, 1, false);
@@ -788,32 +837,11 @@ struct Fwd {
                 if (first && in_s2d && !in_planes) {
                     shortcut_s2d();
                     shortcut = c->p("rsc" + sfx);
-                } else if (first) {   // 1x1/2 projection, no bias, no BN (resnet.py:211-212)
-                    IgemmDesc d = conv_desc(xin, H, W, cin, cin, c->p("pk:" + pfx + "/shortcut/weights"), 1, 1, 2, 2, true,
-                                            cout, c->p("rsc" + sfx), cout, Ho, Wo);
-                    if (!x_fp32_valid) d.x = nullptr;                   // the merge wrote this block input as planes only
-                    if (in_planes) {
-                        d.xp3 = in_planes;
-                        d.p3_np = B * H * (W + 1);
-                        auto hs = c->h2_slot.find(pfx + "/shortcut");
-                        if (h2() && hs != c->h2_slot.end()) {
-                            d.xp3_fmt = 1;
-                            d.xp3_cstride = (unsigned)((size_t)d.p3_np * 64);
-                            d.xp3_bytes = (unsigned)p3h_bytes(B, H, W, cin);
-                            d.wh2 = c->p("pkh:" + pfx + "/shortcut/weights");
-                            d.wh2_bytes = (unsigned)((size_t)d.N * d.Kpad * 4);
-                            d.h2_a_inv = x_ai ? x_ai : h2_a_inv();
-                            d.h2_w_inv = c->p("h2s") + hs->second;
-                        } else {
-                            d.xp3_cstride = (unsigned)((size_t)d.p3_np * 96);
-                            d.xp3_bytes = (unsigned)p3_bytes(B, H, W, cin);
-                        }
-                    }
-                    if (h2() && p3_here) d.stats = bn_acc(20 + st);      // (sum, sumsq) of the projection: the residual's magnitude for the merge's fp16 scale
-                    layer = pfx + "/shortcut";
-                    gemm(d, 1, false);
+                } else if (first) {   // (x_fp32_valid false: the merge wrote this block input as planes only; without fp16x2: bf16x3 planes, no scale)
+                    const bool proj_h2 = h2() && has_h2_filter(pfx + "/shortcut");
+                    projection(pfx, st, xin, x_fp32_valid, H, W, cin, cout, in_planes, proj_h2 ? (x_ai ? x_ai : h2_a_inv()) : nullptr, h2() && p3_here, Ho, Wo);
                     if (in_s2d && !rc) {    // tuning: both layouts are there - plan the dense form too (it leaves the same sums and statistics)
-                        if (memset_groups(d.stats, (size_t)2 * d.N * sizeof(double)) != hipSuccess) rc = fail(SAGEN_ERR_HIP, "autotune: memset failed");
+                        if (memset_groups(bn_acc(20 + st), (size_t)2 * cout * sizeof(double)) != hipSuccess) rc = fail(SAGEN_ERR_HIP, "autotune: memset failed");
                         shortcut_s2d();
                     }
                     shortcut = c->p("rsc" + sfx);
@@ -1025,24 +1053,9 @@ struct Fwd {
                 void* nplanes = p3_here && (unit == 1 || to_next_stage) ? (keep ? pl_buf("x", kidx + 1) : (void*)c->p("p3" + sfx)) : nullptr;
                 // unit 2 of a plane stage finds the planes of its input written by unit 1's merge (stage 2's unit 1: by the pool)
                 const bool x_planes = p3_here && (stride == 1 ? (unit == 2 || (keep && st == 0)) : (keep && c->use_p3g));
-                if (first) {
-                    IgemmDesc d = conv_desc(xin, H, W, cin, cin, c->p("pk:" + pfx + "/shortcut/weights"), 1, 1, 2, 2, true,
-                                            cout, c->p("rsc" + sfx), cout, Ho, Wo);
-                    auto hsc = c->h2_slot.find(pfx + "/shortcut");
-                    if (x_planes && hsc != c->h2_slot.end()) {       // the projection on the planes of the block input (conv3g_kernel)
-                        d.xp3 = xplanes;
-                        d.p3_np = B * H * (W + 1);
-                        d.xp3_fmt = 1;
-                        d.xp3_cstride = (unsigned)((size_t)d.p3_np * 64);
-                        d.xp3_bytes = (unsigned)p3h_bytes(B, H, W, cin);
-                        d.wh2 = c->p("pkh:" + pfx + "/shortcut/weights");
-                        d.wh2_bytes = (unsigned)((size_t)d.N * d.Kpad * 4);
-                        d.h2_a_inv = xplanes_ai;
-                        d.h2_w_inv = c->p("h2s") + hsc->second;
-                    }
-                    if (h2() && p3_here) d.stats = bn_acc(20 + st);      // the projection's (sum, sumsq): the residual bound of the merge's fp16 scale
-                    layer = pfx + "/shortcut";
-                    gemm(d, 1, false);
+                if (first) {          // the projection on the planes of the block input (conv3g_kernel) where they are retained
+                    projection(pfx, st, xin, true, H, W, cin, cout, x_planes && has_h2_filter(pfx + "/shortcut") ? xplanes : nullptr, xplanes_ai,
+                               h2() && p3_here, Ho, Wo);
                     shortcut = c->p("rsc" + sfx);
                 }
                 float* y1 = c->p("t:y1:" + k); float* a1 = c->p("t:a1:" + k); float* y2 = c->p("t:y2:" + k); float* xout = c->p("t:out:" + k);

@@ -140,42 +140,22 @@ int sagen_create_impl(sagen_ctx** out, const sagen_config* cfg, int groups) {
     // packed filters
     size_t h2_pack_blocks = 0;
     for (const auto& vs : c->vars) {
-        if (vs.name.size() < 8 || vs.name.compare(vs.name.size() - 8, 8, "/weights") != 0) continue;
-        size_t n;
-        if (vs.name.find("/deconv") != std::string::npos) {
-            const int l = vs.name[vs.name.find("/deconv") + 7] - '1';
-            const int sh = AENC_S[l][0], sw = AENC_S[l][1];
-            const long taps = (long)cdiv(vs.shape[0], sh) * cdiv(vs.shape[1], sw);
-            n = packed_floats((long)sh * sw * vs.shape[2], taps * vs.shape[3]);
-        } else if (vs.ndim == 4) {
-            long cinp = vs.shape[2] == 3 ? 4 : vs.shape[2];
-            long taps = vs.shape[0] * vs.shape[1];
-            if (vs.shape[2] == 3) taps = vs.shape[0] * (vs.shape[1] + 1);        // ResNet stem: tap rows padded 7 -> 8 (igemm3s2.hip)
-            if (vs.shape[2] == 1) { cinp = vs.shape[1]; taps = vs.shape[0]; }   // audio conv1: kw acts as channels
-            n = packed_floats(vs.shape[3], taps * cinp);
-        } else {
-            n = packed_floats(vs.shape[1], vs.shape[0]);
-        }
+        if (!is_weights(vs.name)) continue;
+        const PkSpec k = pk_spec(vs);
+        const std::string lname = vs.name.substr(0, vs.name.size() - 8);
+        const size_t n = (size_t)k.N * k.Kpad;
         c->alloc("pk:" + vs.name, packed_split_floats(n));      // fp32 filter + its three bf16 planes (bf16x3 tiles)
-        if (vs.name.find("/deconv") != std::string::npos) {     // deconv5 .. deconv2 also in scatter form: [(p, q, o)][c] (Fwd::deconv_scatter)
-            const int l = vs.name[vs.name.find("/deconv") + 7] - '1';
-            if (l >= 1 && vs.shape[3] % 16 == 0) {
-                const size_t ns = packed_floats((long)vs.shape[0] * vs.shape[1] * vs.shape[2], vs.shape[3]);
-                c->alloc("pks:" + vs.name, packed_split_floats(ns));
-                c->alloc("pkhs:" + vs.name, ns);                   // ... and as two fp16 planes (conv3g_kernel on planes of the concat buffer)
-                h2_pack_blocks += ns / 1024 + 1;
-                c->h2_slot["pks:" + vs.name.substr(0, vs.name.size() - 8)] = -1;     // (slot numbers are dealt below)
-            }
+        if (k.Ns) {                                             // scatter form (Fwd::deconv_scatter), fp32 + bf16x3 and as two fp16 planes
+            const size_t ns = (size_t)k.Ns * k.Ks;
+            c->alloc("pks:" + vs.name, packed_split_floats(ns));
+            c->alloc("pkhs:" + vs.name, ns);
+            h2_pack_blocks += ns / 1024 + 1;
+            c->h2_slot["pks:" + lname] = -1;                    // (slot numbers are dealt below)
         }
-        // the 3x3 convs (and 1x1 projections) of the ResNet trunks also as two fp16 planes of w * 2^kw (conv3h.hip): N * Kpad * 2 halves
-        // ... and deconv1 of the mask decoder (conv3g_kernel with the fused decoder tail on planes of cat1: sagen_forward_impl)
-        if ((vs.ndim == 4 && ((vs.shape[0] == 3 && vs.shape[1] == 3) || (vs.shape[0] == 1 && vs.shape[1] == 1)) && vs.shape[2] % 16 == 0 &&
-             vs.name.find("_encoder/conv") != std::string::npos) || vs.name == "separation/deconv1/weights" ||
-            (vs.ndim == 4 && vs.shape[2] == 3 && vs.name.find("_encoder/conv1/conv/weights") != std::string::npos) ||      // ... and the stem, for float frames (stem8.hip, F16)
-            (vs.ndim == 4 && vs.shape[2] % 16 == 0 && vs.name.compare(0, 18, "audio_encoder/conv") == 0)) {                 // ... and conv2 .. conv5 of the audio encoder (round 6: conv3g_kernel on planes of cat_l's encoder half)
+        if (k.h2) {                                             // N * Kpad * 2 halves
             c->alloc("pkh:" + vs.name, n);
             h2_pack_blocks += n / 1024 + 1;
-            c->h2_slot[vs.name.substr(0, vs.name.size() - 8)] = -1;
+            c->h2_slot[lname] = -1;
         }
     }
     {   // 2^-kw slots of the fp16x2 filter planes, h2s[8 ..]
@@ -294,7 +274,7 @@ int sagen_create_impl(sagen_ctx** out, const sagen_config* cfg, int groups) {
     }
     c->grp_floats = c->ws_floats - c->grp_off;          // (a multiple of 64 floats: every buffer is rounded up to 256 bytes)
     c->ws_floats = c->grp_off + (size_t)c->G * c->grp_floats;
-    if (c->G > 1 && (c->use_fcm || c->sk_fused || c->fp32_only || !c->use_h2 || !c->use_p3 || !c->use_p3g || c->p3_from_stage > 2 || c->no_lean_trunk)) {
+    if (c->G > 1 && sagen_ctx::off_grouped(c)) {
         sagen_destroy_impl(c);
         return fail(SAGEN_ERR_UNSUPPORTED, "sagen_create_grouped: the grouped launch runs the default kernels only (an environment switch selected others)");
     }
@@ -353,34 +333,18 @@ int sagen_bind_impl(sagen_ctx* c, const sagen_tensor* tensors, int n, void* work
 
 // repack every filter from the bound variables into the kernels' layouts (bind; and once per training step, after the optimiser
 // has updated the variables in place)
-// The pack of one "/weights" variable as a job of the batched launch (same layouts as the single-variable launchers of igemm.hip)
-static PackJob forward_pack_job(const sagen_ctx* c, const VarSpec& vs) {
+// The pack of one "/weights" variable as a job of the batched launch (same layouts as the single-variable launchers of igemm.hip);
+// scatter: its scatter form, rows (p, q, o), columns c
+static PackJob forward_pack_job(const sagen_ctx* c, const VarSpec& vs, const PkSpec& k, bool scatter = false) {
     PackJob j;
     j.src = c->v(vs.name);
-    j.dst = c->p("pk:" + vs.name);
-    if (vs.name.find("/deconv") != std::string::npos) {
-        const int l = vs.name[vs.name.find("/deconv") + 7] - '1';
-        const int sh = AENC_S[l][0], sw = AENC_S[l][1];
-        const int nth = cdiv(vs.shape[0], sh), ntw = cdiv(vs.shape[1], sw);
-        j.kind = PACK_DECONV;
-        j.N = sh * sw * (int)vs.shape[2];
-        j.Kpad = (nth * ntw * (int)vs.shape[3] + 15) / 16 * 16;
-        j.p[0] = (int)vs.shape[0]; j.p[1] = (int)vs.shape[1]; j.p[2] = (int)vs.shape[2]; j.p[3] = (int)vs.shape[3]; j.p[4] = sh; j.p[5] = sw; j.p[6] = ntw;
-    } else if (vs.ndim == 4) {
-        int cin = (int)vs.shape[2], cinp = cin == 3 ? 4 : cin, taps = (int)(vs.shape[0] * vs.shape[1]);
-        if (cin == 1) { cin = cinp = (int)vs.shape[1]; taps = (int)vs.shape[0]; }
-        const bool stem = cin == 3;                   // tap rows padded 7 -> 8, K = (dh, dw8, c4)
-        if (stem) taps = (int)(vs.shape[0] * (vs.shape[1] + 1));
-        j.kind = PACK_CONV;
-        j.N = (int)vs.shape[3];
-        j.Kpad = (taps * cinp + 15) / 16 * 16;
-        j.p[0] = taps; j.p[1] = cin; j.p[2] = cinp; j.p[3] = (int)vs.shape[3];
-        j.p[4] = stem ? (int)vs.shape[1] : 0; j.p[5] = stem ? (int)vs.shape[1] + 1 : 0;
+    j.dst = c->p((scatter ? "pks:" : "pk:") + vs.name);
+    if (scatter) {
+        j.kind = PACK_ROWS; j.N = k.Ns; j.Kpad = k.Ks;
+        j.p[0] = k.Ns; j.p[1] = k.Ks;
     } else {
-        const int K = (int)vs.shape[0], N = (int)vs.shape[1];
-        j.kind = PACK_CONV;
-        j.N = N; j.Kpad = (K + 15) / 16 * 16;
-        j.p[0] = 1; j.p[1] = K; j.p[2] = K; j.p[3] = N;
+        j.kind = k.kind; j.N = k.N; j.Kpad = k.Kpad;
+        std::copy(k.p, k.p + 7, j.p);
     }
     return j;
 }
@@ -399,17 +363,10 @@ int sagen_repack_part(sagen_ctx* c, hipStream_t s, int part) {
     if (c->pack_jobs.empty()) {          // first call after bind: build the table from the bound variables and ship it
         for (int pass = 0; pass < 2; ++pass) {
             for (const auto& vs : c->vars) {
-                if (vs.name.size() < 8 || vs.name.compare(vs.name.size() - 8, 8, "/weights") != 0) continue;
-                const bool stem = vs.name.find("/conv1/conv/") != std::string::npos;
-                if (stem == (pass == 0)) c->pack_jobs.push_back(forward_pack_job(c, vs));
-                if (pass == 1 && c->bufs.count("pks:" + vs.name)) {      // the scatter-form pack of a stride-1 transposed conv: rows (p, q, o), columns c
-                    PackJob j;
-                    j.src = c->v(vs.name); j.dst = c->p("pks:" + vs.name);
-                    j.kind = PACK_ROWS;
-                    j.N = (int)(vs.shape[0] * vs.shape[1] * vs.shape[2]); j.Kpad = (int)vs.shape[3];
-                    j.p[0] = j.N; j.p[1] = (int)vs.shape[3];
-                    c->pack_jobs.push_back(j);
-                }
+                if (!is_weights(vs.name)) continue;
+                const PkSpec k = pk_spec(vs);
+                if (k.stem == (pass == 0)) c->pack_jobs.push_back(forward_pack_job(c, vs, k));
+                if (pass == 1 && k.Ns) c->pack_jobs.push_back(forward_pack_job(c, vs, k, true));
             }
             if (pass == 0) c->pack_early_jobs = (int)c->pack_jobs.size();
         }
@@ -428,34 +385,22 @@ int sagen_repack_part(sagen_ctx* c, hipStream_t s, int part) {
     // the fp16x2 filter planes of the trunks' 3x3 convs and 1x1 projections, from the fp32 packs just written: two launches for all
     // of them (bind; every training step)
     if (c->h2_jobs.empty()) {
-        int nb = 0;
-        for (const auto& kv : c->h2_slot) {
-            const bool scatter = kv.first.compare(0, 4, "pks:") == 0;       // the scatter-form pack of a transposed conv: rows (p, q, o), columns c
-            const std::string vname = (scatter ? kv.first.substr(4) : kv.first) + "/weights";
-            const VarSpec* vs = nullptr;
-            for (const auto& v : c->vars) if (v.name == vname) vs = &v;
-            if (!vs) continue;
-            H2Job j;
-            if (scatter) {
-                j.N = (int)(vs->shape[0] * vs->shape[1] * vs->shape[2]); j.Kpad = (int)vs->shape[3];
-                j.wp = c->p("pks:" + vs->name); j.w2 = c->p("pkhs:" + vs->name); j.w_inv = c->p("h2s") + kv.second;
-                j.first_block = nb;
-                nb += (int)(((long)j.N * j.Kpad + 1023) / 1024);
-                c->h2_jobs.push_back(j);
-                continue;
-            }
-            j.N = (int)vs->shape[3]; j.Kpad = (int)(vs->shape[0] * vs->shape[1] * vs->shape[2]);
-            if (vs->shape[2] == 3) j.Kpad = (int)(vs->shape[0] * (vs->shape[1] + 1) * 4);      // the stem's pack: tap rows padded 7 -> 8, channels 3 -> 4
-            if (vs->name.find("/deconv") != std::string::npos) {      // depth-to-space pack: N = (ry, rx, o), K = (dp, dq, c)
-                const int l = vs->name[vs->name.find("/deconv") + 7] - '1';
-                j.N = AENC_S[l][0] * AENC_S[l][1] * (int)vs->shape[2];
-                j.Kpad = cdiv(vs->shape[0], AENC_S[l][0]) * cdiv(vs->shape[1], AENC_S[l][1]) * (int)vs->shape[3];
-            }
-            j.wp = c->p("pk:" + vs->name); j.w2 = c->p("pkh:" + vs->name); j.w_inv = c->p("h2s") + kv.second;
-            j.first_block = nb;
-            nb += (int)(((long)j.N * j.Kpad + 1023) / 1024);
-            c->h2_jobs.push_back(j);
+        c->h2_jobs.assign(c->h2_slot.size(), H2Job());          // in slot order (the slots were dealt in the map's key order)
+        for (const auto& vs : c->vars) {
+            if (!is_weights(vs.name)) continue;
+            const PkSpec k = pk_spec(vs);
+            auto job = [&](const std::string& key, const char* from, const char* to, int N, int Kpad) {
+                const int slot = c->h2_slot.at(key);
+                H2Job& j = c->h2_jobs[slot - H2S_FILTER_FIRST];
+                j.N = N; j.Kpad = Kpad;
+                j.wp = c->p(from + vs.name); j.w2 = c->p(to + vs.name); j.w_inv = c->p("h2s") + slot;
+            };
+            const std::string lname = vs.name.substr(0, vs.name.size() - 8);
+            if (k.h2) job(lname, "pk:", "pkh:", k.N, k.Kpad);
+            if (k.Ns) job("pks:" + lname, "pks:", "pkhs:", k.Ns, k.Ks);
         }
+        int nb = 0;
+        for (H2Job& j : c->h2_jobs) { j.first_block = nb; nb += (int)(((long)j.N * j.Kpad + 1023) / 1024); }
         c->h2_blocks = nb;
         if (c->h2_jobs.size() * sizeof(H2Job) > c->bufs.at("h2:jobs").n * sizeof(float)) return fail(SAGEN_ERR_WORKSPACE, "fp16x2 job table too small");
         if (!c->h2_jobs.empty() && hipMemcpyAsync(c->p("h2:jobs"), c->h2_jobs.data(), c->h2_jobs.size() * sizeof(H2Job), hipMemcpyHostToDevice, s) != hipSuccess)
@@ -491,7 +436,7 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
     } group_scope(c->group_info());
     if (c->G > 1) {
         if (c->train_mode) return fail(SAGEN_ERR_UNSUPPORTED, "the training step has no grouped launch");
-        if (!c->freq_mask || c->fp32_only || !c->use_h2 || !c->use_p3 || !c->use_p3g || c->p3_from_stage > 2 || c->no_lean_trunk || c->use_fcm || c->sk_fused ||
+        if (!c->freq_mask || sagen_ctx::off_grouped(c) ||
             (c->has_video && !c->video_u8 && !c->stem16) || (c->has_video && c->video_u8 && !c->stem8) || (c->has_flow && !c->stem16))
             return fail(SAGEN_ERR_UNSUPPORTED, "grouped forward: an option moved the path off the kernels that take a group dimension "
                         "(fp16x2 / planes_from_stage / plane_gather / u8_fast_stem / f16_fast_stem must keep their defaults)");
@@ -592,7 +537,7 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
         // Round 6: conv2 .. conv5 on fp16x2 planes of cat_l's encoder half (conv3g_kernel: three products per multiply, no operand split in
         // the K loop) - the planes' scale is that half's EXACT maximum, published by conv_l's epilogue (as for the decoder, round 5).  With
         // several batches per launch these layers were the register-staged family's largest share (40 - 76 TFLOP/s: 11 % of a grouped call)
-        bool aud_planes = l >= 1 && want_amax && !c->no_aud_planes && f.h2() && c->bufs.count("aencp") != 0 && c->h2_slot.count(name) != 0 &&
+        bool aud_planes = l >= 1 && want_amax && !c->no_aud_planes && f.h2() && c->bufs.count("aencp") != 0 && g.has_h2_filter(name) &&
                           conv3g_ok_desc(d, c->enc_c[l]);
         if (aud_planes && !c->tuning) {             // a plan that names a register-staged tile keeps the fp32 operand (no pack pass)
             auto it = c->plan.find(name);
@@ -607,14 +552,10 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
             g.layer = name + "/planes";
             g.timed("h2_pack_rows_kernel", 0.0, [&] {
                 return h2_pack_rows_launch(c->p("cat" + std::to_string(l)) + cp, (long)Hl * Wl * 2 * cp, (long)Wl * 2 * cp, 2 * cp, 0, B, Hl, Wl, cp,
-                                           g.cat_amax(l, 1), nullptr, c->p("aencp"), a_inv, reinterpret_cast<unsigned*>(c->p("h2s") + 7), g.s); });
+                                           g.cat_amax(l, 1), nullptr, c->p("aencp"), a_inv, g.h2_sat_count(), g.s); });
             g.layer = name;
-            d.xp3 = c->p("aencp"); d.xp3_fmt = 1; d.xp3_row0 = 0; d.xp3_rows = 0;
-            d.p3_np = B * Hl * (Wl + 1);
-            d.xp3_cstride = (unsigned)((size_t)d.p3_np * 64);
-            d.xp3_bytes = (unsigned)((size_t)d.xp3_cstride * (cp / 16));
-            d.wh2 = c->p("pkh:" + name + "/weights"); d.wh2_bytes = (unsigned)((size_t)d.N * d.Kpad * 4);
-            d.h2_a_inv = a_inv; d.h2_w_inv = c->p("h2s") + c->h2_slot.at(name);
+            const Fwd::H2Filter w = g.h2_filter(name);
+            igemm_set_h2_planes(d, c->p("aencp"), B, Hl, Wl, cp, w.w2, a_inv, w.w_inv);
         }
         g.gemm(d);
     }
@@ -800,19 +741,11 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
         f.layer = "separation/cat1-planes";
         f.timed("h2_pack_rows_kernel", 0.0, [&] {
             return h2_pack_rows_launch(c->p("cat1"), (long)c->enc_h[1] * W1 * C1, (long)W1 * C1, C1, 10, B, 7, W1, C1, f.cat_amax(1, 0), f.cat_amax(1, 1), c->p("cat1p"),
-                                       f.cat_a_inv(1), reinterpret_cast<unsigned*>(c->p("h2s") + 7), s); });
-        const float* w_inv = c->p("h2s") + c->h2_slot.at("separation/deconv1");
+                                       f.cat_a_inv(1), f.h2_sat_count(), s); });
+        const Fwd::H2Filter w = f.h2_filter("separation/deconv1");
         const void* planes = c->p("cat1p");
-        const void* wh2 = c->p("pkh:separation/deconv1/weights");
         const float* a_inv = f.cat_a_inv(1);
-        d1_tweak = [=](IgemmDesc& d) {
-            d.xp3 = planes; d.xp3_fmt = 1; d.xp3_row0 = 10; d.xp3_rows = 7;
-            d.p3_np = B * 7 * (W1 + 1);
-            d.xp3_cstride = (unsigned)((size_t)d.p3_np * 64);
-            d.xp3_bytes = (unsigned)((size_t)d.xp3_cstride * (C1 / 16));
-            d.wh2 = wh2; d.wh2_bytes = (unsigned)((size_t)d.N * d.Kpad * 4);
-            d.h2_a_inv = a_inv; d.h2_w_inv = w_inv;
-        };
+        d1_tweak = [=](IgemmDesc& d) { igemm_set_h2_planes(d, planes, B, 7, W1, C1, w.w2, a_inv, w.w_inv, 10, 7); };
     }
     const int nmask = c->nsep * c->nin;              // deconv1 channels: input channel i, track j -> i * nsep + j (model.py:326-327)
     f.deconv(c->p("cat1"), 31, 127, 64, 0, c->p("dmask"), nmask, false, 11, 17, 67, 23L * 1024 * nmask, 44, c->p("coeffs"), ebuf, 23, d1_tweak);
@@ -962,7 +895,7 @@ int sagen_counter_impl(sagen_ctx* c, const char* name, uint64_t* value, hipStrea
     if (std::string(name) != "fp16x2_saturations") return fail(SAGEN_ERR_UNSUPPORTED, "sagen_counter: unknown counter %s", name);
     unsigned v[SAGEN_MAX_GROUPS] = {0};      // one counter per group
     for (int g = 0; g < c->G; ++g)
-        SAGEN_HIP_CHECK(hipMemcpyAsync(&v[g], c->p("h2s") + (size_t)g * c->grp_floats + 7, sizeof(unsigned), hipMemcpyDeviceToHost, s));
+        SAGEN_HIP_CHECK(hipMemcpyAsync(&v[g], c->p("h2s") + (size_t)g * c->grp_floats + H2S_SAT_COUNT, sizeof(unsigned), hipMemcpyDeviceToHost, s));
     SAGEN_HIP_CHECK(hipStreamSynchronize(s));
     uint64_t tot = 0;
     for (int g = 0; g < c->G; ++g) tot += v[g];

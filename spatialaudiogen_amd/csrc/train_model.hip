@@ -79,8 +79,6 @@ static bool dgrad_phased(int batch, const std::string& n, const PkdSpec& p) {
 }
 static int phase_taps(int k, int r) { return (k - r + 1) / 2; }      // taps dp >= 0 with r + 2 dp < k
 
-static bool is_weights(const std::string& n) { return n.size() >= 8 && n.compare(n.size() - 8, 8, "/weights") == 0; }
-
 static void train_carve(sagen_ctx* c) {
     if (c->tws_floats) return;
     const int B = c->B, nsep = c->nsep, Cb = c->Cb;
@@ -343,6 +341,8 @@ struct Bwd : Fwd {
     }
 
     // ---- data gradients on the forward's contraction kernels ----
+    // a layer's data-gradient filter as fp16x2 planes ("pkdh:") and its 2^-kw in the "t:h2d" table
+    H2Filter h2d_filter(const std::string& name) const { return {c->p("pkdh:" + name + "/weights"), c->p("t:h2d") + c->h2d_slot.at(name + "/weights")}; }
     // stride-1 SAME conv (kh x kw odd): dx = conv(dy, flipped / transposed filter)
     // `planes`: dy as fp16x2 planes (bn_bwd wrote them beside the fp32 dy the weight gradient reads) -> conv3h_kernel
     void dgrad_s1(const std::string& name, const float* dy, int H, int W, int Cout, int Cin, float* dx, const void* planes = nullptr,
@@ -350,18 +350,10 @@ struct Bwd : Fwd {
         if (rc) return;
         int Ho, Wo;
         IgemmDesc d = conv_desc(dy, H, W, Cout, Cout, c->p("pkd:" + name + "/weights"), 3, 3, 1, 1, true, Cin, dx, Cin, Ho, Wo);
-        auto hs = c->h2d_slot.find(name + "/weights");
-        if (planes && planes_a_inv && hs != c->h2d_slot.end()) {
+        if (planes && planes_a_inv && c->h2d_slot.count(name + "/weights")) {
             d.x = nullptr;                          // only the plane-fed tiles may run: the fp32 dy need not exist (bn_bwd)
-            d.xp3 = planes;
-            d.p3_np = c->B * H * (W + 1);
-            d.xp3_fmt = 1;
-            d.xp3_cstride = (unsigned)((size_t)d.p3_np * 64);
-            d.xp3_bytes = (unsigned)p3h_bytes(c->B, H, W, Cout);
-            d.wh2 = c->p("pkdh:" + name + "/weights");
-            d.wh2_bytes = (unsigned)((size_t)d.N * d.Kpad * 4);
-            d.h2_a_inv = planes_a_inv;
-            d.h2_w_inv = c->p("t:h2d") + hs->second;
+            const H2Filter w = h2d_filter(name);
+            igemm_set_h2_planes(d, planes, c->B, H, W, Cout, w.w2, planes_a_inv, w.w_inv);
         }
         layer = "dgrad:" + name;
         contract(d, 1, split_ok);
@@ -446,7 +438,7 @@ struct Bwd : Fwd {
             timed("bn_bwd_reduce_kernel", 0.0, [&] { return bn_bwd_reduce_launch(ga, gb, a, y, bn, npix, C, acc, c->p(redws), s, sm, mx, &nb, relu_bits); });
             timed("bn_bwd_apply_h2_kernel", 0.0, [&] {
                 return bn_bwd_apply_h2_launch(ga, gb, a, y, bn, acc, c->B, H, W, C, planes_only ? nullptr : dy, dz, grad(bn_name + "/bn/gamma"), grad(bn_name + "/bn/beta"), s, sm,
-                                              planes, mx, nb, planes_a_inv, reinterpret_cast<unsigned*>(c->p("h2s") + 7), relu_bits); });
+                                              planes, mx, nb, planes_a_inv, h2_sat_count(), relu_bits); });
             return !rc;
         }
         bn_bwd_plain(bn_name, li, ga, gb, act, y, npix, C, dy, dz, self_mask);

@@ -112,3 +112,37 @@ def test_tile_table_is_exposed_and_consistent():
     assert names == golden
     import test_gpu_model
     assert test_gpu_model.ALL_TILES_FALLBACK == n
+
+
+# configurations whose workspace sizes are pinned (tests/golden/workspace_bytes_v1.txt): name -> (groups, train size too?, overrides of _cfg)
+WORKSPACE_CASES = [
+    ('b2_audio', 1, True, dict(batch=2, encoders=1)),
+    ('b2_audio_video', 1, True, dict(batch=2, encoders=3)),
+    ('b2_audio_video_flow', 1, True, dict(batch=2, encoders=7)),
+    ('b2_audio_video_sep_none', 1, False, dict(batch=2, encoders=3, separation=0, num_sep_tracks=1)),
+    ('b2_audio_video_tracks16', 1, False, dict(batch=2, encoders=3, num_sep_tracks=16)),
+    ('b2_audio_video_tracks64', 1, False, dict(batch=2, encoders=3, num_sep_tracks=64)),
+    ('b2_audio_video_ambi2', 1, False, dict(batch=2, encoders=3, ambi_order=2)),
+    ('b16_audio_video', 1, False, dict(batch=16, encoders=3)),
+    ('b2_audio_video_groups2', 2, False, dict(batch=2, encoders=3)),
+]
+
+
+def workspace_sizes(lib):
+    """'name bytes [train bytes]' per case of WORKSPACE_CASES: what the golden file holds, one line each."""
+    lines = []
+    for name, groups, train, kw in WORKSPACE_CASES:
+        h, cfg = C.c_void_p(), _cfg(**kw)
+        rc = lib.sagen_create(C.byref(h), C.byref(cfg)) if groups == 1 else lib.sagen_create_grouped(C.byref(h), C.byref(cfg), groups)
+        assert rc == 0, (name, lib.sagen_last_error())
+        sizes = [lib.sagen_workspace_bytes(h)] + ([lib.sagen_train_workspace_bytes(h)] if train else [])
+        lib.sagen_destroy(h)
+        lines.append(' '.join([name] + [str(int(v)) for v in sizes]))
+    return lines
+
+
+def test_workspace_sizes_are_frozen(lib):
+    """The workspace layout is part of behaviour: the carving of the context (packed filters, fp16x2 planes, job tables, activations) and
+    of the training workspace must give the sizes recorded from the build named in the golden file's comment line."""
+    golden = [l for l in open(os.path.join(ROOT, 'tests', 'golden', 'workspace_bytes_v1.txt')).read().split('\n') if l and not l.startswith('#')]
+    assert workspace_sizes(lib) == golden
