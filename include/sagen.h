@@ -361,6 +361,51 @@ size_t sagen_overlay_blend_scratch_bytes(int n_maps, int mh, int mw, int n_frame
 int sagen_overlay_blend(const float* maps, int n_maps, int64_t map0, int mh, int mw, const double* lut, const uint8_t* frames, int n_frames,
                         int64_t frame0, int h, int w, int frames_per_map, uint8_t* out, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- reprojection of 360-degree frames: equirectangular, cube maps, equi-angular cube maps, head viewport ----------------
+ * What the reference does offline before the network sees a frame - the first-eye crop of scraping/preprocess.py:51-52, the
+ * equi-angular unwarp and x / y remap tables of scraping/utils.py:91-144, the cube <-> equirect step of 3rd-party/vrProjector
+ * (CubemapProjection.py:68-121, EquirectangularProjection.py:23-42) - and, behind the network, the pinhole view of a listener whose
+ * head is turned by the Rot that ambisonics.head_rotation_matrix takes.  One operation: every destination sub-sample has a
+ * direction, the direction is rotated, lands on a source pixel and is fetched bilinearly.
+ *
+ * World frame: x front, y left, z up; az = atan2(y, x), el = atan2(z, hypot(x, y)).  Positions are pixel centres: sub-sample (a, b)
+ * of pixel (i, j) of a cell of W x H pixels sits at xf = (i + (a + 0.5) / S) / W, yf = (j + (b + 0.5) / S) / H, S = supersample.
+ *   SAGEN_PROJ_ER    az = pi - 2 pi xf, el = pi / 2 - pi yf (front at the centre, the listener's left on the left).  As a source:
+ *                    x = (pi - az) / (2 pi) W - 0.5, y = (pi / 2 - el) / pi H - 0.5, bilinear, wrapping in x, clamped in y.  The
+ *                    image is the rectangle (x0, y0, w, h) of the frame (w = h = 0: the whole frame); top-bottom stereo is the
+ *                    rectangle of the top half.
+ *   SAGEN_PROJ_CUBE  face coordinates (p, q) = (2 xf - 1, 2 yf - 1) in the face's cell; direction = axis + p right + q down.  As a
+ *                    source the face is the one whose axis has the largest |component|; x = (p + 1) / 2 n - 0.5 clamped into
+ *                    [0, n - 1] (likewise y): bilinear inside the face, no filtering across faces.
+ *   SAGEN_PROJ_EAC   the same with p -> tan(pi p / 4), q -> tan(pi q / 4) (the inverse of utils.py:97-98).
+ *   SAGEN_PROJ_VIEW  destination only: direction = (1, t (1 - 2 xf), t (H / W) (1 - 2 yf)), t = tan(hfov / 2), hfov in radians.
+ * face[f], f = 0..5, is the face of axis +x -x +y -y +z -z: a square rectangle of the frame and an orientation 0..7 against
+ * vrProjector's face image of that axis (bit 2: mirrored left-right; bits 0-1: quarter turns, 1 = the cell is np.rot90(image)).
+ * Destination pixels that lie in no rectangle are not written.
+ *
+ * src [n][src_h][src_w][3], dst [n][dst_h][dst_w][3] uint8 (RGB only).  rot [n_rot][3][3] fp64 DEVICE array, row-major, world
+ * direction = rot . head direction; n_rot = 0 (identity; rot is ignored), 1 (all frames) or n (one per frame).  Per channel the
+ * mean of the S x S bilinear samples, in fp64, stored as floor(mean + 0.5).
+ * Returns: n == 0 SAGEN_OK, nothing touched; a null argument SAGEN_ERR_NULL; SAGEN_ERR_SHAPE for n < 0, a frame dimension < 1, a
+ * rectangle outside its frame, a non-square face, an orientation outside 0..7, n_rot not in {0, 1, n}, hfov outside (0, pi);
+ * SAGEN_ERR_UNSUPPORTED for supersample outside 1..8, a dimension above 16384, n > 65535, an unknown kind, VIEW as a source.
+ * scratch: >= sagen_reproject_scratch_bytes(...) bytes (0 today: the kernel is fused; a null scratch is accepted then). */
+enum { SAGEN_PROJ_ER = 0, SAGEN_PROJ_CUBE = 1, SAGEN_PROJ_EAC = 2, SAGEN_PROJ_VIEW = 3 };
+typedef struct sagen_proj_face {
+    int32_t x0, y0, w, h;       /* rectangle of the frame, w == h */
+    int32_t orient;             /* 0..7 */
+} sagen_proj_face;
+typedef struct sagen_projection {
+    int32_t kind;               /* SAGEN_PROJ_* */
+    int32_t x0, y0, w, h;       /* ER / VIEW: rectangle of the frame (w = h = 0: all of it) */
+    double hfov;                /* VIEW: horizontal field of view, radians */
+    sagen_proj_face face[6];    /* CUBE / EAC */
+} sagen_projection;
+size_t sagen_reproject_scratch_bytes(int n, int dst_h, int dst_w, int supersample);
+int sagen_reproject(const uint8_t* src, int n, int src_h, int src_w, const sagen_projection* src_proj, uint8_t* dst, int dst_h, int dst_w,
+                    const sagen_projection* dst_proj, const double* rot, int n_rot, int supersample, void* scratch, size_t scratch_bytes,
+                    void* stream);
+
 /* ---- moving point sources: encode to ambisonics, binauralise, track ------------------------------------------------------
  * The front end of the reference's ambisonics toolbox: AmbiEncoder.encode / encode_frame / encode_v2 (pyutils/ambisonics/
  * encoder.py:10-55), SourceBinauralizer over VirtualStereoMic and Convolvotron, static and per frame (binauralizer.py:12-121), and

@@ -9,6 +9,7 @@ LIB_PATH = os.environ.get('SAGEN_LIB') or os.path.join(HERE, 'libsagen_hip.so') 
 SAGEN_ENC_AUDIO, SAGEN_ENC_VIDEO, SAGEN_ENC_FLOW = 1, 2, 4
 SAGEN_SEP_NONE, SAGEN_SEP_FREQ_MASK = 0, 1
 SAGEN_SOURCES_MIC, SAGEN_SOURCES_HRIR = 0, 1
+SAGEN_PROJ_ER, SAGEN_PROJ_CUBE, SAGEN_PROJ_EAC, SAGEN_PROJ_VIEW = 0, 1, 2, 3
 
 
 class SagenError(RuntimeError):
@@ -26,6 +27,15 @@ class SagenConfig(C.Structure):
 
 class SagenTensor(C.Structure):
     _fields_ = [('name', C.c_char_p), ('data', C.c_void_p), ('ndim', C.c_int32), ('shape', C.c_int64 * 4)]
+
+
+class SagenProjFace(C.Structure):
+    _fields_ = [('x0', C.c_int32), ('y0', C.c_int32), ('w', C.c_int32), ('h', C.c_int32), ('orient', C.c_int32)]
+
+
+class SagenProjection(C.Structure):
+    _fields_ = [('kind', C.c_int32), ('x0', C.c_int32), ('y0', C.c_int32), ('w', C.c_int32), ('h', C.c_int32), ('hfov', C.c_double),
+                ('face', SagenProjFace * 6)]
 
 
 # every symbol include/sagen.h declares: name -> (restype, argtypes)
@@ -87,6 +97,8 @@ SIGNATURES = {
     'sagen_power_map_windows': (C.c_int, [_P, _I64, _I, _I, _I64, _P, _I, _P, _P, _SZ, _P]),
     'sagen_overlay_blend_scratch_bytes': (_SZ, [_I] * 4),
     'sagen_overlay_blend': (C.c_int, [_P, _I, _I64, _I, _I, _P, _P, _I, _I64, _I, _I, _I, _P, _P, _SZ, _P]),
+    'sagen_reproject_scratch_bytes': (_SZ, [_I] * 4),
+    'sagen_reproject': (C.c_int, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _SZ, _P]),
     'sagen_source_track': (C.c_int, [_P, _P, _P, _P, _I, C.c_double, _I64, _I64, _I64, _P, _I, _P, _P, _P]),
     'sagen_encode_sources': (C.c_int, [_P, _I64, _P, _P, _P, _P, _I, C.c_double, _I, _I, C.c_double, _I64, _I64, _P, _P]),
     'sagen_binauralize_sources': (C.c_int, [_P, _I64, _P, _P, _P, _P, _I, C.c_double, _I, _P, _P, _I, _I, _I64, _I64, _I64, _P, _P]),

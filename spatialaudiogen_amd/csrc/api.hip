@@ -2,6 +2,7 @@
 // no exceptions across the boundary.
 #include "kernels.h"
 #include "emd_core.h"
+#include "project_core.h"
 #include <new>
 #include <cstdlib>
 #include <algorithm>
@@ -519,6 +520,29 @@ int sagen_overlay_blend(const float* maps, int n_maps, int64_t map0, int mh, int
     if (((uintptr_t)scratch) % 16 || ((uintptr_t)lut) % 8)
         return fail(SAGEN_ERR_SHAPE, "sagen_overlay_blend: scratch must be 16-byte aligned, lut 8-byte aligned");
     return overlay_blend_launch(maps, map0, mh, mw, lut, frames, n_frames, frame0, h, w, frames_per_map, out, scratch, (hipStream_t)stream);
+}
+
+size_t sagen_reproject_scratch_bytes(int n, int dst_h, int dst_w, int supersample) {
+    (void)n; (void)dst_h; (void)dst_w; (void)supersample;
+    return 0;                                          // the kernel is fused: nothing is staged between passes
+}
+
+int sagen_reproject(const uint8_t* src, int n, int src_h, int src_w, const sagen_projection* src_proj, uint8_t* dst, int dst_h, int dst_w,
+                    const sagen_projection* dst_proj, const double* rot, int n_rot, int supersample, void* scratch, size_t scratch_bytes,
+                    void* stream) {
+    (void)scratch; (void)scratch_bytes;
+    if (n < 0 || src_h <= 0 || src_w <= 0 || dst_h <= 0 || dst_w <= 0)
+        return fail(SAGEN_ERR_SHAPE, "sagen_reproject: n=%d source %dx%d destination %dx%d", n, src_h, src_w, dst_h, dst_w);
+    if (n == 0) return SAGEN_OK;
+    if (!src || !dst || !src_proj || !dst_proj || (n_rot != 0 && !rot)) return fail(SAGEN_ERR_NULL, "sagen_reproject: null argument");
+    ProjArgs a;
+    const char* why;
+    const int rc = proj_args_fill(a, n, src_h, src_w, src_proj, dst_h, dst_w, dst_proj, n_rot, supersample, &why);
+    if (rc != SAGEN_OK)
+        return fail(rc, "sagen_reproject: %s (n=%d n_rot=%d supersample=%d source %dx%d kind %d, destination %dx%d kind %d)", why, n, n_rot,
+                    supersample, src_h, src_w, src_proj->kind, dst_h, dst_w, dst_proj->kind);
+    if (n_rot != 0 && ((uintptr_t)rot) % 8) return fail(SAGEN_ERR_SHAPE, "sagen_reproject: rot must be 8-byte aligned");
+    return reproject_launch(src, dst, rot, a, (hipStream_t)stream);
 }
 
 int sagen_stft_loss_grad(const float* pred_yzx, const float* target_yzx, const float* mask, int batch, float* grad, double* loss,

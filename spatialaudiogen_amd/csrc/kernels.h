@@ -384,6 +384,13 @@ int overlay_blend_launch(const float* maps, long long map0, int mh, int mw, cons
                          long long frame0, int h, int w, int frames_per_map, uint8_t* out, void* scratch, hipStream_t s);
 
 // -----------------------------------------------------------------------------------------
+// reprojection of 360-degree frames (project.hip): sagen_reproject of include/sagen.h; ProjArgs is project_core.h's, checked and
+// filled by proj_args_fill
+// -----------------------------------------------------------------------------------------
+struct ProjArgs;
+int reproject_launch(const uint8_t* src, uint8_t* dst, const double* rot, const ProjArgs& a, hipStream_t s);
+
+// -----------------------------------------------------------------------------------------
 // training-step pieces (train.hip): stft loss + gradient w.r.t. the prediction, fused Adam over a flat bucket
 // -----------------------------------------------------------------------------------------
 int stft_loss_grad_launch(const float* pred, const float* gt, const float* mask, int B, float* grad, double* loss, hipStream_t s);

@@ -21,6 +21,7 @@
 #include "../../include/sagen.h"
 #include "../csrc/emd_core.h"
 #include "../csrc/sources_core.h"
+#include "../csrc/project_core.h"
 
 namespace {
 
@@ -604,6 +605,54 @@ int sagen_binauralize_sources(const float* signals, int64_t ld, const double* ct
         const bool z = h && t < zero_before;
         y[i * 2] = z ? 0.f : (float)acc[0];
         y[i * 2 + 1] = z ? 0.f : (float)acc[1];
+    }
+    return SAGEN_OK;
+}
+
+/* Reprojection of 360-degree frames (include/sagen.h: sagen_reproject; scraping/utils.py:91-144, preprocess.py:51-52, vrProjector's
+ * CubemapProjection.py:68-121): a loop per frame and destination pixel over the fp64 core the device uses (csrc/project_core.h) */
+extern "C++" {
+namespace {
+template <int SK, int DK>
+void reproject_frames(const uint8_t* src, uint8_t* dst, const double* rot, const sagen::ProjArgs& a) {
+    const size_t src_bytes = (size_t)a.src.fh * a.src.fw * 3, dst_bytes = (size_t)a.dst.fh * a.dst.fw * 3;
+    for (int fr = 0; fr < a.n; ++fr) {
+        const double* rp = a.n_rot == 0 ? nullptr : rot + (a.n_rot == 1 ? 0 : (size_t)fr * 9);
+        for (int py = 0; py < a.dst.fh; ++py)
+            for (int px = 0; px < a.dst.fw; ++px) {
+                int f, cx, cy, cw, ch;
+                if (!sagen::proj_dst_cell<DK>(a.dst, px, py, f, cx, cy, cw, ch)) continue;
+                sagen::proj_pixel<SK, DK>(a, src + fr * src_bytes, rp, f, cx, cy, cw, ch, dst + fr * dst_bytes + ((size_t)py * a.dst.fw + px) * 3);
+            }
+    }
+}
+template <int SK>
+void reproject_dst(const uint8_t* src, uint8_t* dst, const double* rot, const sagen::ProjArgs& a) {
+    switch (a.dst.kind) {
+        case SAGEN_PROJ_ER: reproject_frames<SK, SAGEN_PROJ_ER>(src, dst, rot, a); break;
+        case SAGEN_PROJ_CUBE: reproject_frames<SK, SAGEN_PROJ_CUBE>(src, dst, rot, a); break;
+        case SAGEN_PROJ_EAC: reproject_frames<SK, SAGEN_PROJ_EAC>(src, dst, rot, a); break;
+        default: reproject_frames<SK, SAGEN_PROJ_VIEW>(src, dst, rot, a); break;
+    }
+}
+}  // namespace
+}  // extern "C++"
+
+size_t sagen_reproject_scratch_bytes(int, int, int, int) { return 0; }
+
+int sagen_reproject(const uint8_t* src, int n, int src_h, int src_w, const sagen_projection* src_proj, uint8_t* dst, int dst_h, int dst_w,
+                    const sagen_projection* dst_proj, const double* rot, int n_rot, int supersample, void*, size_t, void*) {
+    if (n < 0 || src_h <= 0 || src_w <= 0 || dst_h <= 0 || dst_w <= 0) return fail(SAGEN_ERR_SHAPE, "sagen_reproject: bad sizes");
+    if (n == 0) return SAGEN_OK;
+    if (!src || !dst || !src_proj || !dst_proj || (n_rot != 0 && !rot)) return fail(SAGEN_ERR_NULL, "sagen_reproject: null argument");
+    sagen::ProjArgs a;
+    const char* why;
+    const int rc = sagen::proj_args_fill(a, n, src_h, src_w, src_proj, dst_h, dst_w, dst_proj, n_rot, supersample, &why);
+    if (rc != SAGEN_OK) return fail(rc, "sagen_reproject: %s", why);
+    switch (a.src.kind) {
+        case SAGEN_PROJ_ER: reproject_dst<SAGEN_PROJ_ER>(src, dst, rot, a); break;
+        case SAGEN_PROJ_CUBE: reproject_dst<SAGEN_PROJ_CUBE>(src, dst, rot, a); break;
+        default: reproject_dst<SAGEN_PROJ_EAC>(src, dst, rot, a); break;
     }
     return SAGEN_OK;
 }

@@ -198,6 +198,36 @@ def overlay_blend(maps, map0, lut, frames, frame0, frames_per_map):
     return out
 
 
+def reproject(frames, src_proj, dst_hw, dst_proj, rot=None, supersample=1, out=None):
+    """Reproject 360-degree frames (include/sagen.h: sagen_reproject; scraping/utils.py:91-144, preprocess.py:51-52 and vrProjector
+    in the reference): frames [n, h, w, 3] uint8, src_proj / dst_proj _lib.SagenProjection descriptors (project.py builds them),
+    dst_hw the destination frame's (height, width), rot None, [3, 3] or [n, 3, 3] float64 on the frames' device (world = rot . head)
+    -> [n, dst_h, dst_w, 3] uint8.  out: optional destination to write into (pixels outside the destination's rectangles keep
+    their bytes; a fresh destination starts at zero)."""
+    dev_ok = lambda t: isinstance(t, torch.Tensor) and t.is_cuda != _twin()
+    if not (dev_ok(frames) and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3):
+        raise TypeError('frames must be a [n, h, w, 3] uint8 tensor on %s' % ('the host (the CPU twin is loaded)' if _twin() else 'the device'))
+    frames = frames.contiguous()
+    n, h, w = frames.shape[:3]
+    dh, dw = int(dst_hw[0]), int(dst_hw[1])
+    n_rot = 0
+    if rot is not None:
+        if not (dev_ok(rot) and rot.dtype == torch.float64 and rot.device == frames.device and tuple(rot.shape[-2:]) == (3, 3) and rot.dim() in (2, 3)):
+            raise TypeError('rot must be a [3, 3] or [n, 3, 3] float64 tensor on the frames\' device')
+        rot = rot.contiguous()
+        n_rot = 1 if rot.dim() == 2 else rot.shape[0]
+    if out is None:
+        out = torch.zeros((n, dh, dw, 3), dtype=torch.uint8, device=frames.device)
+    elif not (out.dtype == torch.uint8 and out.device == frames.device and tuple(out.shape) == (n, dh, dw, 3) and out.is_contiguous()):
+        raise TypeError('out must be a contiguous uint8 tensor of shape %s on %s' % ((n, dh, dw, 3), frames.device))
+    l = _lib.lib()
+    nbytes = int(l.sagen_reproject_scratch_bytes(n, dh, dw, int(supersample)))
+    scratch = torch.empty((nbytes + 7) // 8, dtype=torch.float64, device=frames.device) if nbytes else None
+    check(l.sagen_reproject(_ptr(frames), n, h, w, C.addressof(src_proj), _ptr(out), dh, dw, C.addressof(dst_proj), _ptr(rot), n_rot,
+                            int(supersample), _ptr(scratch), nbytes, _stream()))
+    return out
+
+
 def eval_mel_env(pred, target):
     """myutils.compute_lsd_dist / compute_envelope_dist (myutils.py:96-116) per window: pred / target [B, 4800, C] ->
     (mel_lsd [B, C], env_mse [B, C])."""
