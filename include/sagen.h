@@ -203,6 +203,10 @@ int sagen_stft_mag(const float* audio, int batch, int n_samples, int f0, int f1,
  * zero-bordered 4-channel copy of the input).  Supported cin: a power of two >= 4; 3; or 1 with
  * padding VALID, kw % 4 == 0 and sw % 4 == 0 (the spectrogram conv). */
 size_t sagen_conv2d_scratch_bytes(int batch, int h, int w, int kh, int kw, int cin, int cout);
+/* The least scratch sagen_conv2d accepts: the repacked filter (and the 4-channel copy for cin == 3) without the room
+ * sagen_conv2d_scratch_bytes adds for the activation planes of a dense 3x3 stride-1 SAME conv with cin % 16 == 0 (the size callers
+ * allocated before those planes existed).  With less than sagen_conv2d_scratch_bytes such a conv runs on the fp32-activation kernels. */
+size_t sagen_conv2d_min_scratch_bytes(int batch, int h, int w, int kh, int kw, int cin, int cout);
 size_t sagen_bn_stats_floats(int batch, int hout, int wout, int cout);
 int sagen_conv2d(const float* x, int batch, int h, int w, int cin,
                  const float* w_hwio, int kh, int kw, int cout, int sh, int sw, int padding,
@@ -233,6 +237,21 @@ int sagen_deconv2d(const float* x, int batch, int h, int w, int cin,
                    const float* w_hwoi, int kh, int kw, int cout, int sh, int sw,
                    const float* bias, int relu, float* y,
                    void* scratch, size_t scratch_bytes, void* stream);
+
+/* Test accessors (host only, launch nothing): what sagen_conv2d / sagen_fc / sagen_deconv2d would run for these shapes, a scratch of
+ * scratch_bytes and these optional operands (has_* != 0: the pointer would be non-NULL), as "<tile name> splitk=S planes=0|1" -
+ * the instantiation name as sagen_tile_name spells it, the split-K factor (sagen_fc only; 1 elsewhere) and whether the plane
+ * pre-pass of the dense 3x3 stride-1 SAME convs runs first.  They share the descriptor construction and the tile choice with the
+ * ops themselves and return the op's own refusal for bad dimensions, unsupported channel counts and a short scratch, and
+ * SAGEN_ERR_UNSUPPORTED for a tile that cannot run the problem.  They do NOT repeat the checks the contraction's launcher makes
+ * after the filter has been packed - the prologue on a one-tap conv, a padded conv with more than 64 taps, the limit on the number of
+ * taps, operands beyond 2 GiB buffer addressing: for such arguments an accessor names a kernel although the op refuses the call.
+ * buf: >= 96 bytes. */
+int sagen_conv2d_kernel_name(int batch, int h, int w, int cin, int kh, int kw, int cout, int sh, int sw, int padding, int has_prologue,
+                             int has_stats, int has_bias, size_t scratch_bytes, char* buf, size_t buf_bytes);
+int sagen_fc_kernel_name(int m, int k, int n, int has_bias, size_t scratch_bytes, char* buf, size_t buf_bytes);
+int sagen_deconv2d_kernel_name(int batch, int h, int w, int cin, int kh, int kw, int cout, int sh, int sw, int has_bias,
+                               size_t scratch_bytes, char* buf, size_t buf_bytes);
 
 /* separation tail + decoder (model.py:326-347, myutils.istft myutils.py:181-211, model.py:421-434):
  * dmask  [B, 28, 1024, ntracks] : deconv1 output rows 43:71 (pre-sigmoid), NHWC

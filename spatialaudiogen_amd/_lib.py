@@ -70,6 +70,7 @@ SIGNATURES = {
     'sagen_profile_report': (C.c_int, [_P, C.c_char_p, _SZ]),
     'sagen_stft_mag': (C.c_int, [_P, _I, _I, _I, _I, _P, _I, _I, _P, _P]),
     'sagen_conv2d_scratch_bytes': (_SZ, [_I] * 7),
+    'sagen_conv2d_min_scratch_bytes': (_SZ, [_I] * 7),
     'sagen_bn_stats_floats': (_SZ, [_I] * 4),
     'sagen_conv2d': (C.c_int, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P, _P, _P, _SZ, _P]),
     'sagen_bn_finalize': (C.c_int, [_P, _I, _I, _I, _I, _P, _P, _F, _P, _P, _P]),
@@ -79,6 +80,9 @@ SIGNATURES = {
     'sagen_fc': (C.c_int, [_P, _I, _I, _P, _I, _P, _I, _P, _P, _SZ, _P]),
     'sagen_deconv2d_scratch_bytes': (_SZ, [_I] * 6),
     'sagen_deconv2d': (C.c_int, [_P, _I, _I, _I, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _SZ, _P]),
+    'sagen_conv2d_kernel_name': (C.c_int, [_I] * 13 + [_SZ, C.c_char_p, _SZ]),
+    'sagen_fc_kernel_name': (C.c_int, [_I] * 4 + [_SZ, C.c_char_p, _SZ]),
+    'sagen_deconv2d_kernel_name': (C.c_int, [_I] * 10 + [_SZ, C.c_char_p, _SZ]),
     'sagen_mask_istft_mix_scratch_bytes': (_SZ, [_I]),
     'sagen_mask_istft_mix': (C.c_int, [_P, _P, _P, _I, _I, _P, _P, _SZ, _P]),
     'sagen_mask_istft_mix_hoa_scratch_bytes': (_SZ, [_I, _I]),

@@ -184,9 +184,93 @@ size_t sagen_conv2d_scratch_bytes(int batch, int h, int w, int kh, int kw, int c
     return pk_bytes(cout, (long)kh * kw * cin) + planes;
 }
 
+/* the least sagen_conv2d accepts: the packed filter (+ the padded image for cin == 3), no room for activation planes */
+size_t sagen_conv2d_min_scratch_bytes(int batch, int h, int w, int kh, int kw, int cin, int cout) {
+    return cin == 3 ? sagen_conv2d_scratch_bytes(batch, h, w, kh, kw, cin, cout) : pk_bytes(cout, (long)kh * kw * (cin == 1 ? 1 : cin));
+}
+
 size_t sagen_bn_stats_floats(int batch, int hout, int wout, int cout) {
     (void)batch; (void)hout; (void)wout;
     return (size_t)4 * cout;                  // two fp64 accumulators per channel
+}
+
+/* ---- forward, op level: each op's descriptor construction and tile choice sit in ONE function, which the op and its test accessor
+ *      (sagen_*_kernel_name: host only) both call.  The functions look at no operand: the accessors pass a stand-in for every pointer. ---- */
+struct ConvOp {
+    IgemmDesc d;                                        // the problem igemm_launch gets (with the planes where `planes`)
+    IgemmTile tile = TILE_AUTO;
+    bool planes = false;                                // conv3p.hip: the elementwise pre-pass writes the bf16 planes first
+    int pt = 0, pb = 0, pl = 0, pr = 0;
+    int pack_taps = 0, pack_cin = 0, pack_cpad = 0;     // pack_conv_launch(w_hwio, taps, cin, cin padded, ...)
+    float* xpad = nullptr;                              // cin == 3: the padded 4-channel image, behind the packed filter
+};
+
+static int conv2d_op(ConvOp& o, const float* x, int batch, int h, int w, int cin, int kh, int kw, int cout, int sh, int sw, int padding,
+                     const float* bias, int relu, const float* in_scale, const float* in_shift, float* y, float* bn_stats, void* scratch,
+                     size_t scratch_bytes) {
+    if (batch <= 0 || h <= 0 || w <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || cout <= 0)
+        return fail(SAGEN_ERR_SHAPE, "sagen_conv2d: bad dimensions");
+    if ((in_scale == nullptr) != (in_shift == nullptr)) return fail(SAGEN_ERR_NULL, "sagen_conv2d: in_scale/in_shift must come together");
+    if (scratch_bytes < sagen_conv2d_min_scratch_bytes(batch, h, w, kh, kw, cin, cout)) return fail(SAGEN_ERR_WORKSPACE, "sagen_conv2d: scratch too small");
+    const bool room_for_planes = scratch_bytes >= sagen_conv2d_scratch_bytes(batch, h, w, kh, kw, cin, cout);
+    int Hout, Wout;
+    int& pt = o.pt; int& pb = o.pb; int& pl = o.pl; int& pr = o.pr;
+    if (padding == 1) {
+        Hout = cdiv(h, sh); Wout = cdiv(w, sw);
+        const int th = std::max((Hout - 1) * sh + kh - h, 0), tw = std::max((Wout - 1) * sw + kw - w, 0);
+        pt = th / 2; pb = th - pt; pl = tw / 2; pr = tw - pl;
+    } else if (padding == 0) {
+        if (h < kh || w < kw) return fail(SAGEN_ERR_SHAPE, "sagen_conv2d: VALID conv larger than input");
+        Hout = (h - kh) / sh + 1; Wout = (w - kw) / sw + 1;
+    } else {
+        return fail(SAGEN_ERR_SHAPE, "sagen_conv2d: padding must be 0 (VALID) or 1 (SAME)");
+    }
+    float* wp = (float*)scratch;
+    IgemmDesc& d = o.d;
+    d.y = y; d.bias = bias; d.relu_out = relu; d.in_scale = in_scale; d.in_shift = in_shift; d.stats = (double*)bn_stats;
+    d.M = batch * Hout * Wout; d.N = cout; d.Cout = cout;
+    d.Hg = Hout; d.Wg = Wout; d.Hlim = Hout; d.Wlim = Wout;
+    d.ldy = cout; d.y_rstride = (long)Wout * cout; d.y_bstride = (long)Hout * Wout * cout;
+    d.in_sh = sh; d.in_sw = sw; d.w = wp;
+    if (cin == 1) {
+        if (padding != 0 || kw % 4 || sw % 4 || in_scale)
+            return fail(SAGEN_ERR_UNSUPPORTED, "sagen_conv2d: cin=1 needs VALID padding, kw%%4==0, sw%%4==0, no input BN");
+        d.x = x; d.Hin = h; d.Win = w; d.Cin = kw; d.ldx = 1; d.x_bstride = (long)h * w;
+        d.ntaps = kh; d.TW = 1; d.tap_sh = 1; d.tap_sw = 0; d.log2Cin = ilog2_exact(kw);
+        if (kh > 1 && d.log2Cin < 0) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_conv2d: cin=1 needs power-of-two kw");
+        d.K = kh * kw; d.Kpad = (d.K + 15) / 16 * 16;
+        o.pack_taps = kh; o.pack_cin = kw; o.pack_cpad = kw;
+    } else if (cin == 3) {
+        if (in_scale) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_conv2d: cin=3 does not take an input BN");
+        o.xpad = (float*)((char*)scratch + pk_bytes(cout, (long)kh * kw * 4));
+        d.x = o.xpad; d.Hin = h + pt + pb; d.Win = w + pl + pr; d.Cin = 4; d.ldx = 4; d.x_bstride = (long)d.Hin * d.Win * 4;
+        d.ntaps = kh * kw; d.TW = kw; d.log2Cin = 2;
+        d.K = kh * kw * 4; d.Kpad = (d.K + 15) / 16 * 16;
+        o.pack_taps = kh * kw; o.pack_cin = 3; o.pack_cpad = 4;
+    } else {
+        if (cin % 4 || (kh * kw > 1 && ilog2_exact(cin) < 2))
+            return fail(SAGEN_ERR_UNSUPPORTED, "sagen_conv2d: cin=%d (supported: 1, 3, powers of two >= 4; any multiple of 4 for 1x1)", cin);
+        d.x = x; d.Hin = h; d.Win = w; d.Cin = cin; d.ldx = cin; d.x_bstride = (long)h * w * cin;
+        d.ntaps = kh * kw; d.TW = kw; d.tap_h0 = -pt; d.tap_w0 = -pl; d.log2Cin = ilog2_exact(cin);
+        d.K = kh * kw * cin; d.Kpad = (d.K + 15) / 16 * 16;
+        o.pack_taps = kh * kw; o.pack_cin = cin; o.pack_cpad = cin;
+    }
+    d.w_split = 1;                                      // (the op runs pack_split_launch behind pack_conv_launch)
+    static const bool no_p3 = getenv("SAGEN_NO_P3") != nullptr || getenv("SAGEN_FP32_ONLY") != nullptr;
+    if (!no_p3 && room_for_planes && sh == 1 && sw == 1 && padding == 1 && cin % 16 == 0 && igemm_p3_eligible(d) &&
+        p3_bytes(batch, h, w, cin) < (1UL << 31)) {
+        // dense 3x3 stride-1 SAME: one elementwise pass applies the input BN+ReLU (if any) and writes the three bf16
+        // planes; the contraction then runs LDS-DMA -> MFMA only (conv3p.hip)
+        IgemmDesc e = d;
+        igemm_set_p3_planes(e, (char*)scratch + pk_bytes(cout, (long)kh * kw * cin), batch, h, w, cin);
+        const IgemmTile t = igemm_pick_tile(e);
+        if (igemm_tile_p3(t)) {
+            d = e; o.tile = t; o.planes = true;
+            return SAGEN_OK;
+        }
+    }
+    o.tile = igemm_pick_tile(d);
+    return SAGEN_OK;
 }
 
 int sagen_conv2d(const float* x, int batch, int h, int w, int cin, const float* w_hwio, int kh, int kw, int cout, int sh,
@@ -195,75 +279,42 @@ int sagen_conv2d(const float* x, int batch, int h, int w, int cin, const float* 
     return guarded([&]() -> int {
         hipStream_t s = (hipStream_t)stream;
         if (!x || !w_hwio || !y || !scratch) return fail(SAGEN_ERR_NULL, "sagen_conv2d: null argument");
-        if (batch <= 0 || h <= 0 || w <= 0 || kh <= 0 || kw <= 0 || sh <= 0 || sw <= 0 || cout <= 0)
-            return fail(SAGEN_ERR_SHAPE, "sagen_conv2d: bad dimensions");
-        if ((in_scale == nullptr) != (in_shift == nullptr)) return fail(SAGEN_ERR_NULL, "sagen_conv2d: in_scale/in_shift must come together");
-        const size_t need_min = cin == 3 ? sagen_conv2d_scratch_bytes(batch, h, w, kh, kw, cin, cout) : pk_bytes(cout, (long)kh * kw * (cin == 1 ? 1 : cin));
-        if (scratch_bytes < need_min) return fail(SAGEN_ERR_WORKSPACE, "sagen_conv2d: scratch too small");
-        const bool room_for_planes = scratch_bytes >= sagen_conv2d_scratch_bytes(batch, h, w, kh, kw, cin, cout);
-        int Hout, Wout, pt = 0, pb = 0, pl = 0, pr = 0;
-        if (padding == 1) {
-            Hout = cdiv(h, sh); Wout = cdiv(w, sw);
-            const int th = std::max((Hout - 1) * sh + kh - h, 0), tw = std::max((Wout - 1) * sw + kw - w, 0);
-            pt = th / 2; pb = th - pt; pl = tw / 2; pr = tw - pl;
-        } else if (padding == 0) {
-            if (h < kh || w < kw) return fail(SAGEN_ERR_SHAPE, "sagen_conv2d: VALID conv larger than input");
-            Hout = (h - kh) / sh + 1; Wout = (w - kw) / sw + 1;
-        } else {
-            return fail(SAGEN_ERR_SHAPE, "sagen_conv2d: padding must be 0 (VALID) or 1 (SAME)");
-        }
-        float* wp = (float*)scratch;
-        IgemmDesc d;
-        d.y = y; d.bias = bias; d.relu_out = relu; d.in_scale = in_scale; d.in_shift = in_shift; d.stats = (double*)bn_stats;
-        d.M = batch * Hout * Wout; d.N = cout; d.Cout = cout;
-        d.Hg = Hout; d.Wg = Wout; d.Hlim = Hout; d.Wlim = Wout;
-        d.ldy = cout; d.y_rstride = (long)Wout * cout; d.y_bstride = (long)Hout * Wout * cout;
-        d.in_sh = sh; d.in_sw = sw; d.w = wp;
-        int rc;
-        if (cin == 1) {
-            if (padding != 0 || kw % 4 || sw % 4 || in_scale)
-                return fail(SAGEN_ERR_UNSUPPORTED, "sagen_conv2d: cin=1 needs VALID padding, kw%%4==0, sw%%4==0, no input BN");
-            d.x = x; d.Hin = h; d.Win = w; d.Cin = kw; d.ldx = 1; d.x_bstride = (long)h * w;
-            d.ntaps = kh; d.TW = 1; d.tap_sh = 1; d.tap_sw = 0; d.log2Cin = ilog2_exact(kw);
-            if (kh > 1 && d.log2Cin < 0) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_conv2d: cin=1 needs power-of-two kw");
-            d.K = kh * kw; d.Kpad = (d.K + 15) / 16 * 16;
-            rc = pack_conv_launch(w_hwio, kh, kw, kw, cout, wp, cout, d.Kpad, s);
-        } else if (cin == 3) {
-            if (in_scale) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_conv2d: cin=3 does not take an input BN");
-            float* xp = (float*)((char*)scratch + pk_bytes(cout, (long)kh * kw * 4));
-            rc = pad_nhwc3to4_launch(x, xp, batch, h, w, pt, pb, pl, pr, s);
-            if (rc) return rc;
-            d.x = xp; d.Hin = h + pt + pb; d.Win = w + pl + pr; d.Cin = 4; d.ldx = 4; d.x_bstride = (long)d.Hin * d.Win * 4;
-            d.ntaps = kh * kw; d.TW = kw; d.log2Cin = 2;
-            d.K = kh * kw * 4; d.Kpad = (d.K + 15) / 16 * 16;
-            rc = pack_conv_launch(w_hwio, kh * kw, 3, 4, cout, wp, cout, d.Kpad, s);
-        } else {
-            if (cin % 4 || (kh * kw > 1 && ilog2_exact(cin) < 2))
-                return fail(SAGEN_ERR_UNSUPPORTED, "sagen_conv2d: cin=%d (supported: 1, 3, powers of two >= 4; any multiple of 4 for 1x1)", cin);
-            d.x = x; d.Hin = h; d.Win = w; d.Cin = cin; d.ldx = cin; d.x_bstride = (long)h * w * cin;
-            d.ntaps = kh * kw; d.TW = kw; d.tap_h0 = -pt; d.tap_w0 = -pl; d.log2Cin = ilog2_exact(cin);
-            d.K = kh * kw * cin; d.Kpad = (d.K + 15) / 16 * 16;
-            rc = pack_conv_launch(w_hwio, kh * kw, cin, cin, cout, wp, cout, d.Kpad, s);
-        }
-        if (!rc) rc = pack_split_launch(wp, cout, d.Kpad, s);
+        ConvOp o;
+        int rc = conv2d_op(o, x, batch, h, w, cin, kh, kw, cout, sh, sw, padding, bias, relu, in_scale, in_shift, y, bn_stats, scratch, scratch_bytes);
         if (rc) return rc;
-        d.w_split = 1;
-        if (bn_stats) SAGEN_HIP_CHECK(hipMemsetAsync(bn_stats, 0, (size_t)2 * cout * sizeof(double), s));
-        static const bool no_p3 = getenv("SAGEN_NO_P3") != nullptr || getenv("SAGEN_FP32_ONLY") != nullptr;
-        if (!no_p3 && room_for_planes && sh == 1 && sw == 1 && padding == 1 && cin % 16 == 0 && igemm_p3_eligible(d) &&
-            p3_bytes(batch, h, w, cin) < (1UL << 31)) {
-            // dense 3x3 stride-1 SAME: one elementwise pass applies the input BN+ReLU (if any) and writes the three bf16
-            // planes; the contraction then runs LDS-DMA -> MFMA only (conv3p.hip)
-            IgemmDesc e = d;
-            igemm_set_p3_planes(e, (char*)scratch + pk_bytes(cout, (long)kh * kw * cin), batch, h, w, cin);
-            const IgemmTile t = igemm_pick_tile(e);
-            if (igemm_tile_p3(t)) {
-                rc = p3_pack_launch(x, in_scale, in_shift, BnRef(), nullptr, in_scale ? 1 : 0, nullptr, (void*)e.xp3, batch, h, w, cin, s);
-                if (rc) return rc;
-                return igemm_launch(e, t, s);
-            }
+        const IgemmDesc& d = o.d;
+        if (o.xpad) {
+            rc = pad_nhwc3to4_launch(x, o.xpad, batch, h, w, o.pt, o.pb, o.pl, o.pr, s);
+            if (rc) return rc;
         }
-        return igemm_launch(d, TILE_AUTO, s);
+        rc = pack_conv_launch(w_hwio, o.pack_taps, o.pack_cin, o.pack_cpad, cout, (float*)scratch, cout, d.Kpad, s);
+        if (!rc) rc = pack_split_launch((float*)scratch, cout, d.Kpad, s);
+        if (rc) return rc;
+        if (bn_stats) SAGEN_HIP_CHECK(hipMemsetAsync(bn_stats, 0, (size_t)2 * cout * sizeof(double), s));
+        if (o.planes) {
+            rc = p3_pack_launch(x, in_scale, in_shift, BnRef(), nullptr, in_scale ? 1 : 0, nullptr, (void*)d.xp3, batch, h, w, cin, s);
+            if (rc) return rc;
+        }
+        return igemm_launch(d, o.tile, s);
+    });
+}
+
+/* host only: a stand-in for the operands (never dereferenced), the description "<tile name> splitk=S planes=0|1" */
+static int describe_op(const char* fn, const IgemmDesc& d, IgemmTile tile, int splitk, bool planes, char* buf, size_t buf_bytes) {
+    if (!igemm_tile_ok(d, tile)) return fail(SAGEN_ERR_UNSUPPORTED, "%s: %s cannot run this problem (Kpad=%d Cin=%d)", fn, igemm_tile_name(tile), d.Kpad, d.Cin);
+    snprintf(buf, buf_bytes, "%s splitk=%d planes=%d", igemm_tile_name(tile), splitk, planes ? 1 : 0);
+    return SAGEN_OK;
+}
+
+int sagen_conv2d_kernel_name(int batch, int h, int w, int cin, int kh, int kw, int cout, int sh, int sw, int padding, int has_prologue,
+                             int has_stats, int has_bias, size_t scratch_bytes, char* buf, size_t buf_bytes) {
+    return guarded([&]() -> int {
+        if (!buf || buf_bytes < 96) return fail(SAGEN_ERR_NULL, "sagen_conv2d_kernel_name: buffer of >= 96 bytes needed");
+        float* p = (float*)buf;
+        ConvOp o;
+        const int rc = conv2d_op(o, p, batch, h, w, cin, kh, kw, cout, sh, sw, padding, has_bias ? p : nullptr, 0, has_prologue ? p : nullptr,
+                                 has_prologue ? p : nullptr, p, has_stats ? p : nullptr, buf, scratch_bytes);
+        return rc ? rc : describe_op("sagen_conv2d_kernel_name", o.d, o.tile, 1, o.planes, buf, buf_bytes);
     });
 }
 
@@ -294,32 +345,55 @@ size_t sagen_fc_scratch_bytes(int m, int k, int n) {
     return pk_bytes(n, k) + align_up((size_t)64 * m * n * sizeof(float), 256);
 }
 
+struct FcOp {
+    IgemmDesc d;
+    IgemmTile tile = TILE_AUTO;
+    int splitk = 1;                                     // > 1: partial sums into the workspace, bias + ReLU in splitk_reduce_launch
+    float* ws = nullptr;
+};
+
+static int fc_op(FcOp& o, const float* x, int m, int k, int n, const float* bias, int relu, float* y, void* scratch, size_t scratch_bytes) {
+    if (m <= 0 || k <= 0 || n <= 0 || k % 4) return fail(SAGEN_ERR_SHAPE, "sagen_fc: bad sizes (k must be a multiple of 4)");
+    if (scratch_bytes < sagen_fc_scratch_bytes(m, k, n)) return fail(SAGEN_ERR_WORKSPACE, "sagen_fc: scratch too small");
+    o.ws = (float*)((char*)scratch + pk_bytes(n, k));
+    IgemmDesc& d = o.d;
+    d.x = x; d.w = (float*)scratch; d.y = y;
+    d.M = m; d.N = n; d.K = k; d.Kpad = (k + 15) / 16 * 16; d.Cin = k; d.ldx = k; d.x_bstride = k;
+    d.Cout = n; d.ldy = n; d.y_rstride = n; d.y_bstride = n;
+    // low-parallelism rows: split K so the weight stream is spread over the chip
+    o.tile = igemm_pick_tile(d);
+    o.splitk = igemm_auto_splitk(d, o.tile);
+    if (o.splitk > 1) {
+        d.splitk = o.splitk; d.splitk_ws = o.ws;
+    } else {
+        d.bias = bias; d.relu_out = relu;
+    }
+    return SAGEN_OK;
+}
+
 int sagen_fc(const float* x, int m, int k, const float* w_kn, int n, const float* bias, int relu, float* y, void* scratch,
              size_t scratch_bytes, void* stream) {
     return guarded([&]() -> int {
         hipStream_t s = (hipStream_t)stream;
         if (!x || !w_kn || !y || !scratch) return fail(SAGEN_ERR_NULL, "sagen_fc: null argument");
-        if (m <= 0 || k <= 0 || n <= 0 || k % 4) return fail(SAGEN_ERR_SHAPE, "sagen_fc: bad sizes (k must be a multiple of 4)");
-        if (scratch_bytes < sagen_fc_scratch_bytes(m, k, n)) return fail(SAGEN_ERR_WORKSPACE, "sagen_fc: scratch too small");
-        float* wp = (float*)scratch;
-        float* ws = (float*)((char*)scratch + pk_bytes(n, k));
-        IgemmDesc d;
-        d.x = x; d.w = wp; d.y = y;
-        d.M = m; d.N = n; d.K = k; d.Kpad = (k + 15) / 16 * 16; d.Cin = k; d.ldx = k; d.x_bstride = k;
-        d.Cout = n; d.ldy = n; d.y_rstride = n; d.y_bstride = n;
-        int rc = pack_conv_launch(w_kn, 1, k, k, n, wp, n, d.Kpad, s);
+        FcOp o;
+        int rc = fc_op(o, x, m, k, n, bias, relu, y, scratch, scratch_bytes);
         if (rc) return rc;
-        // low-parallelism rows: split K so the weight stream is spread over the chip
-        IgemmTile tile = igemm_pick_tile(d);
-        const int sk = igemm_auto_splitk(d, tile);
-        if (sk > 1) {
-            d.splitk = sk; d.splitk_ws = ws;
-            rc = igemm_launch(d, tile, s);
-            if (rc) return rc;
-            return splitk_reduce_launch(ws, sk, m, n, bias, relu, y, n, 1, nullptr, s);
-        }
-        d.bias = bias; d.relu_out = relu;
-        return igemm_launch(d, tile, s);
+        rc = pack_conv_launch(w_kn, 1, k, k, n, (float*)scratch, n, o.d.Kpad, s);
+        if (rc) return rc;
+        rc = igemm_launch(o.d, o.tile, s);
+        if (rc || o.splitk == 1) return rc;
+        return splitk_reduce_launch(o.ws, o.splitk, m, n, bias, relu, y, n, 1, nullptr, s);
+    });
+}
+
+int sagen_fc_kernel_name(int m, int k, int n, int has_bias, size_t scratch_bytes, char* buf, size_t buf_bytes) {
+    return guarded([&]() -> int {
+        if (!buf || buf_bytes < 96) return fail(SAGEN_ERR_NULL, "sagen_fc_kernel_name: buffer of >= 96 bytes needed");
+        float* p = (float*)buf;
+        FcOp o;
+        const int rc = fc_op(o, p, m, k, n, has_bias ? p : nullptr, 0, p, buf, scratch_bytes);
+        return rc ? rc : describe_op("sagen_fc_kernel_name", o.d, o.tile, o.splitk, false, buf, buf_bytes);
     });
 }
 
@@ -327,31 +401,56 @@ size_t sagen_deconv2d_scratch_bytes(int kh, int kw, int cin, int cout, int sh, i
     return pk_bytes((long)sh * sw * cout, (long)cdiv(kh, sh) * cdiv(kw, sw) * cin);
 }
 
+struct DeconvOp {
+    IgemmDesc d;
+    IgemmTile tile = TILE_AUTO;
+};
+
+static int deconv2d_op(DeconvOp& o, const float* x, int batch, int h, int w, int cin, int kh, int kw, int cout, int sh, int sw, const float* bias,
+                       int relu, float* y, void* scratch, size_t scratch_bytes) {
+    if (batch <= 0 || h <= 0 || w <= 0 || kh < sh || kw < sw || sh <= 0 || sw <= 0 || cout <= 0)
+        return fail(SAGEN_ERR_SHAPE, "sagen_deconv2d: bad dimensions (kernel must be >= stride)");
+    if (ilog2_exact(cin) < 2) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_deconv2d: cin=%d must be a power of two >= 4", cin);
+    if (scratch_bytes < sagen_deconv2d_scratch_bytes(kh, kw, cin, cout, sh, sw))
+        return fail(SAGEN_ERR_WORKSPACE, "sagen_deconv2d: scratch too small");
+    const int Hout = h * sh + kh - sh, Wout = w * sw + kw - sw;
+    const int nth = cdiv(kh, sh), ntw = cdiv(kw, sw);
+    IgemmDesc& d = o.d;
+    d.x = x; d.w = (float*)scratch; d.y = y; d.bias = bias; d.relu_out = relu;
+    d.Hg = cdiv(Hout, sh); d.Wg = cdiv(Wout, sw);
+    d.M = batch * d.Hg * d.Wg; d.N = sh * sw * cout; d.K = nth * ntw * cin; d.Kpad = (d.K + 15) / 16 * 16;
+    d.Hin = h; d.Win = w; d.Cin = cin; d.ldx = cin; d.x_bstride = (long)h * w * cin;
+    d.ntaps = nth * ntw; d.TW = ntw; d.tap_sh = -1; d.tap_sw = -1; d.log2Cin = ilog2_exact(cin);
+    d.dsh = sh; d.dsw = sw; d.Cout = cout; d.Hlim = Hout; d.Wlim = Wout;
+    d.ldy = cout; d.y_rstride = (long)Wout * cout; d.y_bstride = (long)Hout * Wout * cout;
+    d.w_split = 1;                                      // (the op runs pack_split_launch behind pack_deconv_launch)
+    o.tile = igemm_pick_tile(d);
+    return SAGEN_OK;
+}
+
 int sagen_deconv2d(const float* x, int batch, int h, int w, int cin, const float* w_hwoi, int kh, int kw, int cout, int sh,
                    int sw, const float* bias, int relu, float* y, void* scratch, size_t scratch_bytes, void* stream) {
     return guarded([&]() -> int {
         hipStream_t s = (hipStream_t)stream;
         if (!x || !w_hwoi || !y || !scratch) return fail(SAGEN_ERR_NULL, "sagen_deconv2d: null argument");
-        if (batch <= 0 || h <= 0 || w <= 0 || kh < sh || kw < sw || sh <= 0 || sw <= 0 || cout <= 0)
-            return fail(SAGEN_ERR_SHAPE, "sagen_deconv2d: bad dimensions (kernel must be >= stride)");
-        if (ilog2_exact(cin) < 2) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_deconv2d: cin=%d must be a power of two >= 4", cin);
-        if (scratch_bytes < sagen_deconv2d_scratch_bytes(kh, kw, cin, cout, sh, sw))
-            return fail(SAGEN_ERR_WORKSPACE, "sagen_deconv2d: scratch too small");
-        const int Hout = h * sh + kh - sh, Wout = w * sw + kw - sw;
-        const int nth = cdiv(kh, sh), ntw = cdiv(kw, sw);
-        IgemmDesc d;
-        d.x = x; d.w = (float*)scratch; d.y = y; d.bias = bias; d.relu_out = relu;
-        d.Hg = cdiv(Hout, sh); d.Wg = cdiv(Wout, sw);
-        d.M = batch * d.Hg * d.Wg; d.N = sh * sw * cout; d.K = nth * ntw * cin; d.Kpad = (d.K + 15) / 16 * 16;
-        d.Hin = h; d.Win = w; d.Cin = cin; d.ldx = cin; d.x_bstride = (long)h * w * cin;
-        d.ntaps = nth * ntw; d.TW = ntw; d.tap_sh = -1; d.tap_sw = -1; d.log2Cin = ilog2_exact(cin);
-        d.dsh = sh; d.dsw = sw; d.Cout = cout; d.Hlim = Hout; d.Wlim = Wout;
-        d.ldy = cout; d.y_rstride = (long)Wout * cout; d.y_bstride = (long)Hout * Wout * cout;
-        int rc = pack_deconv_launch(w_hwoi, kh, kw, cout, cin, sh, sw, (float*)scratch, d.N, d.Kpad, s);
-        if (!rc) rc = pack_split_launch((float*)scratch, d.N, d.Kpad, s);
+        DeconvOp o;
+        int rc = deconv2d_op(o, x, batch, h, w, cin, kh, kw, cout, sh, sw, bias, relu, y, scratch, scratch_bytes);
         if (rc) return rc;
-        d.w_split = 1;
-        return igemm_launch(d, TILE_AUTO, s);
+        rc = pack_deconv_launch(w_hwoi, kh, kw, cout, cin, sh, sw, (float*)scratch, o.d.N, o.d.Kpad, s);
+        if (!rc) rc = pack_split_launch((float*)scratch, o.d.N, o.d.Kpad, s);
+        if (rc) return rc;
+        return igemm_launch(o.d, o.tile, s);
+    });
+}
+
+int sagen_deconv2d_kernel_name(int batch, int h, int w, int cin, int kh, int kw, int cout, int sh, int sw, int has_bias, size_t scratch_bytes,
+                               char* buf, size_t buf_bytes) {
+    return guarded([&]() -> int {
+        if (!buf || buf_bytes < 96) return fail(SAGEN_ERR_NULL, "sagen_deconv2d_kernel_name: buffer of >= 96 bytes needed");
+        float* p = (float*)buf;
+        DeconvOp o;
+        const int rc = deconv2d_op(o, p, batch, h, w, cin, kh, kw, cout, sh, sw, has_bias ? p : nullptr, 0, p, buf, scratch_bytes);
+        return rc ? rc : describe_op("sagen_deconv2d_kernel_name", o.d, o.tile, 1, false, buf, buf_bytes);
     });
 }
 

@@ -51,9 +51,11 @@ def stft_mag(audio, f0, f1, c0=None, c1=None):
 
 
 def conv_2d(x, weights, stride=1, padding='SAME', biases=None, relu=False, in_scale=None, in_shift=None,
-            return_bn_stats=False):
+            return_bn_stats=False, out=None, stats_out=None, planes_scratch=True):
     """tfw.conv_2d minus batch-norm (core.py:156-220).  x [B,H,W,Cin]; weights HWIO.
-    With return_bn_stats the raw-output statistics for training-mode BN come back too."""
+    With return_bn_stats the raw-output statistics for training-mode BN come back too.  out / stats_out: optional tensors to write
+    into ([B,Ho,Wo,cout] float32, [2*cout] float64).  planes_scratch=False: a scratch of the size callers allocated before the
+    activation planes existed (the packed filter alone) - the library then runs the fp32-activation kernels."""
     x, weights = _f32(x, 'x'), _f32(weights, 'weights')
     B, H, W, Cin = x.shape
     kh, kw, cin2, cout = weights.shape
@@ -65,14 +67,31 @@ def conv_2d(x, weights, stride=1, padding='SAME', biases=None, relu=False, in_sc
     else:
         Ho, Wo = (H - kh) // sh + 1, (W - kw) // sw + 1
     l = _lib.lib()
-    y = torch.empty(B, Ho, Wo, cout, dtype=torch.float32, device=x.device)
-    scratch = _scratch(l.sagen_conv2d_scratch_bytes(B, H, W, kh, kw, Cin, cout), x.device)
+    y = _out(out, (B, Ho, Wo, cout), x, 'out')
+    scratch = _scratch(conv_2d_scratch_bytes(B, H, W, kh, kw, Cin, cout, planes_scratch), x.device)
     stats = None
+    if stats_out is not None and not return_bn_stats:
+        raise ValueError('stats_out needs return_bn_stats=True')
     if return_bn_stats:
-        stats = torch.zeros(int(l.sagen_bn_stats_floats(B, Ho, Wo, cout)) // 2, dtype=torch.float64, device=x.device)
+        n_stats = int(l.sagen_bn_stats_floats(B, Ho, Wo, cout)) // 2
+        if stats_out is None:
+            stats = torch.zeros(n_stats, dtype=torch.float64, device=x.device)
+        elif not (stats_out.dtype == torch.float64 and stats_out.device == x.device and tuple(stats_out.shape) == (n_stats,) and stats_out.is_contiguous()):
+            raise TypeError('stats_out must be a contiguous float64 tensor of shape (%d,) on %s' % (n_stats, x.device))
+        else:
+            stats = stats_out
     check(l.sagen_conv2d(_ptr(x), B, H, W, Cin, _ptr(weights), kh, kw, cout, sh, sw, pad, _ptr(biases), int(relu),
                          _ptr(in_scale), _ptr(in_shift), _ptr(y), _ptr(stats), _ptr(scratch), scratch.numel() * 4, _stream()))
     return (y, stats) if return_bn_stats else y
+
+
+def conv_2d_scratch_bytes(B, H, W, kh, kw, Cin, cout, planes=True):
+    """The scratch conv_2d allocates: sagen_conv2d_scratch_bytes, or with planes=False sagen_conv2d_min_scratch_bytes - the packed
+    filter alone, the size from before the activation planes, which sagen_conv2d still accepts (include/sagen.h)."""
+    l = _lib.lib()
+    if planes or _twin():
+        return int(l.sagen_conv2d_scratch_bytes(B, H, W, kh, kw, Cin, cout))
+    return int(l.sagen_conv2d_min_scratch_bytes(B, H, W, kh, kw, Cin, cout))
 
 
 def bn_finalize(stats, shape, gamma, beta, eps=1e-3):
@@ -101,27 +120,27 @@ def maxpool3x3s2(x, scale=None, shift=None):
     return y
 
 
-def fully_connected(x, weights, biases=None, relu=False):
-    """tfw.fully_connected (core.py:43-93): acts on the last axis."""
+def fully_connected(x, weights, biases=None, relu=False, out=None):
+    """tfw.fully_connected (core.py:43-93): acts on the last axis.  out: optional tensor to write into."""
     x, weights = _f32(x, 'x'), _f32(weights, 'weights')
     K, N = weights.shape
     M = x.numel() // K
     l = _lib.lib()
-    y = torch.empty(x.shape[:-1] + (N,), dtype=torch.float32, device=x.device)
+    y = _out(out, tuple(x.shape[:-1]) + (N,), x, 'out')
     scratch = _scratch(l.sagen_fc_scratch_bytes(M, K, N), x.device)
     check(l.sagen_fc(_ptr(x), M, K, _ptr(weights), N, _ptr(biases), int(relu), _ptr(y), _ptr(scratch), scratch.numel() * 4, _stream()))
     return y
 
 
-def deconv_2d(x, weights, stride, biases=None, relu=False):
-    """tfw.deconv_2d (core.py:96-153), VALID.  weights [kh,kw,Cout,Cin]."""
+def deconv_2d(x, weights, stride, biases=None, relu=False, out=None):
+    """tfw.deconv_2d (core.py:96-153), VALID.  weights [kh,kw,Cout,Cin].  out: optional tensor to write into."""
     x, weights = _f32(x, 'x'), _f32(weights, 'weights')
     B, H, W, Cin = x.shape
     kh, kw, cout, cin2 = weights.shape
     assert cin2 == Cin
     sh, sw = stride
     l = _lib.lib()
-    y = torch.empty(B, H * sh + kh - sh, W * sw + kw - sw, cout, dtype=torch.float32, device=x.device)
+    y = _out(out, (B, H * sh + kh - sh, W * sw + kw - sw, cout), x, 'out')
     scratch = _scratch(l.sagen_deconv2d_scratch_bytes(kh, kw, Cin, cout, sh, sw), x.device)
     check(l.sagen_deconv2d(_ptr(x), B, H, W, Cin, _ptr(weights), kh, kw, cout, sh, sw, _ptr(biases), int(relu), _ptr(y),
                            _ptr(scratch), scratch.numel() * 4, _stream()))

@@ -27,6 +27,18 @@ def test_op_level_cases_pass_on_the_cpu_twin(twin):
     assert ' passed' in r.stdout and 'failed' not in r.stdout, r.stdout[-500:]
 
 
+def test_forward_sweeps_pass_on_the_cpu_twin(twin):
+    """The forward op-level sweeps (test_gpu_forward_ops.py) against the twin: its accumulator is double, so the elementwise bound is
+    held with n = 1, the integer cases bit for bit, every output element written and no guard touched - the oracle, the bounds and
+    the cases are proven before a kernel is involved.  The twin chooses no kernel: the plan assertion alone does not run."""
+    env = dict(os.environ, SAGEN_LIB=twin)
+    r = subprocess.run([sys.executable, '-m', 'pytest', os.path.join(ROOT, 'tests', 'test_gpu_forward_ops.py'), '-m', 'gpu', '-q', '-x',
+                        '-k', 'test_conv_sweep or test_fc_sweep or test_deconv_sweep', '-p', 'no:cacheprovider'], env=env, cwd=ROOT,
+                       capture_output=True, text=True, timeout=1500)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
+    assert ' passed' in r.stdout and 'failed' not in r.stdout and 'skipped' not in r.stdout, r.stdout[-500:]
+
+
 def test_the_twin_is_op_level_only_and_never_a_fallback(twin):
     code = ("import os, sys; sys.path.insert(0, %r)\n"
             "from spatialaudiogen_amd import _lib\n"

@@ -280,8 +280,11 @@ def test_evaluation_metrics(T, B):
 
 
 def _dw_cases():
-    """Randomised 3x3 stride-1 SAME convolutions (the geometry igemm3dw_kernel takes over): odd / tiny images, ragged M
-    tails, N off the tile sizes, multi-image batches (image-edge and batch-edge gap slots), with the fused BN prologue."""
+    """Randomised 3x3 stride-1 SAME convolutions with cin % 16 == 0: odd / tiny images, ragged M tails, N off the tile sizes,
+    multi-image batches (image-edge and batch-edge gap slots), with the fused BN prologue.  Which kernel they reach depends on the
+    switch: by default ops.conv_2d sizes its scratch with sagen_conv2d_scratch_bytes and sagen_conv2d runs the plane tiles
+    (conv3p_kernel); igemm3dw_kernel runs under SAGEN_NO_P3 and where SAGEN_FORCE_TILE names one of its tiles (cases with M > 128
+    and N >= 64 only), igemm_kernel under SAGEN_FP32_ONLY.  test_gpu_forward_ops.py asserts the kernel per case and selection."""
     r = np.random.default_rng(20240917)
     cases = []
     for i in range(28):
