@@ -425,6 +425,59 @@ int sagen_reproject(const uint8_t* src, int n, int src_h, int src_w, const sagen
                     const sagen_projection* dst_proj, const double* rot, int n_rot, int supersample, void* scratch, size_t scratch_bytes,
                     void* stream);
 
+/* ---- dense optical flow between consecutive frames, and the flow folder's byte coding --------------------------------------
+ * The reference's third encoder reads a folder flow/%06d.jpg + flow/flow_limits.npy (feeder.py:135-161) that it makes offline with
+ * FlowNet2 under caffe (scraping/preprocess.py:156-204, scraping/flow.py).  sagen_optical_flow is NOT that network: it is a
+ * classical pyramidal Horn-Schunck estimator with warping, so a checkpoint trained on FlowNet2 flows sees another estimator here.
+ * sagen_flow_encode restates the storage format of preprocess.py:183-196 exactly.
+ *
+ * frames [n_frames][h][w][3] uint8 RGB -> flow [n_frames - 1][h][w][2] fp32: flow k goes from frame k to frame k + 1, u (channel 0)
+ * in pixels to the right, v (channel 1) in pixels down.  Everything before the one rounding to fp32 is fp64.
+ * Neighbour and fetch rule, used everywhere: a row index (or coordinate) is clamped into [0, h - 1]; a column index wraps modulo w
+ * when wrap = 1 (the equirectangular seam) and is clamped into [0, w - 1] when wrap = 0.  Bilinear fetches apply the rule to the
+ * taps of floor(coordinate); coordinates are held within +-2^20.
+ *   luma      0.299 R + 0.587 G + 0.114 B, levels 0..255
+ *   pyramid   level l + 1 is the 2 x 2 mean of level l; a fine centre (x, y) sits at coarse ((x + .5) / 2 - .5, (y + .5) / 2 - .5).
+ *             h and w must be divisible by 2^(levels - 1)
+ *   level     coarsest first.  Both images are smoothed by the separable binomial [1 4 6 4 1] / 16, rows first.  The flow starts at
+ *             zero on the coarsest level, elsewhere at 2 x the bilinear fetch of the coarser flow at the coordinates above
+ *   warp      (u0, v0) = the flow so far; I2w(x, y) = bilinear fetch of the smoothed second image at (x + u0, y + v0);
+ *             Ix = ((I2w[x+1] - I2w[x-1]) + (I1[x+1] - I1[x-1])) / 4, Iy likewise, It = I2w - I1
+ *   iteration (Jacobi, `iters` per warp, from (u0, v0))  ubar = the 4 edge neighbours / 6 + the 4 diagonal neighbours / 12;
+ *             t = (Ix (ubar - u0) + Iy (vbar - v0) + It) / (alpha^2 + Ix^2 + Iy^2); u = ubar - Ix t, v = vbar - Iy t
+ * fuse: Jacobi iterations per launch on a tile held in LDS (temporal blocking), 1..8, 0 = the library's choice.  The result does
+ * not depend on it, bit for bit; sagen_flow_auto_fuse() is the depth that 0 takes (host-only).  Identical frames give a flow of
+ * exactly zero.
+ * Returns: n_frames <= 1 (but >= 0) SAGEN_OK, nothing touched; a null argument SAGEN_ERR_NULL; SAGEN_ERR_SHAPE for n_frames < 0,
+ * h or w < 1, h or w not divisible by 2^(levels - 1), scratch smaller than sagen_optical_flow_scratch_bytes(...) or not 8-byte
+ * aligned; SAGEN_ERR_UNSUPPORTED for levels outside 1..8, warps outside 1..16, iters outside 1..1000, fuse outside 0..8, alpha <= 0
+ * or not finite, h or w above 4096, a coarsest level of fewer than 4 rows or columns, n_frames > 65535.  A refused call writes
+ * nothing; sagen_last_error names the parameter.  sagen_optical_flow_scratch_bytes is 0 for sizes the call would refuse.
+ *
+ * sagen_flow_encode: flow [n][h][w][2] fp32 -> rgb [n][h][w][3] uint8 and limits [n][2] fp32 (the rows of flow_limits.npy).
+ *   per pixel  mag = (float)sqrt((double)u^2 + (double)v^2); ang = atan2(v, u) + pi in fp64, 0 where mag < 0.005
+ *   per frame  lo, hi = min, max of mag; if hi - lo < 1 then hi = lo + 1, in fp32: the stored limits are the ones used
+ *   bytes      R = trunc(ang * 255 / (2 pi)), G = 0, B = trunc((mag - lo) / (hi - lo) * 255) in fp64 on the fp32 mag, lo, hi
+ * The + pi is the reference's: feeder.py:147-160 decodes m cos(a), m sin(a) WITHOUT subtracting it, so the network sees the
+ * NEGATED flow vector, there as here.
+ * Returns: n == 0 SAGEN_OK, nothing touched; a null argument SAGEN_ERR_NULL; SAGEN_ERR_SHAPE for n < 0, h or w < 1, scratch
+ * smaller than sagen_flow_encode_scratch_bytes(...); SAGEN_ERR_UNSUPPORTED for h or w above 4096, n > 65535. */
+typedef struct sagen_flow_params {
+    int32_t levels;             /* pyramid levels, 1..8 */
+    int32_t warps;              /* warps per level, 1..16 */
+    int32_t iters;              /* Jacobi iterations per warp, 1..1000 */
+    int32_t wrap;               /* 1: columns wrap (equirectangular), 0: clamped */
+    int32_t fuse;               /* Jacobi iterations per launch, 1..8; 0: the library chooses */
+    double alpha;               /* smoothness weight, in levels of 0..255 */
+} sagen_flow_params;
+size_t sagen_optical_flow_scratch_bytes(int n_frames, int h, int w, int levels);
+int sagen_optical_flow(const uint8_t* frames, int n_frames, int h, int w, const sagen_flow_params* p, float* flow, void* scratch,
+                       size_t scratch_bytes, void* stream);
+int sagen_flow_auto_fuse(void);
+size_t sagen_flow_encode_scratch_bytes(int n, int h, int w);
+int sagen_flow_encode(const float* flow, int n, int h, int w, uint8_t* rgb, float* limits, void* scratch, size_t scratch_bytes,
+                      void* stream);
+
 /* ---- moving point sources: encode to ambisonics, binauralise, track ------------------------------------------------------
  * The front end of the reference's ambisonics toolbox: AmbiEncoder.encode / encode_frame / encode_v2 (pyutils/ambisonics/
  * encoder.py:10-55), SourceBinauralizer over VirtualStereoMic and Convolvotron, static and per frame (binauralizer.py:12-121), and

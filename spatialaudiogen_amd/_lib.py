@@ -38,6 +38,11 @@ class SagenProjection(C.Structure):
                 ('face', SagenProjFace * 6)]
 
 
+class SagenFlowParams(C.Structure):
+    _fields_ = [('levels', C.c_int32), ('warps', C.c_int32), ('iters', C.c_int32), ('wrap', C.c_int32), ('fuse', C.c_int32),
+                ('alpha', C.c_double)]
+
+
 # every symbol include/sagen.h declares: name -> (restype, argtypes)
 _P, _I, _F, _SZ, _I64 = C.c_void_p, C.c_int, C.c_float, C.c_size_t, C.c_int64
 SIGNATURES = {
@@ -103,6 +108,11 @@ SIGNATURES = {
     'sagen_overlay_blend': (C.c_int, [_P, _I, _I64, _I, _I, _P, _P, _I, _I64, _I, _I, _I, _P, _P, _SZ, _P]),
     'sagen_reproject_scratch_bytes': (_SZ, [_I] * 4),
     'sagen_reproject': (C.c_int, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _I, _I, _P, _SZ, _P]),
+    'sagen_optical_flow_scratch_bytes': (_SZ, [_I] * 4),
+    'sagen_optical_flow': (C.c_int, [_P, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    'sagen_flow_auto_fuse': (C.c_int, []),
+    'sagen_flow_encode_scratch_bytes': (_SZ, [_I] * 3),
+    'sagen_flow_encode': (C.c_int, [_P, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     'sagen_source_track': (C.c_int, [_P, _P, _P, _P, _I, C.c_double, _I64, _I64, _I64, _P, _I, _P, _P, _P]),
     'sagen_encode_sources': (C.c_int, [_P, _I64, _P, _P, _P, _P, _I, C.c_double, _I, _I, C.c_double, _I64, _I64, _P, _P]),
     'sagen_binauralize_sources': (C.c_int, [_P, _I64, _P, _P, _P, _P, _I, C.c_double, _I, _P, _P, _I, _I, _I64, _I64, _I64, _P, _P]),

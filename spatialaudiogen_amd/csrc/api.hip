@@ -3,6 +3,7 @@
 #include "kernels.h"
 #include "emd_core.h"
 #include "project_core.h"
+#include "flow_core.h"
 #include <new>
 #include <cstdlib>
 #include <algorithm>
@@ -642,6 +643,50 @@ int sagen_reproject(const uint8_t* src, int n, int src_h, int src_w, const sagen
                     supersample, src_h, src_w, src_proj->kind, dst_h, dst_w, dst_proj->kind);
     if (n_rot != 0 && ((uintptr_t)rot) % 8) return fail(SAGEN_ERR_SHAPE, "sagen_reproject: rot must be 8-byte aligned");
     return reproject_launch(src, dst, rot, a, (hipStream_t)stream);
+}
+
+size_t sagen_optical_flow_scratch_bytes(int n_frames, int h, int w, int levels) {
+    const char* why;
+    if (n_frames <= 1 || flow_check_sizes(n_frames, h, w, levels, &why) != SAGEN_OK) return 0;
+    return flow_scratch_doubles(n_frames, h, w, levels) * sizeof(double);
+}
+
+int sagen_optical_flow(const uint8_t* frames, int n_frames, int h, int w, const sagen_flow_params* p, float* flow, void* scratch,
+                       size_t scratch_bytes, void* stream) {
+    if (n_frames < 0) return fail(SAGEN_ERR_SHAPE, "sagen_optical_flow: n_frames=%d", n_frames);
+    if (n_frames <= 1) return SAGEN_OK;
+    if (!frames || !p || !flow || !scratch) return fail(SAGEN_ERR_NULL, "sagen_optical_flow: null argument");
+    FlowArgs a;
+    const char* why;
+    const int rc = flow_args_fill(a, n_frames, h, w, p, &why);
+    if (rc != SAGEN_OK)
+        return fail(rc, "sagen_optical_flow: %s (n_frames=%d h=%d w=%d levels=%d warps=%d iters=%d fuse=%d alpha=%g)", why, n_frames, h, w,
+                    p->levels, p->warps, p->iters, p->fuse, p->alpha);
+    const size_t need = flow_scratch_doubles(n_frames, h, w, a.levels) * sizeof(double);
+    if (scratch_bytes < need) return fail(SAGEN_ERR_SHAPE, "sagen_optical_flow: scratch_bytes=%zu, %zu needed", scratch_bytes, need);
+    if (((uintptr_t)scratch) % 8) return fail(SAGEN_ERR_SHAPE, "sagen_optical_flow: scratch must be 8-byte aligned");
+    return optical_flow_launch(frames, a, flow, scratch, (hipStream_t)stream);
+}
+
+int sagen_flow_auto_fuse(void) { return flow_auto_fuse(); }
+
+size_t sagen_flow_encode_scratch_bytes(int n, int h, int w) {
+    (void)h; (void)w;
+    return n > 0 ? (size_t)n * FLOW_ENC_PARTS * 2 * sizeof(float) : 0;
+}
+
+int sagen_flow_encode(const float* flow, int n, int h, int w, uint8_t* rgb, float* limits, void* scratch, size_t scratch_bytes,
+                      void* stream) {
+    if (n < 0) return fail(SAGEN_ERR_SHAPE, "sagen_flow_encode: n=%d", n);
+    if (n == 0) return SAGEN_OK;
+    const char* why;
+    const int rc = flow_encode_check(n, h, w, &why);
+    if (rc != SAGEN_OK) return fail(rc, "sagen_flow_encode: %s (n=%d h=%d w=%d)", why, n, h, w);
+    if (!flow || !rgb || !limits || !scratch) return fail(SAGEN_ERR_NULL, "sagen_flow_encode: null argument");
+    const size_t need = sagen_flow_encode_scratch_bytes(n, h, w);
+    if (scratch_bytes < need) return fail(SAGEN_ERR_SHAPE, "sagen_flow_encode: scratch_bytes=%zu, %zu needed", scratch_bytes, need);
+    if (((uintptr_t)scratch) % 4) return fail(SAGEN_ERR_SHAPE, "sagen_flow_encode: scratch must be 4-byte aligned");
+    return flow_encode_launch(flow, n, h, w, rgb, limits, scratch, (hipStream_t)stream);
 }
 
 int sagen_stft_loss_grad(const float* pred_yzx, const float* target_yzx, const float* mask, int batch, float* grad, double* loss,

@@ -391,6 +391,15 @@ struct ProjArgs;
 int reproject_launch(const uint8_t* src, uint8_t* dst, const double* rot, const ProjArgs& a, hipStream_t s);
 
 // -----------------------------------------------------------------------------------------
+// dense optical flow and its byte coding (flow.hip): sagen_optical_flow / sagen_flow_encode of include/sagen.h; FlowArgs is
+// flow_core.h's, checked and filled by flow_args_fill
+// -----------------------------------------------------------------------------------------
+struct FlowArgs;
+int flow_auto_fuse();
+int optical_flow_launch(const uint8_t* frames, const FlowArgs& a, float* flow, void* scratch, hipStream_t s);
+int flow_encode_launch(const float* flow, int n, int h, int w, uint8_t* rgb, float* limits, void* scratch, hipStream_t s);
+
+// -----------------------------------------------------------------------------------------
 // training-step pieces (train.hip): stft loss + gradient w.r.t. the prediction, fused Adam over a flat bucket
 // -----------------------------------------------------------------------------------------
 int stft_loss_grad_launch(const float* pred, const float* gt, const float* mask, int B, float* grad, double* loss, hipStream_t s);

@@ -22,6 +22,7 @@
 #include "../csrc/emd_core.h"
 #include "../csrc/sources_core.h"
 #include "../csrc/project_core.h"
+#include "../csrc/flow_core.h"
 
 namespace {
 
@@ -653,6 +654,129 @@ int sagen_reproject(const uint8_t* src, int n, int src_h, int src_w, const sagen
         case SAGEN_PROJ_ER: reproject_dst<SAGEN_PROJ_ER>(src, dst, rot, a); break;
         case SAGEN_PROJ_CUBE: reproject_dst<SAGEN_PROJ_CUBE>(src, dst, rot, a); break;
         default: reproject_dst<SAGEN_PROJ_EAC>(src, dst, rot, a); break;
+    }
+    return SAGEN_OK;
+}
+
+/* Dense optical flow and its byte coding (include/sagen.h: sagen_optical_flow, sagen_flow_encode): plain loops per pair over the fp64
+ * core the device uses (csrc/flow_core.h).  Every Jacobi sweep covers the whole level: `fuse` is checked and otherwise ignored, which
+ * is what "the result does not depend on it" means on this side. */
+extern "C++" {
+namespace {
+void flow_pair(const double* p1, const double* p2, const sagen::FlowArgs& a, float* out, double* s1, double* s2, sagen::FlowUV* cur,
+               sagen::FlowUV* oth, sagen::FlowUV* f0, sagen::FlowCoef* coef) {
+    using namespace sagen;
+    size_t off[FLOW_MAX_LEVELS];
+    off[0] = 0;
+    for (int l = 1; l < a.levels; ++l) off[l] = off[l - 1] + (size_t)(a.h >> (l - 1)) * (a.w >> (l - 1));
+    for (int l = a.levels - 1; l >= 0; --l) {
+        const int h = a.h >> l, w = a.w >> l;
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x) {
+                s1[(size_t)y * w + x] = flow_smooth(p1 + off[l], h, w, a.wrap, x, y);
+                s2[(size_t)y * w + x] = flow_smooth(p2 + off[l], h, w, a.wrap, x, y);
+                FlowUV r;
+                r.u = 0.; r.v = 0.;
+                if (l != a.levels - 1) r = flow_upsample(cur, h / 2, w / 2, a.wrap, x, y);
+                oth[(size_t)y * w + x] = r;
+            }
+        std::swap(cur, oth);
+        for (int wp = 0; wp < a.warps; ++wp) {
+            for (int y = 0; y < h; ++y)
+                for (int x = 0; x < w; ++x) {
+                    coef[(size_t)y * w + x] = flow_derivs(s1, s2, cur, h, w, a.wrap, x, y);
+                    f0[(size_t)y * w + x] = cur[(size_t)y * w + x];
+                }
+            for (int it = 0; it < a.iters; ++it) {
+                for (int y = 0; y < h; ++y) {
+                    const FlowUV* rn = cur + (size_t)flow_iy(y - 1, h) * w;
+                    const FlowUV* rc = cur + (size_t)y * w;
+                    const FlowUV* rs = cur + (size_t)flow_iy(y + 1, h) * w;
+                    for (int x = 0; x < w; ++x) {
+                        const int xw = flow_ix(x - 1, w, a.wrap), xe = flow_ix(x + 1, w, a.wrap);
+                        const double ub = flow_average(rn[x].u, rs[x].u, rc[xw].u, rc[xe].u, rn[xw].u, rn[xe].u, rs[xw].u, rs[xe].u);
+                        const double vb = flow_average(rn[x].v, rs[x].v, rc[xw].v, rc[xe].v, rn[xw].v, rn[xe].v, rs[xw].v, rs[xe].v);
+                        oth[(size_t)y * w + x] = flow_hs_update(ub, vb, coef[(size_t)y * w + x], f0[(size_t)y * w + x], a.alpha2);
+                    }
+                }
+                std::swap(cur, oth);
+            }
+        }
+    }
+    for (size_t i = 0; i < (size_t)a.h * a.w; ++i) {
+        out[2 * i] = (float)cur[i].u;
+        out[2 * i + 1] = (float)cur[i].v;
+    }
+}
+}  // namespace
+}  // extern "C++"
+
+size_t sagen_optical_flow_scratch_bytes(int n_frames, int h, int w, int levels) {
+    const char* why;
+    if (n_frames <= 1 || sagen::flow_check_sizes(n_frames, h, w, levels, &why) != SAGEN_OK) return 0;
+    return sagen::flow_scratch_doubles(n_frames, h, w, levels) * sizeof(double);
+}
+
+int sagen_optical_flow(const uint8_t* frames, int n_frames, int h, int w, const sagen_flow_params* p, float* flow, void* scratch,
+                       size_t scratch_bytes, void*) {
+    using namespace sagen;
+    if (n_frames < 0) return fail(SAGEN_ERR_SHAPE, "sagen_optical_flow: n_frames=%d", n_frames);
+    if (n_frames <= 1) return SAGEN_OK;
+    if (!frames || !p || !flow || !scratch) return fail(SAGEN_ERR_NULL, "sagen_optical_flow: null argument");
+    FlowArgs a;
+    const char* why;
+    const int rc = flow_args_fill(a, n_frames, h, w, p, &why);
+    if (rc != SAGEN_OK) return fail(rc, "sagen_optical_flow: %s", why);
+    if (scratch_bytes < flow_scratch_doubles(n_frames, h, w, a.levels) * sizeof(double)) return fail(SAGEN_ERR_SHAPE, "sagen_optical_flow: scratch_bytes too small");
+    if (((uintptr_t)scratch) % 8) return fail(SAGEN_ERR_SHAPE, "sagen_optical_flow: scratch must be 8-byte aligned");
+    // the device's layout: three (u, v) fields and the coefficients per pair, the pyramids, the smoothed level (two frames used here)
+    const size_t hw = (size_t)h * w, pyr = flow_level_pixels(h, w, a.levels);
+    FlowUV* cur = (FlowUV*)scratch;
+    FlowUV* oth = cur + (size_t)(n_frames - 1) * hw;
+    FlowUV* f0 = oth + (size_t)(n_frames - 1) * hw;
+    FlowCoef* coef = (FlowCoef*)(f0 + (size_t)(n_frames - 1) * hw);
+    double* pyramid = (double*)(coef + (size_t)(n_frames - 1) * hw);
+    double* smooth = pyramid + (size_t)n_frames * pyr;
+    for (int f = 0; f < n_frames; ++f) {
+        double* g = pyramid + (size_t)f * pyr;
+        for (size_t i = 0; i < hw; ++i) g[i] = flow_luma(frames + ((size_t)f * hw + i) * 3);
+        size_t fine = 0;
+        for (int l = 1; l < a.levels; ++l) {
+            const int ch = h >> l, cw = w >> l;
+            const size_t coarse = fine + (size_t)(2 * ch) * (2 * cw);
+            for (int y = 0; y < ch; ++y)
+                for (int x = 0; x < cw; ++x) g[coarse + (size_t)y * cw + x] = flow_down(g + fine, 2 * cw, x, y);
+            fine = coarse;
+        }
+    }
+    for (int k = 0; k + 1 < n_frames; ++k)
+        flow_pair(pyramid + (size_t)k * pyr, pyramid + (size_t)(k + 1) * pyr, a, flow + (size_t)k * hw * 2, smooth, smooth + hw, cur, oth, f0, coef);
+    return SAGEN_OK;
+}
+
+size_t sagen_flow_encode_scratch_bytes(int n, int, int) { return n > 0 ? (size_t)n * sagen::FLOW_ENC_PARTS * 2 * sizeof(float) : 0; }
+
+int sagen_flow_encode(const float* flow, int n, int h, int w, uint8_t* rgb, float* limits, void* scratch, size_t scratch_bytes, void*) {
+    using namespace sagen;
+    if (n < 0) return fail(SAGEN_ERR_SHAPE, "sagen_flow_encode: n is negative");
+    if (n == 0) return SAGEN_OK;
+    const char* why;
+    const int rc = flow_encode_check(n, h, w, &why);
+    if (rc != SAGEN_OK) return fail(rc, "sagen_flow_encode: %s", why);
+    if (!flow || !rgb || !limits || !scratch) return fail(SAGEN_ERR_NULL, "sagen_flow_encode: null argument");
+    if (scratch_bytes < sagen_flow_encode_scratch_bytes(n, h, w)) return fail(SAGEN_ERR_SHAPE, "sagen_flow_encode: scratch_bytes too small");
+    const size_t hw = (size_t)h * w;
+    for (int f = 0; f < n; ++f) {
+        const float* p = flow + (size_t)f * hw * 2;
+        float lo = INFINITY, hi = -INFINITY;
+        for (size_t i = 0; i < hw; ++i) {
+            const float m = flow_mag(p[2 * i], p[2 * i + 1]);
+            lo = m < lo ? m : lo;
+            hi = m > hi ? m : hi;
+        }
+        float* lim = limits + (size_t)f * 2;
+        flow_limits(lo, hi, lim);
+        for (size_t i = 0; i < hw; ++i) flow_bytes(p[2 * i], p[2 * i + 1], lim[0], lim[1], rgb + ((size_t)f * hw + i) * 3);
     }
     return SAGEN_OK;
 }

@@ -247,6 +247,53 @@ def reproject(frames, src_proj, dst_hw, dst_proj, rot=None, supersample=1, out=N
     return out
 
 
+def optical_flow(frames, params=None):
+    """Dense optical flow between consecutive frames (include/sagen.h: sagen_optical_flow; in place of the reference's offline
+    FlowNet2 pass, scraping/preprocess.py:156-204): frames [n, h, w, 3] uint8, params a _lib.SagenFlowParams (flow.FlowParams.struct()
+    builds one; None: levels 5, warps 3, iters 30, wrap, alpha 8) -> [max(n - 1, 0), h, w, 2] float32, flow k from frame k to k + 1."""
+    if not (isinstance(frames, torch.Tensor) and frames.is_cuda != _twin() and frames.dtype == torch.uint8 and frames.dim() == 4 and frames.shape[3] == 3):
+        raise TypeError('frames must be a [n, h, w, 3] uint8 tensor on %s' % ('the host (the CPU twin is loaded)' if _twin() else 'the device'))
+    if params is None:
+        params = _lib.SagenFlowParams(5, 3, 30, 1, 0, 8.)
+    if not isinstance(params, _lib.SagenFlowParams):
+        raise TypeError('params must be a _lib.SagenFlowParams (flow.FlowParams(...).struct())')
+    frames = frames.contiguous()
+    n, h, w = frames.shape[:3]
+    if not 1 <= params.levels <= 8:
+        raise ValueError('levels takes 1..8, got %d' % params.levels)
+    if h % (1 << (params.levels - 1)) or w % (1 << (params.levels - 1)):
+        raise ValueError('frames of %dx%d cannot be halved %d times (levels %d)' % (h, w, params.levels - 1, params.levels))
+    out = torch.empty((max(n - 1, 0), h, w, 2), dtype=torch.float32, device=frames.device)
+    if n <= 1:
+        return out
+    l = _lib.lib()
+    nbytes = int(l.sagen_optical_flow_scratch_bytes(n, h, w, params.levels))
+    scratch = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=frames.device)
+    check(l.sagen_optical_flow(_ptr(frames), n, h, w, C.addressof(params), _ptr(out), _ptr(scratch), nbytes, _stream()))
+    return out
+
+
+def flow_encode(flow):
+    """The flow folder's byte coding (include/sagen.h: sagen_flow_encode; scraping/preprocess.py:183-196): flow [n, h, w, 2] float32
+    -> (rgb [n, h, w, 3] uint8: angle + pi, 0, magnitude within the frame's limits; limits [n, 2] float32: the rows of
+    flow_limits.npy)."""
+    if not (isinstance(flow, torch.Tensor) and flow.is_cuda != _twin() and flow.dtype == torch.float32 and flow.dim() == 4 and flow.shape[3] == 2):
+        raise TypeError('flow must be a [n, h, w, 2] float32 tensor on %s' % ('the host (the CPU twin is loaded)' if _twin() else 'the device'))
+    flow = flow.contiguous()
+    n, h, w = flow.shape[:3]
+    if h < 1 or w < 1:
+        raise ValueError('flow frames of %dx%d' % (h, w))
+    rgb = torch.empty((n, h, w, 3), dtype=torch.uint8, device=flow.device)
+    limits = torch.empty((n, 2), dtype=torch.float32, device=flow.device)
+    if n == 0:
+        return rgb, limits
+    l = _lib.lib()
+    nbytes = int(l.sagen_flow_encode_scratch_bytes(n, h, w))
+    scratch = torch.empty(nbytes // 4, dtype=torch.float32, device=flow.device)
+    check(l.sagen_flow_encode(_ptr(flow), n, h, w, _ptr(rgb), _ptr(limits), _ptr(scratch), nbytes, _stream()))
+    return rgb, limits
+
+
 def eval_mel_env(pred, target):
     """myutils.compute_lsd_dist / compute_envelope_dist (myutils.py:96-116) per window: pred / target [B, 4800, C] ->
     (mel_lsd [B, C], env_mse [B, C])."""
