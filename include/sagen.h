@@ -478,6 +478,41 @@ size_t sagen_flow_encode_scratch_bytes(int n, int h, int w);
 int sagen_flow_encode(const float* flow, int n, int h, int w, uint8_t* rgb, float* limits, void* scratch, size_t scratch_bytes,
                       void* stream);
 
+/* ---- rational polyphase FIR resampling, and the RMS of strided windows ---------------------------------------------------------
+ * The reference resamples in three places: resampy.resample(..., 'kaiser_fast') in load_wav(fname, rate) (pyutils/iolib/audio.py:23),
+ * `ffmpeg -ar 48000` with the `pan=4c|c0=c...` channel remap of prepare_ambisonics (scraping/preprocess.py:14-34), and
+ * AmbisonicArray.convert(sample_rate, ordering, normalization) (pyutils/ambisonics/common.py:34-59); compute_audio_pow
+ * (scraping/preprocess.py:146-153) then writes the RMS of 0.1-s windows.  sagen_resample_fir is NOT resampy's tabulated filter nor
+ * swresample: it is a Kaiser-windowed sinc of our own in rational polyphase form, bit-compatible with neither.
+ *
+ * Rates rate_in : rate_out = M : L in lowest terms; h[k], k = -H .. H, is the prototype filter at L x the input rate (zero phase:
+ * output 0 sits on input 0).  With z[m][o] = sum_c mix[o][c] x[m][c] (c ascending; mix null: z = x, c_out = c_in),
+ *   y[n][o] = sum_m h[n M - m L] z[m][o]   over |n M - m L| <= H, m ascending,
+ * both sums in fp64, each product rounded before it is added, one rounding to fp32 at the end.
+ *   taps [L][T] fp64, T = ceil((2 H + 1) / L): row p serves the outputs of phase (n M) mod L = p, in the order of m:
+ *        taps[p][t] = h[kmax(p) - t L], kmax(p) = p + L floor((H - p) / L), zero where that index falls below -H;
+ *        output n reads the rows m = ceil((n M - H) / L) + t
+ *   x    [n_in][c_in] fp32: the stream's rows x0 .. x0 + n_in - 1.  Rows outside the buffer (and before the stream, m < 0) count as
+ *        zero: the caller supplies every row the stream really has among those the outputs reach
+ *   y    [n][c_out] fp32: the outputs n0 .. n0 + n - 1
+ * An output's value depends on n and the rows alone, not on the window (x0, n_in, n0, n) it is computed in: a stream resampled in
+ * pieces gives the bits of the one-call result.
+ * Returns: n == 0 SAGEN_OK, nothing touched; a null taps, y or (with n_in > 0) x SAGEN_ERR_NULL; SAGEN_ERR_SHAPE for L, M or T < 1,
+ * H < 0, T != ceil((2 H + 1) / L), a negative x0, n_in, n0 or n, c_in or c_out < 1, c_out != c_in without a mix;
+ * SAGEN_ERR_UNSUPPORTED for more than 64 channels on either side, T > 4096, L or M > 2^20, a table above 64 MiB, a position or count
+ * above 2^40.  A refused call writes nothing; sagen_last_error names the parameter.
+ *
+ * sagen_window_rms: x [n][channels] fp32 -> rms[i] = sqrt(sum_{j < length} x[first + i hop + j][channel]^2 / length), i < count, fp64:
+ * the device form of compute_audio_pow.  The sum runs in one fixed order: 64 partial sums (partial l takes j = l, l + 64, ...
+ * ascending), then a butterfly over the partials (l with l ^ 1, then ^ 2, ... ^ 32).
+ * Returns: count == 0 SAGEN_OK, nothing touched; a null argument SAGEN_ERR_NULL; SAGEN_ERR_SHAPE for a negative n or count, a channel
+ * outside the row, length < 1, hop or first < 0, a window that does not lie inside the n rows; SAGEN_ERR_UNSUPPORTED for n > 2^40,
+ * channels > 2^20, count >= 2^31. */
+int sagen_resample_fir(const float* x, int64_t x0, int64_t n_in, int c_in, const double* taps, int L, int M, int H, int T, const double* mix,
+                       int c_out, int64_t n0, int64_t n, float* y, void* stream);
+int sagen_window_rms(const float* x, int64_t n, int channels, int channel, int64_t first, int64_t hop, int64_t length, int64_t count,
+                     double* rms, void* stream);
+
 /* ---- moving point sources: encode to ambisonics, binauralise, track ------------------------------------------------------
  * The front end of the reference's ambisonics toolbox: AmbiEncoder.encode / encode_frame / encode_v2 (pyutils/ambisonics/
  * encoder.py:10-55), SourceBinauralizer over VirtualStereoMic and Convolvotron, static and per frame (binauralizer.py:12-121), and

@@ -113,6 +113,8 @@ SIGNATURES = {
     'sagen_flow_auto_fuse': (C.c_int, []),
     'sagen_flow_encode_scratch_bytes': (_SZ, [_I] * 3),
     'sagen_flow_encode': (C.c_int, [_P, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    'sagen_resample_fir': (C.c_int, [_P, _I64, _I64, _I, _P, _I, _I, _I, _I, _P, _I, _I64, _I64, _P, _P]),
+    'sagen_window_rms': (C.c_int, [_P, _I64, _I, _I, _I64, _I64, _I64, _I64, _P, _P]),
     'sagen_source_track': (C.c_int, [_P, _P, _P, _P, _I, C.c_double, _I64, _I64, _I64, _P, _I, _P, _P, _P]),
     'sagen_encode_sources': (C.c_int, [_P, _I64, _P, _P, _P, _P, _I, C.c_double, _I, _I, C.c_double, _I64, _I64, _P, _P]),
     'sagen_binauralize_sources': (C.c_int, [_P, _I64, _P, _P, _P, _P, _I, C.c_double, _I, _P, _P, _I, _I, _I64, _I64, _I64, _P, _P]),

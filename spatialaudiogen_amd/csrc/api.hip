@@ -4,6 +4,7 @@
 #include "emd_core.h"
 #include "project_core.h"
 #include "flow_core.h"
+#include "resample_core.h"
 #include <new>
 #include <cstdlib>
 #include <algorithm>
@@ -687,6 +688,34 @@ int sagen_flow_encode(const float* flow, int n, int h, int w, uint8_t* rgb, floa
     if (scratch_bytes < need) return fail(SAGEN_ERR_SHAPE, "sagen_flow_encode: scratch_bytes=%zu, %zu needed", scratch_bytes, need);
     if (((uintptr_t)scratch) % 4) return fail(SAGEN_ERR_SHAPE, "sagen_flow_encode: scratch must be 4-byte aligned");
     return flow_encode_launch(flow, n, h, w, rgb, limits, scratch, (hipStream_t)stream);
+}
+
+int sagen_resample_fir(const float* x, int64_t x0, int64_t n_in, int c_in, const double* taps, int L, int M, int H, int T, const double* mix,
+                       int c_out, int64_t n0, int64_t n, float* y, void* stream) {
+    if (n < 0) return fail(SAGEN_ERR_SHAPE, "sagen_resample_fir: n=%ld", (long)n);
+    if (n == 0) return SAGEN_OK;
+    if (!taps || !y || (!x && n_in != 0)) return fail(SAGEN_ERR_NULL, "sagen_resample_fir: null argument");
+    ResampleArgs a;
+    const char* why;
+    int rc = resample_args_fill(a, x0, n_in, c_in, L, M, H, T, mix != nullptr, c_out, n0, n, &why);
+    if (rc == SAGEN_OK) rc = resample_fir_launch(x, taps, mix, y, a, &why, (hipStream_t)stream);
+    if (rc != SAGEN_OK && rc != SAGEN_ERR_HIP)
+        return fail(rc, "sagen_resample_fir: %s (x0=%ld n_in=%ld c_in=%d L=%d M=%d H=%d T=%d c_out=%d n0=%ld n=%ld)", why, (long)x0, (long)n_in,
+                    c_in, L, M, H, T, c_out, (long)n0, (long)n);
+    return rc;
+}
+
+int sagen_window_rms(const float* x, int64_t n, int channels, int channel, int64_t first, int64_t hop, int64_t length, int64_t count,
+                     double* rms, void* stream) {
+    if (count < 0) return fail(SAGEN_ERR_SHAPE, "sagen_window_rms: count=%ld", (long)count);
+    if (count == 0) return SAGEN_OK;
+    if (!x || !rms) return fail(SAGEN_ERR_NULL, "sagen_window_rms: null argument");
+    const char* why;
+    const int rc = window_rms_check(n, channels, channel, first, hop, length, count, &why);
+    if (rc != SAGEN_OK)
+        return fail(rc, "sagen_window_rms: %s (n=%ld channels=%d channel=%d first=%ld hop=%ld length=%ld count=%ld)", why, (long)n, channels,
+                    channel, (long)first, (long)hop, (long)length, (long)count);
+    return window_rms_launch(x, channels, channel, first, hop, length, count, rms, (hipStream_t)stream);
 }
 
 int sagen_stft_loss_grad(const float* pred_yzx, const float* target_yzx, const float* mask, int batch, float* grad, double* loss,

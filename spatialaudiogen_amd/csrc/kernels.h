@@ -400,6 +400,15 @@ int optical_flow_launch(const uint8_t* frames, const FlowArgs& a, float* flow, v
 int flow_encode_launch(const float* flow, int n, int h, int w, uint8_t* rgb, float* limits, void* scratch, hipStream_t s);
 
 // -----------------------------------------------------------------------------------------
+// polyphase FIR resampling and windowed RMS (resample.hip): sagen_resample_fir / sagen_window_rms of include/sagen.h; ResampleArgs is
+// resample_core.h's, checked and filled by resample_args_fill
+// -----------------------------------------------------------------------------------------
+struct ResampleArgs;
+int resample_fir_launch(const float* x, const double* taps, const double* mix, float* y, const ResampleArgs& a, const char** why, hipStream_t s);
+int window_rms_launch(const float* x, int channels, int channel, long long first, long long hop, long long length, long long count,
+                      double* rms, hipStream_t s);
+
+// -----------------------------------------------------------------------------------------
 // training-step pieces (train.hip): stft loss + gradient w.r.t. the prediction, fused Adam over a flat bucket
 // -----------------------------------------------------------------------------------------
 int stft_loss_grad_launch(const float* pred, const float* gt, const float* mask, int B, float* grad, double* loss, hipStream_t s);

@@ -23,6 +23,7 @@
 #include "../csrc/sources_core.h"
 #include "../csrc/project_core.h"
 #include "../csrc/flow_core.h"
+#include "../csrc/resample_core.h"
 
 namespace {
 
@@ -777,6 +778,49 @@ int sagen_flow_encode(const float* flow, int n, int h, int w, uint8_t* rgb, floa
         float* lim = limits + (size_t)f * 2;
         flow_limits(lo, hi, lim);
         for (size_t i = 0; i < hw; ++i) flow_bytes(p[2 * i], p[2 * i + 1], lim[0], lim[1], rgb + ((size_t)f * hw + i) * 3);
+    }
+    return SAGEN_OK;
+}
+
+/* Polyphase FIR resampling and windowed RMS (include/sagen.h: sagen_resample_fir, sagen_window_rms; pyutils/iolib/audio.py:23,
+ * scraping/preprocess.py:14-34 and :146-153, pyutils/ambisonics/common.py:34-59): plain loops per output over the fp64 core the
+ * device uses (csrc/resample_core.h).  The rows an output reaches are mixed into a small buffer, zeros where the x buffer has none. */
+int sagen_resample_fir(const float* x, int64_t x0, int64_t n_in, int c_in, const double* taps, int L, int M, int H, int T, const double* mix,
+                       int c_out, int64_t n0, int64_t n, float* y, void*) {
+    using namespace sagen;
+    if (n < 0) return fail(SAGEN_ERR_SHAPE, "sagen_resample_fir: n is negative");
+    if (n == 0) return SAGEN_OK;
+    if (!taps || !y || (!x && n_in != 0)) return fail(SAGEN_ERR_NULL, "sagen_resample_fir: null argument");
+    ResampleArgs a;
+    const char* why;
+    const int rc = resample_args_fill(a, x0, n_in, c_in, L, M, H, T, mix != nullptr, c_out, n0, n, &why);
+    if (rc != SAGEN_OK) return fail(rc, "sagen_resample_fir: %s", why);
+    std::vector<double> z((size_t)T * c_out);
+    for (long long j = 0; j < a.n; ++j) {
+        const long long nn = a.n0 + j, m0 = rs_first_row(nn, L, M, H);
+        for (int t = 0; t < T; ++t) {
+            const long long r = m0 + t - a.x0;
+            for (int o = 0; o < c_out; ++o) z[(size_t)t * c_out + o] = (r >= 0 && r < a.n_in) ? rs_mix_row(x, r, c_in, mix, o) : 0.;
+        }
+        const double* row = taps + (long long)rs_phase(nn, L, M) * T;
+        for (int o = 0; o < c_out; ++o) y[j * c_out + o] = (float)rs_dot(row, z.data() + o, c_out, T);
+    }
+    return SAGEN_OK;
+}
+
+int sagen_window_rms(const float* x, int64_t n, int channels, int channel, int64_t first, int64_t hop, int64_t length, int64_t count,
+                     double* rms, void*) {
+    using namespace sagen;
+    if (count < 0) return fail(SAGEN_ERR_SHAPE, "sagen_window_rms: count is negative");
+    if (count == 0) return SAGEN_OK;
+    if (!x || !rms) return fail(SAGEN_ERR_NULL, "sagen_window_rms: null argument");
+    const char* why;
+    const int rc = window_rms_check(n, channels, channel, first, hop, length, count, &why);
+    if (rc != SAGEN_OK) return fail(rc, "sagen_window_rms: %s", why);
+    for (long long i = 0; i < count; ++i) {
+        double p[RMS_LANES];
+        for (int l = 0; l < RMS_LANES; ++l) p[l] = rms_partial(x, first + i * hop, channels, channel, length, l);
+        rms[i] = rms_finish_host(p, length);
     }
     return SAGEN_OK;
 }

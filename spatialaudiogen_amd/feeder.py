@@ -20,7 +20,7 @@ gets -
     frame index                         max(int(t * video_rate), 0)                    feeder.py:121
     time filters on audio_pow.lst       skip_rate, silence, start, duration, threads   feeder.py:222-238
 - the truncations differ by one sample for about a fifth of the windows, and the network sees that.
-Nothing here touches the GPU.
+Nothing here touches the GPU, except load_wav(..., resample=...) when it is asked to resample a file (resample.py).
 """
 import collections
 import os
@@ -41,16 +41,22 @@ except ImportError:       # pragma: no cover
 _PCM_SCALE = {np.dtype(np.int16): (0.0, 32768.0), np.dtype(np.int32): (0.0, 2147483648.0), np.dtype(np.uint8): (128.0, 128.0)}
 
 
-def load_wav(fname, rate=None):
+def load_wav(fname, rate=None, resample=None):
     """(float64 [n, channels] in [-1, 1), rate) - integer PCM scaled by 1/2^(bits-1) the way libsndfile does for
-    the reference (pyutils/iolib/audio.py:11-28).  There is no resampler offline: a rate mismatch raises."""
+    the reference (pyutils/iolib/audio.py:11-28).  resample=None: a rate mismatch raises.  resample='best' | 'fast' | (zeros, beta,
+    rolloff): a file at another rate goes through the device's polyphase resampler (resample.resample, in place of the reference's
+    resampy call, audio.py:23) and comes back as float64 rows at `rate`."""
     from scipy.io import wavfile
     file_rate, pcm = wavfile.read(fname)
-    if rate is not None and int(rate) != int(file_rate):
+    if rate is not None and int(rate) != int(file_rate) and resample is None:
         raise ValueError('%s is sampled at %d Hz, expected %d (no resampler available offline)' % (fname, file_rate, rate))
     pcm = pcm[:, None] if pcm.ndim == 1 else pcm
     offset, scale = _PCM_SCALE.get(pcm.dtype, (0.0, 1.0))
-    return (pcm.astype(np.float64) - offset) / scale, file_rate
+    data = (pcm.astype(np.float64) - offset) / scale
+    if rate is not None and int(rate) != int(file_rate):
+        from .resample import resample as resample_rows
+        return resample_rows(data, file_rate, rate, quality=resample).astype(np.float64), int(rate)
+    return data, file_rate
 
 
 def save_wav(fname, signal, rate, subtype='PCM_16'):

@@ -294,6 +294,43 @@ def flow_encode(flow):
     return rgb, limits
 
 
+def _f64(t, name):
+    if not (isinstance(t, torch.Tensor) and t.dtype == torch.float64 and t.is_cuda != _twin()):
+        raise TypeError('%s must be a %s float64 tensor' % (name, 'host (the CPU twin is loaded)' if _twin() else 'CUDA'))
+    return t.contiguous()
+
+
+def resample_fir(x, x0, taps, L, M, H, n0, n, mix=None):
+    """Rational polyphase FIR (include/sagen.h: sagen_resample_fir; resample.design builds the table): x [n_in, C_in] float32 = the
+    stream's rows x0 .., taps [L, T] float64, mix [C_out, C_in] float64 or None -> y [n, C_out] float32 = the outputs n0 .. n0 + n - 1.
+    Rows outside the buffer count as zero."""
+    x, taps = _f32(x, 'x'), _f64(taps, 'taps')
+    if x.dim() != 2 or taps.dim() != 2 or taps.shape[0] != int(L):
+        raise ValueError('resample_fir: x [rows, C_in] and taps [L, T] expected')
+    c_in = c_out = x.shape[1]
+    if mix is not None:
+        mix = _f64(mix, 'mix')
+        if mix.dim() != 2 or mix.shape[1] != c_in:
+            raise ValueError('resample_fir: mix [C_out, %d] expected' % c_in)
+        c_out = mix.shape[0]
+    y = torch.empty(max(int(n), 0), c_out, dtype=torch.float32, device=x.device)
+    check(_lib.lib().sagen_resample_fir(_ptr(x), int(x0), x.shape[0], c_in, _ptr(taps), int(L), int(M), int(H), taps.shape[1], _ptr(mix),
+                                        c_out, int(n0), int(n), _ptr(y), _stream()))
+    return y
+
+
+def window_rms(x, channel, first, hop, length, count):
+    """RMS of strided windows of one channel (include/sagen.h: sagen_window_rms; compute_audio_pow, scraping/preprocess.py:146-153):
+    x [n, C] float32 -> [count] float64, window i = rows first + i hop .. + length - 1."""
+    x = _f32(x, 'x')
+    if x.dim() != 2:
+        raise ValueError('window_rms: x [rows, C] expected')
+    out = torch.empty(max(int(count), 0), dtype=torch.float64, device=x.device)
+    check(_lib.lib().sagen_window_rms(_ptr(x), x.shape[0], x.shape[1], int(channel), int(first), int(hop), int(length), int(count),
+                                      _ptr(out), _stream()))
+    return out
+
+
 def eval_mel_env(pred, target):
     """myutils.compute_lsd_dist / compute_envelope_dist (myutils.py:96-116) per window: pred / target [B, 4800, C] ->
     (mel_lsd [B, C], env_mse [B, C])."""

@@ -1,7 +1,7 @@
 """Render ambisonics to something a person can listen to, on the device: the reference's output stage as ONE operation.
 
     python -m spatialaudiogen_amd.render IN_AMBIX.wav OUT.wav [--render {wy,ears,mic,hrir,speakers}] [--hrir_dir DIR]
-           [--decode {projection,pseudoinv}] [--yaw DEG --pitch DEG --roll DEG] [--normalize PEAK] [--overwrite]
+           [--resample_hrir [QUALITY]] [--decode {projection,pseudoinv}] [--yaw DEG --pitch DEG --roll DEG] [--normalize PEAK] [--overwrite]
 
 (the surface of pyutils/ambisonics/scripts/binauralize_ambisonics.py; the order is taken from the channel count, 4 or 9).
 
@@ -88,6 +88,19 @@ class HrirSet(object):
                 right.append(r[:, j])
         return cls(np.array(dirs), np.array(left), np.array(right), rate)
 
+    def resampled(self, rate, quality='best', device=None):
+        """The set at another sample rate: every response through resample.resample (the polyphase FIR of csrc/resample.hip, 64
+        responses per call), scaled by rate_in / rate_out so that each response keeps its frequency response - an impulse response
+        sampled more densely sums more samples per unit of time.  ceil(K L / M) taps."""
+        from . import resample as R
+        if int(rate) == self.rate:
+            return self
+        rows = np.concatenate([self.left, self.right], 0).T.astype(np.float32)               # [K, 2 P]
+        out = [R.resample(np.ascontiguousarray(rows[:, i:i + 64]), self.rate, rate, quality=quality, device=device) for i in range(0, rows.shape[1], 64)]
+        both = np.concatenate(out, 1).astype(np.float64).T * (self.rate / float(rate))
+        P = self.left.shape[0]
+        return HrirSet(self.directions, both[:P], both[P:], rate)
+
 
 # ---- tap tables ---------------------------------------------------------------------------------------------------------------
 def taps_wy(order=1):
@@ -129,10 +142,11 @@ def taps_hrir(order, hrir):
     return h
 
 
-def build_taps(mode, order, rate=48000, hrir=None, decode=None, positions=None):
+def build_taps(mode, order, rate=48000, hrir=None, decode=None, positions=None, resample=None, device=None):
     """(taps [O, C, K] fp64, zero_before) of one rendering.  decode: 'projection' | 'pseudoinv' for ears (default pseudoinv, what
     the reference's script uses) and speakers (default projection); mic and hrir decode by projection onto the ring as the
-    reference does (its pseudoinv layouts come from a t-design table it does not ship)."""
+    reference does (its pseudoinv layouts come from a t-design table it does not ship).  resample: None refuses HRIRs that are not at
+    `rate`; a quality ('best', 'fast' or a (zeros, beta, rolloff) tuple) resamples them on `device` (HrirSet.resampled)."""
     if mode not in MODES:
         raise ValueError('unknown rendering %r (one of %s)' % (mode, ', '.join(MODES)))
     if mode in ('wy', 'mic', 'hrir') and decode not in (None, 'projection'):
@@ -148,7 +162,9 @@ def build_taps(mode, order, rate=48000, hrir=None, decode=None, positions=None):
     if hrir is None:
         raise ValueError("the 'hrir' rendering needs a set of HRIRs (--hrir_dir)")
     if int(hrir.rate) != int(rate):
-        raise ValueError('the HRIRs are sampled at %d Hz, the audio at %d Hz (no resampler available offline)' % (hrir.rate, rate))
+        if resample is None:
+            raise ValueError('the HRIRs are sampled at %d Hz, the audio at %d Hz (no resampler available offline)' % (hrir.rate, rate))
+        hrir = hrir.resampled(rate, resample, device)
     h = taps_hrir(order, hrir)
     return h, h.shape[2] - 1
 
@@ -214,6 +230,8 @@ def add_render_arguments(parser, default_mode=None):
     parser.add_argument('--render', choices=MODES, default=default_mode, help='rendering: W+-Y fold-down, decode at the ears, virtual '
                         'stereo microphone over a speaker ring, HRIRs over a speaker ring, or the speaker feeds themselves')
     parser.add_argument('--hrir_dir', default=None, help='directory of CIPIC-layout HRIR wavs ([neg]<az>az{left,right}.wav), for --render hrir')
+    from .resample import add_quality_flag
+    add_quality_flag(parser, '--resample_hrir', 'resample HRIRs that are not at the audio rate on the device')
     parser.add_argument('--decode', choices=('projection', 'pseudoinv'), default=None, help='decoder of ears (default pseudoinv) / speakers (default projection)')
     parser.add_argument('--yaw', type=float, default=0., help='head yaw in degrees (the field is rotated by the inverse)')
     parser.add_argument('--pitch', type=float, default=0.)
@@ -239,11 +257,20 @@ def check_render_arguments(args, channels, tool):
 
 def rendering_from_arguments(args, channels, rate, tool):
     """Everything of a rendering that is made on the HOST: (taps, zero_before, rotation).  Reads the HRIR files; a missing directory
-    or a rate mismatch is refused here, before the caller touches the device."""
+    or a rate mismatch is refused here, before the caller touches the device.  With --resample_hrir a rate mismatch is not refused:
+    the HRIRs then go through the device's resampler here."""
     order = {4: 1, 9: 2}[channels]
     try:
         hrir = HrirSet.from_cipic_dir(args.hrir_dir) if args.render == 'hrir' else None
-        taps, zero_before = build_taps(args.render, order, rate, hrir=hrir, decode=args.decode)
+        quality = getattr(args, 'resample_hrir', None)
+        device = None
+        if quality is not None and hrir is not None and hrir.rate != int(rate):         # the one rendering that reaches the device here
+            from . import _lib
+            _lib.lib()
+            if not _lib.IS_CPU_TWIN:
+                import torch
+                torch.cuda.set_device(getattr(args, 'gpu', 0))                      # (what the caller does next anyway)
+        taps, zero_before = build_taps(args.render, order, rate, hrir=hrir, decode=args.decode, resample=quality, device=device)
     except (ValueError, IOError) as e:
         raise SystemExit('%s: %s' % (tool, e))
     rotation = None

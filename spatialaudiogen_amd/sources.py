@@ -3,8 +3,8 @@ front end of the reference's ambisonics toolbox (AmbiEncoder, SourceBinauralizer
 three operations per audio sample (include/sagen.h: sagen_encode_sources, sagen_binauralize_sources, sagen_source_track;
 csrc/sources.hip).
 
-    python -m spatialaudiogen_amd.sources encode POSITION_FN AMBI_ORDER OUTPUT_FN [--rate 24000] [--base_dir DIR] [--overwrite]
-    python -m spatialaudiogen_amd.sources binauralize INPUT_FN POSITION_FN OUTPUT_FN [--use_hrtfs --hrtf_dir DIR] [--overwrite]
+    python -m spatialaudiogen_amd.sources encode POSITION_FN AMBI_ORDER OUTPUT_FN [--rate 24000] [--base_dir DIR] [--overwrite] [--resample [QUALITY]]
+    python -m spatialaudiogen_amd.sources binauralize INPUT_FN POSITION_FN OUTPUT_FN [--use_hrtfs --hrtf_dir DIR] [--overwrite] [--resample [QUALITY]]
     python -m spatialaudiogen_amd.sources encode_and_binauralize INPUT_FN POSITION_FN AMBI_ORDER OUTPUT_FN [--overwrite]
     ... encode_xyz INPUT_FN X Y Z AMBI_ORDER OUTPUT_FN | binauralize_xyz INPUT_FN X Y Z OUTPUT_FN [--use_hrtfs --hrtf_dir DIR] |
         encode_and_binauralize_xyz INPUT_FN X Y Z AMBI_ORDER OUTPUT_FN
@@ -13,7 +13,8 @@ csrc/sources.hip).
 _xyz variants, which place one static source at a cartesian position).  `encode` reads a position file with a header per source
 (read_position_file), the wavs relative to --base_dir (default: the position file's directory); the other two read one mono wav and a
 plain file of `phi nu r` lines.  Every command takes --overwrite, --gpu N and --float (a 32-bit float wav instead of PCM16).  A wav
-whose rate differs from --rate is refused: there is no resampler here.  Samples a source's trajectory does not cover (position.py:82:
+whose rate differs from --rate is refused, and so are HRIRs that are not at the rate of the input, unless --resample [best|fast] is
+given: then they go through the device's polyphase resampler (resample.py).  Samples a source's trajectory does not cover (position.py:82:
 nframes = int(duration * rate) can be one short of the signal) stay zero.
 """
 import os
@@ -188,10 +189,10 @@ class SourceScene(object):
 
 
 # ---- command lines ------------------------------------------------------------------------------------------------------------
-def _mono(fn, rate=None):
+def _mono(fn, rate=None, resample=None):
     from .feeder import load_wav
     try:
-        data, file_rate = load_wav(fn, rate)
+        data, file_rate = load_wav(fn, rate, resample)
     except ValueError as e:
         raise SystemExit('sources: %s' % e)
     return data[:, 0], file_rate            # (the scripts keep the first channel of a file that is not mono)
@@ -226,7 +227,7 @@ def run_encode(args):
     if not wavs:
         raise SystemExit('sources encode: %s names no wav per source (header `id wav [img] npts`)' % args.position_fn)
     base = args.base_dir if args.base_dir is not None else os.path.dirname(os.path.abspath(args.position_fn))
-    data = [_mono(os.path.join(base, wavs[k]), args.rate)[0] for k in ids]
+    data = [_mono(os.path.join(base, wavs[k]), args.rate, args.resample)[0] for k in ids]
     scene = SourceScene(data, [points[k] for k in ids], args.rate)
     rows = max(len(d) for d in data)
     ambix = _padded(scene.encode(args.ambi_order).cpu().numpy(), rows).astype(np.float64)
@@ -256,6 +257,8 @@ def run_binauralize(args):
         except (ValueError, IOError) as e:
             raise SystemExit('sources binauralize: %s' % e)
     scene, rows, rate, static = _single_source(args)
+    if hrir is not None and args.resample is not None:
+        hrir = hrir.resampled(rate, args.resample, scene.device)
     try:
         y = scene.binauralize('hrir' if args.use_hrtfs else 'mic', hrir, static=static)
     except ValueError as e:
@@ -294,6 +297,8 @@ def parse_arguments(argv=None):
                 p.add_argument(a)
         p.add_argument('--overwrite', action='store_true', help='Whether to overwrite the output file.')
         p.add_argument('--gpu', type=int, default=0, help='GPU id')
+        from .resample import add_quality_flag
+        add_quality_flag(p, '--resample', 'resample mono wavs (encode: to --rate) and HRIRs (binauralize: to the rate of the input) on the device')
         p.add_argument('--float', dest='float_wav', action='store_true', help='Write a 32-bit float wav instead of 16-bit PCM.')
         return p
 
