@@ -47,11 +47,6 @@ char* err_buf() {
     return buf;
 }
 
-GroupInfo& cur_group() {
-    static thread_local GroupInfo gi;
-    return gi;
-}
-
 int fail(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
@@ -173,7 +168,7 @@ int sagen_stft_mag(const float* audio, int batch, int n_samples, int f0, int f1,
                    void* stream) {
     if (!audio || (!mag && !spec)) return fail(SAGEN_ERR_NULL, "sagen_stft_mag: null argument");
     if (batch <= 0) return fail(SAGEN_ERR_SHAPE, "sagen_stft_mag: batch=%d", batch);
-    return stft_launch(audio, batch, n_samples, f0, f1, mag, c0, c1, spec, (hipStream_t)stream);
+    return stft_launch(audio, batch, n_samples, f0, f1, mag, c0, c1, spec, GroupInfo(), (hipStream_t)stream);
 }
 
 size_t sagen_conv2d_scratch_bytes(int batch, int h, int w, int kh, int kw, int cin, int cout) {
@@ -294,7 +289,7 @@ int sagen_conv2d(const float* x, int batch, int h, int w, int cin, const float* 
         if (rc) return rc;
         if (bn_stats) SAGEN_HIP_CHECK(hipMemsetAsync(bn_stats, 0, (size_t)2 * cout * sizeof(double), s));
         if (o.planes) {
-            rc = p3_pack_launch(x, in_scale, in_shift, BnRef(), nullptr, in_scale ? 1 : 0, nullptr, (void*)d.xp3, batch, h, w, cin, s);
+            rc = p3_pack_launch(x, in_scale, in_shift, BnRef(), nullptr, in_scale ? 1 : 0, nullptr, (void*)d.xp3, batch, h, w, cin, GroupInfo(), s);
             if (rc) return rc;
         }
         return igemm_launch(d, o.tile, s);
@@ -385,7 +380,7 @@ int sagen_fc(const float* x, int m, int k, const float* w_kn, int n, const float
         if (rc) return rc;
         rc = igemm_launch(o.d, o.tile, s);
         if (rc || o.splitk == 1) return rc;
-        return splitk_reduce_launch(o.ws, o.splitk, m, n, bias, relu, y, n, 1, nullptr, s);
+        return splitk_reduce_launch(o.ws, o.splitk, m, n, bias, relu, y, n, 1, nullptr, GroupInfo(), s);
     });
 }
 
@@ -464,7 +459,7 @@ int sagen_mask_istft_mix(const float* dmask, const float* spec, const float* coe
     if (batch <= 0) return fail(SAGEN_ERR_SHAPE, "sagen_mask_istft_mix: batch=%d", batch);
     if (scratch_bytes < mask_istft_scratch_bytes(batch)) return fail(SAGEN_ERR_WORKSPACE, "sagen_mask_istft_mix: scratch too small");
     return mask_istft_mix_launch(dmask, 28L * 1024 * ntracks, 0, spec, coeffs, batch, ntracks, ambi_yzx, (float*)scratch,
-                                 (hipStream_t)stream);
+                                 GroupInfo(), (hipStream_t)stream);
 }
 
 size_t sagen_mask_istft_mix_hoa_scratch_bytes(int batch, int nout) {
@@ -479,7 +474,7 @@ int sagen_mask_istft_mix_hoa(const float* dmask, const float* spec, const float*
             return fail(SAGEN_ERR_UNSUPPORTED, "sagen_mask_istft_mix_hoa: (nin, nout) = (%d, %d) (supported: (4, 5), ambi_order 2)", nin, nout);
         if (scratch_bytes < mask_istft_hoa_scratch_bytes(batch, nout)) return fail(SAGEN_ERR_WORKSPACE, "sagen_mask_istft_mix_hoa: scratch too small");
         return mask_istft_hoa_launch(dmask, 28L * 1024 * nin * ntracks, 0, spec, coeffs, batch, ntracks, nin, nout, out, (float*)scratch,
-                                     (hipStream_t)stream);
+                                     GroupInfo(), (hipStream_t)stream);
     });
 }
 

@@ -42,9 +42,10 @@ __device__ __forceinline__ T* grp_ptr(T* p, const GroupInfo& gi, int g) {
 }
 // in a kernel with a `const GroupInfo gi` parameter: pointer p of THIS workgroup's group (blockIdx.z)
 #define SAGEN_GRP(p) (gi.G > 1 ? ::sagen::grp_ptr((p), gi, (int)blockIdx.z) : (p))
-// the group the launches of THIS thread are issued for (set by sagen_forward_impl around a grouped forward; G = 1 otherwise: the op
-// level, the training step and ungrouped contexts never see a group dimension)
-GroupInfo& cur_group();
+// On the host the group is an ARGUMENT like every other operand of a launch, never ambient state: a launcher whose kernel takes a
+// group dimension has a required `const GroupInfo&` parameter, a contraction carries it in IgemmDesc::grp.  Fwd (model.h) holds the
+// group of its context and passes it on; the op level, the training step and the weight gradients pass a default-constructed one
+// (G = 1) in plain sight.  Launchers without the parameter run one group: Fwd refuses them in a grouped context (Fwd::timed_no_group).
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }

@@ -345,7 +345,7 @@ static bool uniform_taps_for(const IgemmDesc& d, int bk) {
 }
 bool igemm_tile_ok(const IgemmDesc& d, IgemmTile t) {
     if (t < 0 || t >= TILE_AUTO) return false;
-    if (cur_group().G > 1 && !igemm_tile_grouped(t)) return false;
+    if (d.grp.G > 1 && !igemm_tile_grouped(t)) return false;
     const TileShape& k = kTiles[t].sh;
     const unsigned f = kTiles[t].traits;
     const bool split = f & (TF_BF16X3 | TF_FP16X2), planes = f & TF_PLANES;
@@ -470,7 +470,6 @@ int igemm_launch(const IgemmDesc& d_in, IgemmTile tile, hipStream_t s) {
         if (!inside && d.ntaps > 64) return fail(SAGEN_ERR_UNSUPPORTED, "igemm: padded conv with %d taps (max 64)", d.ntaps);
     }
     if (tile == TILE_AUTO) tile = igemm_pick_tile(d);
-    d.grp = cur_group();
     if (d.grp.G > 1 && !igemm_tile_grouped(tile)) return fail(SAGEN_ERR_UNSUPPORTED, "igemm: %s has no grouped launch", igemm_tile_name(tile));
     if (!igemm_tile_ok(d, tile)) return fail(SAGEN_ERR_UNSUPPORTED, "igemm: %s cannot run this problem (Kpad=%d Cin=%d)", igemm_tile_name(tile), d.Kpad, d.Cin);
     // wave-uniform tap per K tile: every K tile lies inside one tap (and there is no ragged K tail)
@@ -648,8 +647,7 @@ __global__ __launch_bounds__(256) void splitk_reduce_stats_kernel(const float* _
 }
 
 int splitk_reduce_launch(const float* ws, int splitk, int M, int N, const float* bias, int relu,
-                         float* y, int ldy, int rep, double* stats, hipStream_t s, float* amax_out) {
-    const GroupInfo gi = cur_group();
+                         float* y, int ldy, int rep, double* stats, const GroupInfo& gi, hipStream_t s, float* amax_out) {
     if (stats) {
         if (amax_out) return fail(SAGEN_ERR_UNSUPPORTED, "split-K reduce: statistics and amax_out together");
         if (N % 4 || ldy % 4 || rep != 1 || bias || relu)
@@ -742,7 +740,7 @@ __global__ __launch_bounds__(256) void deconv_gather_kernel(const float* __restr
     if (g.amax_out != nullptr) igemm_publish_amax(g.amax_out, amax);
 }
 
-int deconv_gather_launch(const float* ws, int splitk, const DeconvGather& g, hipStream_t s) {
+int deconv_gather_launch(const float* ws, int splitk, const DeconvGather& g, const GroupInfo& gi, hipStream_t s) {
     if (!ws || !g.y) return fail(SAGEN_ERR_NULL, "deconv_gather: null argument");
     if (g.Cout % 4 || g.ldy % 4 || ((uintptr_t)g.y % 16) || (g.bias && ((uintptr_t)g.bias % 16)))
         return fail(SAGEN_ERR_UNSUPPORTED, "deconv_gather: Cout / ldy must be multiples of 4 and the pointers 16-byte aligned");
@@ -751,7 +749,6 @@ int deconv_gather_launch(const float* ws, int splitk, const DeconvGather& g, hip
         return fail(SAGEN_ERR_SHAPE, "deconv_gather: rows [%d, %d) of %d / input band [%d, +%d) of %d", g.y0, g.y1, Hout, g.in_row0, g.R, g.Hin);
     const long total = (long)g.B * (g.y1 - g.y0) * (g.Win * g.sw + g.kw - g.sw) * (g.Cout / 4);
     const int pt = cdiv(g.kh, g.sh), qt = cdiv(g.kw, g.sw);
-    const GroupInfo gi = cur_group();
     const dim3 grid(cdiv(total, 256), 1, gi.G);
     if (pt <= 2 && qt <= 2) hipLaunchKernelGGL((deconv_gather_kernel<2, 2>), grid, dim3(256), 0, s, ws, splitk, g, gi);
     else if (pt <= 2 && qt <= 3) hipLaunchKernelGGL((deconv_gather_kernel<2, 3>), grid, dim3(256), 0, s, ws, splitk, g, gi);

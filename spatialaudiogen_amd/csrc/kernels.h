@@ -100,7 +100,8 @@ struct IgemmDesc {
     // debug builds (-DSAGEN_TRACE): phase timeline of workgroup `trace_block`
     void* trace = nullptr;
     int trace_block = 0;
-    // grouped launch (common.h: GroupInfo): filled by igemm_launch from cur_group(); the kernels relocate their per-group pointers
+    // grouped launch (common.h: GroupInfo): written by whoever builds the problem (Fwd::contract; one group by default) and checked, never
+    // written, by igemm_tile_ok / igemm_launch; the kernels relocate their per-group pointers
     GroupInfo grp;
 };
 // every pointer of the descriptor that may live in the per-group region of the workspace, moved to group g's copy (filters, the
@@ -188,7 +189,7 @@ bool igemm_tile_ok(const IgemmDesc& d, IgemmTile t);   // can this instantiation
 // per-channel (sum, sumsq) of the raw sums, accumulated into stats[2][N] (fp64 atomics)
 constexpr int SPLITK_RB = 16;
 int splitk_reduce_launch(const float* ws, int splitk, int M, int N, const float* bias, int relu,
-                         float* y, int ldy, int rep, double* stats, hipStream_t s, float* amax_out = nullptr);      // amax_out: IgemmDesc::amax_out of what is written
+                         float* y, int ldy, int rep, double* stats, const GroupInfo& gi, hipStream_t s, float* amax_out = nullptr);      // amax_out: IgemmDesc::amax_out of what is written
 
 // stride-1 conv2d_transpose in scatter form (igemm.hip): gathers act(bias + sum_z sum_taps T_z[(b, y'-p, x'-q)][(p, q, o)]) from the
 // partials ws[splitk][B*Hin*Win][kh*kw*Cout] of the GEMM over the INPUT pixels into y[b, y', x', o] (pixel stride ldy)
@@ -203,7 +204,7 @@ struct DeconvGather {
     float* y = nullptr;               // [B][Hout][Wout][ldy]
     float* amax_out = nullptr;
 };
-int deconv_gather_launch(const float* ws, int splitk, const DeconvGather& g, hipStream_t s);
+int deconv_gather_launch(const float* ws, int splitk, const DeconvGather& g, const GroupInfo& gi, hipStream_t s);
 
 // filter repacking (igemm.hip).  All produce [Npad][Kpad] with zero padding.
 // conv  : Wp[n][(tap, c)] = W_hwio[tap][c][n],  c < cin_src (cin_pad >= cin_src).  With tw_pad > tw_src > 0 the packed
@@ -258,15 +259,16 @@ int pad_u8_nhwc3to4_launch(const unsigned char* x, float* y, int B, int H, int W
 int stempool_launch(const float* xpad, const float* wp, const float* gamma, float* pooled, double* stats, int B, hipStream_t s);
 // the stem for uint8 frames (stem8.hip): centred bf16 plane of the decoded frame, then conv + statistics + raw pool with one operand plane
 size_t stem8_plane_bytes(int B);
-int stem8_prep_launch(const unsigned char* x, void* plane, int B, hipStream_t s, float* zero_ptr = nullptr, long zero_n = 0, int half = 0);   // half: fp16 plane (stem8pool_h2_launch)
+int stem8_prep_launch(const unsigned char* x, void* plane, int B, const GroupInfo& gi, hipStream_t s, float* zero_ptr = nullptr, long zero_n = 0, int half = 0);   // half: fp16 plane (stem8pool_h2_launch)
 int stem8pool_h2_launch(const void* plane, const float* wp, const void* wh2, const float* w_inv, const float* gamma, float* pooled, double* stats, int B,
-                        hipStream_t s);    // uint8 frames, one fp16 plane x two fp16 filter planes: two products per multiply   // zero_ptr: zero_n floats cleared by the same launch (the batch-norm accumulators)
-int stem8pool_launch(const void* plane, const float* wp, const float* gamma, float* pooled, double* stats, int B, hipStream_t s);
+                        const GroupInfo& gi, hipStream_t s);    // uint8 frames, one fp16 plane x two fp16 filter planes: two products per multiply   // zero_ptr: zero_n floats cleared by the same launch (the batch-norm accumulators)
+int stem8pool_launch(const void* plane, const float* wp, const float* gamma, float* pooled, double* stats, int B, const GroupInfo& gi, hipStream_t s);
 // float frames on the same kernel structure (stem8.hip, F16 variant): two fp16 planes of the frame scaled by its exact maximum
-int stem16_prep_launch(const float* x, void* planes, float* part, float* a_inv, int B, hipStream_t s, float* zero_ptr = nullptr, long zero_n = 0);
+int stem16_prep_launch(const float* x, void* planes, float* part, float* a_inv, int B, const GroupInfo& gi, hipStream_t s, float* zero_ptr = nullptr, long zero_n = 0);
 int stem16pool_launch(const void* planes, const void* wh2, const float* gamma, float* pooled, double* stats, const float* a_inv, const float* w_inv,
-                      int B, hipStream_t s);
+                      int B, const GroupInfo& gi, hipStream_t s);
 constexpr int STEM16_PARTS = 1024;
+// the training step's two (one group always: they take no GroupInfo)
 int stem8raw_launch(const void* plane, const float* wp, float* y0, double* stats, int B, hipStream_t s);
 int stem8rawpool_launch(const void* plane, const float* wp, const float* gamma, float* y0, float* pooled, double* stats, int B, hipStream_t s);   // raw output AND its 3x3/2 pool (max, or min where gamma < 0) in one kernel      // no pool: the raw output (training step)
 int assemble_wyzx_launch(const float* audio, const float* yzx, float* out, int B, int snd_size,
@@ -313,7 +315,7 @@ struct P3hScale {
     const float* res_a_inv = nullptr;
 };
 int p3_pack_launch(const float* x, const float* scale, const float* shift, const BnRef& bn, const float* residual, int relu,
-                   float* y, void* p3, int B, int H, int W, int C, hipStream_t s, int fmt = 0, const P3hScale* h2 = nullptr,
+                   float* y, void* p3, int B, int H, int W, int C, const GroupInfo& gi, hipStream_t s, int fmt = 0, const P3hScale* h2 = nullptr,
                    int s2d = 0);        // s2d (fmt 1, H and W even, not in place): the planes in space-to-depth form (conv3s.hip)
 size_t p3h_bytes(int B, int H, int W, int C);
 size_t p3s_bytes(int B, int H, int W, int C);          // ... in space-to-depth form
@@ -321,7 +323,7 @@ size_t p3s_bytes(int B, int H, int W, int C);          // ... in space-to-depth 
 // floats) -> fp16x2 planes [C/16][B*R*(W+1)][2][16] of v * 2^ka with ka from the EXACT maximum the producers' epilogues published
 // (IgemmDesc::amax_out: H2_AMAX_SLOTS words each; amax1 nullable): nothing can saturate.  2^-ka -> a_inv[0].
 int h2_pack_rows_launch(const float* x, long x_bstride, long x_rstride, int ldx, int row0, int B, int R, int W, int C, const float* amax0,
-                        const float* amax1, void* planes, float* a_inv, unsigned* sat_count, hipStream_t s);
+                        const float* amax1, void* planes, float* a_inv, unsigned* sat_count, const GroupInfo& gi, hipStream_t s);
 // 3x3/2 SAME max-pool of relu(bn(x)) -> fp32 NHWC `y` (or null) and planes `p3` (or null) of the pooled tensor
 int p3_maxpool_launch(const float* x, const float* scale, const float* shift, const BnRef& bn, float* y, void* p3, int B, int H,
                       int W, int C, hipStream_t s, int fmt = 0, const P3hScale* h2 = nullptr);
@@ -332,21 +334,21 @@ int p3_maxpool_launch(const float* x, const float* scale, const float* shift, co
 // fills the twiddle / Hann tables once per device (first call synchronises the stream)
 int fft_tables_ensure(hipStream_t s);
 int stft_launch(const float* audio, int B, int n_samples, int f0, int f1, float* mag,
-                int c0, int c1, float* spec, hipStream_t s, float* zero_ptr = nullptr, int zero_n = 0);      // zero_ptr: zero_n floats cleared by the same launch
+                int c0, int c1, float* spec, const GroupInfo& gi, hipStream_t s, float* zero_ptr = nullptr, int zero_n = 0);      // zero_ptr: zero_n floats cleared by the same launch
 // frames: scratch [B][NF][3][1024]; see fft.hip
 size_t mask_istft_scratch_bytes(int B);
 int mask_istft_mix_launch(const float* dmask, long dmask_bstride, int dmask_f0, const float* spec,
                           const float* coeffs, int B, int ntracks, float* out, float* scratch,
-                          hipStream_t s, const float* ebuf = nullptr);
+                          const GroupInfo& gi, hipStream_t s, const float* ebuf = nullptr);
 // ebuf (then dmask may be null): the weighted sigmoid sums E[B][23][1024][8] written by the fused deconv1 epilogue (IgemmDesc::mm_out)
 // second order (fft.hip): audio [B, n_samples, nin] interleaved -> mag [B, f1-f0, 1024, nin], spec [B, nin, c1-c0, 513, 2]
 int stft_multi_launch(const float* audio, int B, int n_samples, int nin, int f0, int f1, float* mag, int c0, int c1, float* spec,
-                      hipStream_t s, float* zero_ptr = nullptr, int zero_n = 0);
+                      const GroupInfo& gi, hipStream_t s, float* zero_ptr = nullptr, int zero_n = 0);
 // dmask [B][..][1024][nin * ntracks] (frame dmask_f0 first), spec [B][nin][28][513][2], coeffs [B][3][nout][nin][ntracks + 1] ->
 // out [B][4800][nout]; scratch: frames [B][23][nout][1024]
 size_t mask_istft_hoa_scratch_bytes(int B, int nout);
 int mask_istft_hoa_launch(const float* dmask, long dmask_bstride, int dmask_f0, const float* spec, const float* coeffs, int B,
-                          int ntracks, int nin, int nout, float* out, float* scratch, hipStream_t s);
+                          int ntracks, int nin, int nout, float* out, float* scratch, const GroupInfo& gi, hipStream_t s);
 
 // -----------------------------------------------------------------------------------------
 // evaluation metrics (eval.hip)

@@ -301,6 +301,8 @@ namespace sagen {
 struct Fwd {
     sagen_ctx* c;
     hipStream_t s;
+    GroupInfo grp;          // the group geometry every launch of this object carries (common.h; one group unless the context is grouped)
+    Fwd(sagen_ctx* ctx, hipStream_t st) : c(ctx), s(st), grp(ctx->group_info()) {}
     int rc = SAGEN_OK;
     std::string layer;      // label of the layer being launched (profiling only)
     std::string wsname = "splitk";   // split-K scratch of this launch stream
@@ -308,8 +310,9 @@ struct Fwd {
     hipEvent_t wait_before_mfma = nullptr;   // event the first contraction of this stream has to wait for (see forward)
     hipEvent_t wait_packs = nullptr;         // training step: the filter packs of everything behind the stem (second stream, sagen_forward_impl)
     // set around one contract(): the partials [sk][M][N] are consumed by this pass instead of splitk_reduce_kernel (the scatter-form
-    // transposed convs: deconv_gather_kernel) - the contraction then ALWAYS writes partials, also with sk = 1
-    std::function<int(const float* ws, int sk, hipStream_t s)> custom_reduce;
+    // transposed convs: deconv_gather_kernel) - the contraction then ALWAYS writes partials, also with sk = 1.  It is handed the group
+    // that holds when it runs: a candidate the tuner times on fewer groups reduces fewer groups
+    std::function<int(const float* ws, int sk, const GroupInfo& grp, hipStream_t s)> custom_reduce;
     const char* custom_reduce_name = "";
 
     hipEvent_t next_event() {
@@ -334,6 +337,16 @@ struct Fwd {
         if (he == hipSuccess) he = hipEventRecord(r.e1, s);
         if (he != hipSuccess && !rc) rc = fail(SAGEN_ERR_HIP, "hipEventRecord: %s", hipGetErrorString(he));
         c->prof.push_back(r);
+    }
+    // a launch WITHOUT a group dimension (its launcher takes no GroupInfo and would run group 0 only): refused in a grouped context,
+    // here and nowhere else
+    bool no_group_ok(const char* kernel) {
+        if (!rc && grp.G > 1) rc = fail(SAGEN_ERR_UNSUPPORTED, "%s: no grouped launch (common.h: GroupInfo)", kernel);
+        return !rc;
+    }
+    template <class F>
+    void timed_no_group(const char* kernel, double flops, F&& launch) {
+        if (no_group_ok(kernel)) timed(kernel, flops, launch);
     }
 
     // ---- one contraction: direct, or split-K partials + reduce (bias / ReLU / row replication / BN statistics) ----
@@ -363,7 +376,7 @@ struct Fwd {
                 e.bias = nullptr; e.relu_out = 0; e.stats = nullptr;
                 if (igemm_tile_p3(tile)) e.y = e.splitk_ws;       // the plane-fed kernels do not split K: their dense output IS partial 0
                 timed(igemm_tile_name(tile), 2.0 * d.M * d.N * d.K, [&] { return igemm_launch(e, tile, s); });
-                timed(custom_reduce_name, 0.0, [&] { return custom_reduce(e.splitk_ws, sk, s); });
+                timed(custom_reduce_name, 0.0, [&] { return custom_reduce(e.splitk_ws, sk, grp, s); });
                 return 0;
             }
             // the partials are combined by the contraction itself (last-arriver, igemm_epilogue) unless statistics ride on the reducer
@@ -379,7 +392,7 @@ struct Fwd {
             e.bias = nullptr; e.relu_out = 0; e.stats = nullptr;
             timed(igemm_tile_name(tile), 2.0 * d.M * d.N * d.K, [&] { return igemm_launch(e, tile, s); });
             timed("splitk_reduce_kernel", 0.0, [&] {
-                return splitk_reduce_launch(e.splitk_ws, sk, d.M, d.N, d.bias, d.relu_out, d.y, d.ldy, rep, d.stats, s, d.amax_out); });
+                return splitk_reduce_launch(e.splitk_ws, sk, d.M, d.N, d.bias, d.relu_out, d.y, d.ldy, rep, d.stats, grp, s, d.amax_out); });
             return 0;
         }
         timed(igemm_tile_name(tile), 2.0 * d.M * d.N * d.K, [&] { return igemm_launch(d, tile, s); });
@@ -414,15 +427,18 @@ struct Fwd {
     // time every (tile, split-K) candidate on the real operands (sagen_autotune): a first pass (1 warm + 4 timed, min)
     // over all candidates, then a playoff of the three fastest (8 interleaved runs each, median) - single timings of
     // ~10 us launches are too noisy to separate close candidates
-    Choice tune(const IgemmDesc& d, int rep, bool allow_split) {
-        // grouped contexts: with SAGEN_TUNE_GROUPS=n the candidates are timed on the first n groups only (the launchers read the group
-        // count from cur_group()) - a shorter tuning pass; the default times the launches the forward will run (the choice between
-        // tiles does depend on the group count: see sagen_ctx::tune_groups)
-        struct FewerGroups {
-            GroupInfo& g; int saved;
-            explicit FewerGroups(int n) : g(cur_group()), saved(g.G) { if (n > 0 && g.G > n) g.G = n; }
-            ~FewerGroups() { g.G = saved; }
-        } fewer(c->tune_groups);
+    Choice tune(const IgemmDesc& d_in, int rep, bool allow_split) {
+        // grouped contexts: with SAGEN_TUNE_GROUPS=n the candidates are timed on the first n groups only (this object's group and the
+        // descriptor's, lowered for the duration) - a shorter tuning pass; the default times the launches the forward will run (the
+        // choice between tiles does depend on the group count: see sagen_ctx::tune_groups)
+        IgemmDesc d = d_in;
+        const int G = grp.G;
+        if (c->tune_groups > 0 && G > c->tune_groups) d.grp.G = grp.G = c->tune_groups;
+        const Choice best = time_candidates(d, rep, allow_split);
+        grp.G = G;
+        return best;
+    }
+    Choice time_candidates(const IgemmDesc& d, int rep, bool allow_split) {
         Choice top[3];
         for (auto& t : top) { t = heuristic(d, rep, allow_split); t.us = 1e30f; }
         const bool dense = dense_out(d);
@@ -485,6 +501,7 @@ struct Fwd {
         if (rc) return 0;
         IgemmDesc d = d_in;
         d.w_split = c->fp32_only ? 0 : 1;          // every bound filter carries its bf16x3 planes
+        d.grp = grp;                               // ... and every contraction of this object its group
         if (rep > 1 && !dense_out(d)) { rc = fail(SAGEN_ERR_UNSUPPORTED, "replicated store needs a dense plain epilogue"); return 0; }
         Choice ch;
         auto it = c->plan.find(layer);
@@ -609,12 +626,12 @@ struct Fwd {
             void* planes = c->p("catp");
             timed("h2_pack_rows_kernel", 0.0, [&] {
                 return h2_pack_rows_launch(x, (long)Hin * Win * Cin, (long)Win * Cin, Cin, in_row0, c->B, R, Win, Cin, cat_amax(lx, 0), cat_amax(lx, 1), planes,
-                                           cat_a_inv(lx), h2_sat_count(), s); });
+                                           cat_a_inv(lx), h2_sat_count(), grp, s); });
             const H2Filter w = h2_filter(name, true);
             igemm_set_h2_planes(d, planes, c->B, R, Win, Cin, w.w2, cat_a_inv(lx), w.w_inv, 0, R);
         }
         custom_reduce_name = "deconv_gather_kernel";
-        custom_reduce = [gd](const float* ws, int sk, hipStream_t st) { return deconv_gather_launch(ws, sk, gd, st); };
+        custom_reduce = [gd](const float* ws, int sk, const GroupInfo& gi, hipStream_t st) { return deconv_gather_launch(ws, sk, gd, gi, st); };
         gemm(d);
         custom_reduce = nullptr;
     }
@@ -725,15 +742,15 @@ struct Fwd {
         const bool lean = !no_lean && h2() && pool_planes && c->use_p3g && c->bufs.count("p3b" + sfx) != 0 && !c->train_mode;
         float* const s16_a_inv = c->p("h2s") + H2S_S16_A_INV + (sfx.empty() ? 0 : 1);        // 2^-ka of the frame planes
         if (fast16)
-            timed("stem16_amax_kernel+stem16_prep_kernel", 0.0, [&] { return stem16_prep_launch(img, c->p("xpad" + sfx), c->p("s16:part" + sfx), s16_a_inv, B, s,
+            timed("stem16_amax_kernel+stem16_prep_kernel", 0.0, [&] { return stem16_prep_launch(img, c->p("xpad" + sfx), c->p("s16:part" + sfx), s16_a_inv, B, grp, s,
                                                                                                c->p("bnacc" + sfx), (long)c->bufs.at("bnacc" + sfx).n); });
         else if (fast8)
-            timed("stem8_prep_kernel", 0.0, [&] { return stem8_prep_launch(reinterpret_cast<const unsigned char*>(img), c->p("xpad" + sfx), B, s,
+            timed("stem8_prep_kernel", 0.0, [&] { return stem8_prep_launch(reinterpret_cast<const unsigned char*>(img), c->p("xpad" + sfx), B, grp, s,
                                                                           c->p("bnacc" + sfx), (long)c->bufs.at("bnacc" + sfx).n, fast8h ? 1 : 0); });
         else if (c->video_u8 && scope == "video_encoder")
-            timed("pad_u8_nhwc3to4_kernel", 0.0, [&] { return pad_u8_nhwc3to4_launch(reinterpret_cast<const unsigned char*>(img), c->p("xpad" + sfx), B, 224, 448, 2, 3, 2, 4, s); });
+            timed_no_group("pad_u8_nhwc3to4_kernel", 0.0, [&] { return pad_u8_nhwc3to4_launch(reinterpret_cast<const unsigned char*>(img), c->p("xpad" + sfx), B, 224, 448, 2, 3, 2, 4, s); });
         else
-            timed("pad_nhwc3to4_kernel", 0.0, [&] { return pad_nhwc3to4_launch(img, c->p("xpad" + sfx), B, 224, 448, 2, 3, 2, 4, s); });
+            timed_no_group("pad_nhwc3to4_kernel", 0.0, [&] { return pad_nhwc3to4_launch(img, c->p("xpad" + sfx), B, 224, 448, 2, 3, 2, 4, s); });
         // conv1 7x7/2 SAME == VALID 7x8 (8th tap column = zero weights) on the padded 4-channel image
         int H = 0, W = 0;
         if (!rc && wait_before_mfma) {
@@ -749,32 +766,32 @@ struct Fwd {
                 if (fast16)
                     timed("stem8pool_kernel<f16>", 2.0 * B * H * W * 64 * 224, [&] {
                         return stem16pool_launch(c->p("xpad" + sfx), h2_filter(name).w2, c->v(name + "/bn/gamma"), c->p("rx0" + sfx), bn_acc(li),
-                                                 s16_a_inv, h2_filter(name).w_inv, B, s); });
+                                                 s16_a_inv, h2_filter(name).w_inv, B, grp, s); });
                 else if (fast8h)
                     timed("stem8pool_kernel<h2>", 2.0 * B * H * W * 64 * 224, [&] {
                         return stem8pool_h2_launch(c->p("xpad" + sfx), c->p("pk:" + name + "/weights"), h2_filter(name).w2, h2_filter(name).w_inv,
-                                                   c->v(name + "/bn/gamma"), c->p("rx0" + sfx), bn_acc(li), B, s); });
+                                                   c->v(name + "/bn/gamma"), c->p("rx0" + sfx), bn_acc(li), B, grp, s); });
                 else
                 timed("stem8pool_kernel", 2.0 * B * H * W * 64 * 224, [&] {
-                    return stem8pool_launch(c->p("xpad" + sfx), c->p("pk:" + name + "/weights"), c->v(name + "/bn/gamma"), c->p("rx0" + sfx), bn_acc(li), B, s); });
+                    return stem8pool_launch(c->p("xpad" + sfx), c->p("pk:" + name + "/weights"), c->v(name + "/bn/gamma"), c->p("rx0" + sfx), bn_acc(li), B, grp, s); });
                 const BnRef bnf = bn_ref(li, name, (long)B * H * W);
                 layer = name + "/bn-relu";
                 P3hScale hs0 = h2_scale(h2_xbound(0));
                 if (lean) hs0.a_inv = h2_a_inv_x(0);
                 if (pool_planes)       // BN + ReLU of the pooled tensor as planes (lean trunk: planes only - the residual of conv2_1 is read from them) and in place
-                    timed("p3_pack_kernel", 0.0, [&] { return p3_pack_launch(c->p("rx0" + sfx), nullptr, nullptr, bnf, nullptr, 1, lean ? nullptr : c->p("rx0" + sfx), c->p("p3" + sfx), B, 56, 112, 64, s, p3_fmt(), &hs0); });
+                    timed("p3_pack_kernel", 0.0, [&] { return p3_pack_launch(c->p("rx0" + sfx), nullptr, nullptr, bnf, nullptr, 1, lean ? nullptr : c->p("rx0" + sfx), c->p("p3" + sfx), B, 56, 112, 64, grp, s, p3_fmt(), &hs0); });
                 else
-                    timed("bn_apply_relu_kernel", 0.0, [&] { return bn_apply_relu_launch(c->p("rx0" + sfx), nullptr, nullptr, bnf, nullptr, c->p("rx0" + sfx), (long)B * 56 * 112, 64, s); });
+                    timed_no_group("bn_apply_relu_kernel", 0.0, [&] { return bn_apply_relu_launch(c->p("rx0" + sfx), nullptr, nullptr, bnf, nullptr, c->p("rx0" + sfx), (long)B * 56 * 112, 64, s); });
             } else if (fused) {
                 // conv + statistics + pool of the RAW output in one kernel (max or min per channel by the sign of gamma), then BN + ReLU on
                 // the pooled tensor in place: relu(bn(.)) is monotone per channel, so this IS maxpool(relu(bn(conv))) (stempool.hip)
                 H = 112; W = 224;
                 layer = name + "+pool";
-                timed("stempool_kernel", 2.0 * B * H * W * 64 * 224, [&] {
+                timed_no_group("stempool_kernel", 2.0 * B * H * W * 64 * 224, [&] {
                     return stempool_launch(c->p("xpad" + sfx), c->p("pk:" + name + "/weights"), c->v(name + "/bn/gamma"), c->p("rx0" + sfx), bn_acc(li), B, s); });
                 const BnRef bnf = bn_ref(li, name, (long)B * H * W);
                 layer = name + "/bn-relu";
-                timed("bn_apply_relu_kernel", 0.0, [&] { return bn_apply_relu_launch(c->p("rx0" + sfx), nullptr, nullptr, bnf, nullptr, c->p("rx0" + sfx), (long)B * 56 * 112, 64, s); });
+                timed_no_group("bn_apply_relu_kernel", 0.0, [&] { return bn_apply_relu_launch(c->p("rx0" + sfx), nullptr, nullptr, bnf, nullptr, c->p("rx0" + sfx), (long)B * 56 * 112, 64, s); });
             } else {
             IgemmDesc d = conv_desc(c->p("xpad" + sfx), 229, 454, 4, 4, c->p("pk:" + name + "/weights"), 7, 8, 2, 2, false, 64,
                                     c->p("y0" + sfx), 64, H, W);
@@ -786,10 +803,10 @@ struct Fwd {
             {
                 P3hScale hs0 = h2_scale(h2_xbound(0));
                 if (lean) hs0.a_inv = h2_a_inv_x(0);
-                timed("p3_maxpool_kernel", 0.0, [&] { return p3_maxpool_launch(c->p("y0" + sfx), nullptr, nullptr, bn, lean ? nullptr : c->p("rx0" + sfx), c->p("p3" + sfx), B, H, W, 64, s, p3_fmt(), &hs0); });
+                timed_no_group("p3_maxpool_kernel", 0.0, [&] { return p3_maxpool_launch(c->p("y0" + sfx), nullptr, nullptr, bn, lean ? nullptr : c->p("rx0" + sfx), c->p("p3" + sfx), B, H, W, 64, s, p3_fmt(), &hs0); });
             }
             else
-                timed("maxpool3x3s2_kernel", 0.0, [&] { return maxpool3x3s2_launch(c->p("y0" + sfx), nullptr, nullptr, bn, c->p("rx0" + sfx), B, H, W, 64, s); });
+                timed_no_group("maxpool3x3s2_kernel", 0.0, [&] { return maxpool3x3s2_launch(c->p("y0" + sfx), nullptr, nullptr, bn, c->p("rx0" + sfx), B, H, W, 64, s); });
             }
             ++li;
             H = (H + 1) / 2; W = (W + 1) / 2;
@@ -856,7 +873,7 @@ struct Fwd {
                     layer = pfx + "/bn1-relu";
                     P3hScale hs1 = h2_scale();
                     if (lean) hs1.a_inv = h2_a_inv_b();
-                    timed("p3_pack_kernel", 0.0, [&] { return p3_pack_launch(c->p("ry1" + sfx), nullptr, nullptr, bn1, nullptr, 1, nullptr, planes, B, Ho, Wo, cout, s, p3_fmt(), &hs1); });
+                    timed("p3_pack_kernel", 0.0, [&] { return p3_pack_launch(c->p("ry1" + sfx), nullptr, nullptr, bn1, nullptr, 1, nullptr, planes, B, Ho, Wo, cout, grp, s, p3_fmt(), &hs1); });
                     conv_bn(nullptr, Ho, Wo, cout, pfx + "/conv_2", 3, 1, cout, BnRef(), c->p("ry2" + sfx), H2, W2, li, "", planes, lean ? h2_a_inv_b() : nullptr);
                     const BnRef bn2 = bn_ref(li, pfx + "/conv_2", (long)B * Ho * Wo);
                     layer = pfx + "/merge";
@@ -890,9 +907,9 @@ struct Fwd {
                         rows_out = c->tuning || !s2d_out;
                     }
                     if (s2d_out)
-                        timed("p3_pack_kernel", 0.0, [&] { return p3_pack_launch(c->p("ry2" + sfx), nullptr, nullptr, bn2, res_planes ? nullptr : shortcut, 1, nullptr, c->p("p3b" + sfx), B, Ho, Wo, cout, s, p3_fmt(), &hs2, 1); });
+                        timed("p3_pack_kernel", 0.0, [&] { return p3_pack_launch(c->p("ry2" + sfx), nullptr, nullptr, bn2, res_planes ? nullptr : shortcut, 1, nullptr, c->p("p3b" + sfx), B, Ho, Wo, cout, grp, s, p3_fmt(), &hs2, 1); });
                     if (rows_out)
-                        timed("p3_pack_kernel", 0.0, [&] { return p3_pack_launch(c->p("ry2" + sfx), nullptr, nullptr, bn2, res_planes ? nullptr : shortcut, 1, y_fp32 ? xout : nullptr, next_p3 ? xplanes : nullptr, B, Ho, Wo, cout, s, p3_fmt(), &hs2); });
+                        timed("p3_pack_kernel", 0.0, [&] { return p3_pack_launch(c->p("ry2" + sfx), nullptr, nullptr, bn2, res_planes ? nullptr : shortcut, 1, y_fp32 ? xout : nullptr, next_p3 ? xplanes : nullptr, B, Ho, Wo, cout, grp, s, p3_fmt(), &hs2); });
                     x_in_s2d = s2d_out; x_in_rows = rows_out;
                     x_in_planes = next_p3;
                     x_fp32_valid = y_fp32;
@@ -907,14 +924,14 @@ struct Fwd {
                 auto run_prologue = [&] { conv_bn(c->p("ry1" + sfx), Ho, Wo, cout, l2, 3, 1, cout, bn1, c->p("ry2" + sfx), H2, W2, li); };
                 auto run_materialized = [&](const std::string& key) {
                     layer = pfx + "/bn1-relu";
-                    timed("bn_apply_relu_kernel", 0.0, [&] { return bn_apply_relu_launch(c->p("ry1" + sfx), nullptr, nullptr, bn1, nullptr, c->p("ry1n" + sfx), (long)B * Ho * Wo, cout, s); });
+                    timed_no_group("bn_apply_relu_kernel", 0.0, [&] { return bn_apply_relu_launch(c->p("ry1" + sfx), nullptr, nullptr, bn1, nullptr, c->p("ry1n" + sfx), (long)B * Ho * Wo, cout, s); });
                     conv_bn(c->p("ry1n" + sfx), Ho, Wo, cout, l2, 3, 1, cout, BnRef(), c->p("ry2" + sfx), H2, W2, li, key);
                 };
                 if (c->tuning && !rc) {
                     run_prologue();
                     const float t_pro = c->plan[l2].us;
                     (void)hipEventRecord(c->tune_e0, s);
-                    (void)bn_apply_relu_launch(c->p("ry1" + sfx), nullptr, nullptr, bn1, nullptr, c->p("ry1n" + sfx), (long)B * Ho * Wo, cout, s);
+                    if (no_group_ok("bn_apply_relu_kernel")) (void)bn_apply_relu_launch(c->p("ry1" + sfx), nullptr, nullptr, bn1, nullptr, c->p("ry1n" + sfx), (long)B * Ho * Wo, cout, s);
                     (void)hipEventRecord(c->tune_e1, s);
                     (void)hipEventSynchronize(c->tune_e1);
                     float ms = 0.f;
@@ -938,9 +955,9 @@ struct Fwd {
                 // stride-2 conv_1 + shortcut of that stage's first block (conv3g_kernel) and is written as planes only
                 const bool planes_out = unit == 2 && st < 3 && c->use_p3g && c->use_p3 && st + 3 >= c->p3_from_stage;
                 if (planes_out)
-                    timed("p3_pack_kernel", 0.0, [&] { return p3_pack_launch(c->p("ry2" + sfx), nullptr, nullptr, bn2, shortcut, 1, nullptr, c->p("p3" + sfx), B, Ho, Wo, cout, s); });
+                    timed("p3_pack_kernel", 0.0, [&] { return p3_pack_launch(c->p("ry2" + sfx), nullptr, nullptr, bn2, shortcut, 1, nullptr, c->p("p3" + sfx), B, Ho, Wo, cout, grp, s); });
                 else
-                    timed("bn_apply_relu_kernel", 0.0, [&] { return bn_apply_relu_launch(c->p("ry2" + sfx), nullptr, nullptr, bn2, shortcut, xout, (long)B * Ho * Wo, cout, s); });
+                    timed_no_group("bn_apply_relu_kernel", 0.0, [&] { return bn_apply_relu_launch(c->p("ry2" + sfx), nullptr, nullptr, bn2, shortcut, xout, (long)B * Ho * Wo, cout, s); });
                 x_in_planes = planes_out;
                 x_fp32_valid = !planes_out;
                 ++li;
@@ -967,16 +984,16 @@ struct Fwd {
             rc = fail(SAGEN_ERR_HIP, "hipMemsetAsync(bn accumulators) failed");
         layer = scope + "/pad";
         if (c->video_u8 && scope == "video_encoder")
-            timed("pad_u8_nhwc3to4_kernel", 0.0, [&] { return pad_u8_nhwc3to4_launch(reinterpret_cast<const unsigned char*>(img), c->p("xpad" + sfx), B, 224, 448, 2, 3, 2, 4, s); });
+            timed_no_group("pad_u8_nhwc3to4_kernel", 0.0, [&] { return pad_u8_nhwc3to4_launch(reinterpret_cast<const unsigned char*>(img), c->p("xpad" + sfx), B, 224, 448, 2, 3, 2, 4, s); });
         else
-            timed("pad_nhwc3to4_kernel", 0.0, [&] { return pad_nhwc3to4_launch(img, c->p("xpad" + sfx), B, 224, 448, 2, 3, 2, 4, s); });
+            timed_no_group("pad_nhwc3to4_kernel", 0.0, [&] { return pad_nhwc3to4_launch(img, c->p("xpad" + sfx), B, 224, 448, 2, 3, 2, 4, s); });
         int H = 0, W = 0;
         // uint8 frames (sagen_train_step_u8): the stem's forward on the exact one-plane operand (stem8.hip, RAW: y0 is kept for the
         // backward); the float xpad above is still what the stem's weight gradient contracts
         const bool fast8 = c->video_u8 && scope == "video_encoder" && c->stem8 && !c->tuning && !c->fp32_only && c->tbufs.count("t:s8plane" + sfx) != 0;
         if (fast8) {
             layer = scope + "/plane";
-            timed("stem8_prep_kernel", 0.0, [&] { return stem8_prep_launch(reinterpret_cast<const unsigned char*>(img), c->p("t:s8plane" + sfx), B, s); });
+            timed("stem8_prep_kernel", 0.0, [&] { return stem8_prep_launch(reinterpret_cast<const unsigned char*>(img), c->p("t:s8plane" + sfx), B, grp, s); });
         }
         if (!rc && wait_before_mfma) {
             if (hipStreamWaitEvent(s, wait_before_mfma, 0) != hipSuccess) rc = fail(SAGEN_ERR_HIP, "hipStreamWaitEvent failed");
@@ -1012,13 +1029,13 @@ struct Fwd {
                 P3hScale hs0 = h2_scale(h2_xbound(0));
                 hs0.a_inv = pl_a_inv(8);
                 layer = name + "/bn-relu";
-                timed("p3_pack_kernel", 0.0, [&] { return p3_pack_launch(c->p("rx0" + sfx), nullptr, nullptr, bn, nullptr, 1, c->p("t:x0" + sfx), pl_buf("x", 0), B, 56, 112, 64, s, 1, &hs0); });
+                timed("p3_pack_kernel", 0.0, [&] { return p3_pack_launch(c->p("rx0" + sfx), nullptr, nullptr, bn, nullptr, 1, c->p("t:x0" + sfx), pl_buf("x", 0), B, 56, 112, 64, grp, s, 1, &hs0); });
             } else if (keep) {                         // the pooled block input also as (retained) planes: stage 2 runs on planes as well
                 P3hScale hs0 = h2_scale(h2_xbound(0));
                 hs0.a_inv = pl_a_inv(8);
-                timed("p3_maxpool_kernel", 0.0, [&] { return p3_maxpool_launch(c->p("y0" + sfx), nullptr, nullptr, bn, c->p("t:x0" + sfx), pl_buf("x", 0), B, H, W, 64, s, 1, &hs0); });
+                timed_no_group("p3_maxpool_kernel", 0.0, [&] { return p3_maxpool_launch(c->p("y0" + sfx), nullptr, nullptr, bn, c->p("t:x0" + sfx), pl_buf("x", 0), B, H, W, 64, s, 1, &hs0); });
             } else {
-                timed("maxpool3x3s2_kernel", 0.0, [&] { return maxpool3x3s2_launch(c->p("y0" + sfx), nullptr, nullptr, bn, c->p("t:x0" + sfx), B, H, W, 64, s); });
+                timed_no_group("maxpool3x3s2_kernel", 0.0, [&] { return maxpool3x3s2_launch(c->p("y0" + sfx), nullptr, nullptr, bn, c->p("t:x0" + sfx), B, H, W, 64, s); });
             }
             ++li;
             H = (H + 1) / 2; W = (W + 1) / 2;
@@ -1070,8 +1087,8 @@ struct Fwd {
                 // backward re-derives the ReLU mask from y1 (unless a debugging switch asks for the fp32 tensor)
                 static const bool a1_wanted = getenv("SAGEN_BN_READ_ACT") != nullptr || getenv("SAGEN_TRAIN_KEEP_A1") != nullptr;
                 float* a1w = (keep && p3_here && !a1_wanted && !wgrad_reads_fp32_operands()) ? nullptr : a1;
-                if (p3_here) timed("p3_pack_kernel", 0.0, [&] { return p3_pack_launch(y1, nullptr, nullptr, bn1, nullptr, 1, a1w, planes, B, Ho, Wo, cout, s, p3_fmt(), &hs1); });
-                else timed("bn_apply_relu_kernel", 0.0, [&] { return bn_apply_relu_launch(y1, nullptr, nullptr, bn1, nullptr, a1, (long)B * Ho * Wo, cout, s); });
+                if (p3_here) timed("p3_pack_kernel", 0.0, [&] { return p3_pack_launch(y1, nullptr, nullptr, bn1, nullptr, 1, a1w, planes, B, Ho, Wo, cout, grp, s, p3_fmt(), &hs1); });
+                else timed_no_group("bn_apply_relu_kernel", 0.0, [&] { return bn_apply_relu_launch(y1, nullptr, nullptr, bn1, nullptr, a1, (long)B * Ho * Wo, cout, s); });
                 conv_bn(p3_here ? a1w : a1, Ho, Wo, cout, pfx + "/conv_2", 3, 1, cout, BnRef(), y2, H2, W2, li, p3_here ? "" : pfx + "/conv_2#mat", planes, planes_ai);
                 const BnRef bn2 = bn_ref(li, pfx + "/conv_2", (long)B * Ho * Wo);
                 ++li;
@@ -1083,8 +1100,8 @@ struct Fwd {
                     hs2.relu_bits = reinterpret_cast<unsigned char*>(c->p("t:mb:" + k));       // the block output's ReLU mask, one bit per element
                 }
                 if (p3_here) xb_par ^= 1;
-                if (p3_here) timed("p3_pack_kernel", 0.0, [&] { return p3_pack_launch(y2, nullptr, nullptr, bn2, shortcut, 1, xout, nplanes, B, Ho, Wo, cout, s, p3_fmt(), &hs2); });
-                else timed("bn_apply_relu_kernel", 0.0, [&] { return bn_apply_relu_launch(y2, nullptr, nullptr, bn2, shortcut, xout, (long)B * Ho * Wo, cout, s); });
+                if (p3_here) timed("p3_pack_kernel", 0.0, [&] { return p3_pack_launch(y2, nullptr, nullptr, bn2, shortcut, 1, xout, nplanes, B, Ho, Wo, cout, grp, s, p3_fmt(), &hs2); });
+                else timed_no_group("bn_apply_relu_kernel", 0.0, [&] { return bn_apply_relu_launch(y2, nullptr, nullptr, bn2, shortcut, xout, (long)B * Ho * Wo, cout, s); });
                 xin = xout;
                 H = Ho; W = Wo; cin = cout;
             }

@@ -428,12 +428,6 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
     const int B = c->B;
     c->events_used = 0;
     c->prof.clear();
-    // grouped context: every launch of this call carries the group dimension (common.h); the launchers read it from cur_group()
-    struct GroupScope {
-        GroupInfo saved;
-        explicit GroupScope(const GroupInfo& gi) : saved(cur_group()) { cur_group() = gi; }
-        ~GroupScope() { cur_group() = saved; }
-    } group_scope(c->group_info());
     if (c->G > 1) {
         if (c->train_mode) return fail(SAGEN_ERR_UNSUPPORTED, "the training step has no grouped launch");
         if (!c->freq_mask || sagen_ctx::off_grouped(c) ||
@@ -447,8 +441,8 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
     // entry and join before the localisation FCs.  While autotuning, or without visual encoders, everything
     // stays on the caller's stream.
     const bool forked = sagen_forward_forks(c);
-    Fwd f{c, s};
-    Fwd g{c, forked ? c->aux : s};
+    Fwd f(c, s);                       // (grouped context: both carry its group into every launch - Fwd::grp)
+    Fwd g(c, forked ? c->aux : s);
     // error exit: work may still be queued on the context's stream, reading the caller's tensors / the workspace - the caller's
     // stream must not run ahead of it (torch's caching allocator could hand that memory out again on `s`)
     auto bail = [&](int rc) {
@@ -488,10 +482,10 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
     // ---- stream g: STFT (myutils.py:119-147) -> |.| of frames 46:173 (model.py:166-178) + spectrum of frames 89:117
     g.layer = "stft";
     if (c->nin == 1)
-        g.timed("stft_kernel", 0.0, [&] { return stft_launch(audio, B, c->snd_size, 46, 173, c->p("mag"), 89, 117, c->p("spec"), g.s,
+        g.timed("stft_kernel", 0.0, [&] { return stft_launch(audio, B, c->snd_size, 46, 173, c->p("mag"), 89, 117, c->p("spec"), g.grp, g.s,
                                                              want_amax ? c->p("amax") : nullptr, 10 * H2_AMAX_FLOATS + 64); });
     else      // one STFT per input channel of the interleaved [B, snd_size, nin] audio (model.py:369)
-        g.timed("stft_multi_kernel", 0.0, [&] { return stft_multi_launch(audio, B, c->snd_size, c->nin, 46, 173, c->p("mag"), 89, 117, c->p("spec"), g.s,
+        g.timed("stft_multi_kernel", 0.0, [&] { return stft_multi_launch(audio, B, c->snd_size, c->nin, 46, 173, c->p("mag"), 89, 117, c->p("spec"), g.grp, g.s,
                                                                          want_amax ? c->p("amax") : nullptr, 10 * H2_AMAX_FLOATS + 64); });
     if (forked) {
         // The LDS FFT kernels give wrong results when bf16x3 contraction waves of ANOTHER stream share their CUs
@@ -552,7 +546,7 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
             g.layer = name + "/planes";
             g.timed("h2_pack_rows_kernel", 0.0, [&] {
                 return h2_pack_rows_launch(c->p("cat" + std::to_string(l)) + cp, (long)Hl * Wl * 2 * cp, (long)Wl * 2 * cp, 2 * cp, 0, B, Hl, Wl, cp,
-                                           g.cat_amax(l, 1), nullptr, c->p("aencp"), a_inv, g.h2_sat_count(), g.s); });
+                                           g.cat_amax(l, 1), nullptr, c->p("aencp"), a_inv, g.h2_sat_count(), g.grp, g.s); });
             g.layer = name;
             const Fwd::H2Filter w = g.h2_filter(name);
             igemm_set_h2_planes(d, c->p("aencp"), B, Hl, Wl, cp, w.w2, a_inv, w.w_inv);
@@ -574,13 +568,13 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
             fl += 2.0 * M * K * Ns[j];
         }
         w.layer = label;
-        w.timed(M <= 32 ? "fcm_kernel<1>" : (M <= 64 ? "fcm_kernel<2>" : "fcm_kernel<3>"), fl, [&] { return fcm_launch(fd, w.s); });
+        w.timed_no_group(M <= 32 ? "fcm_kernel<1>" : (M <= 64 ? "fcm_kernel<2>" : "fcm_kernel<3>"), fl, [&] { return fcm_launch(fd, w.s); });
     };
     // ... and the reducer behind it: y[(m * rep + r) * ldy + n] = act(bias + sum of the slices)
     auto fcm_finish = [&](Fwd& w, const std::string& name, int rows, int N, bool relu, float* y, int ldy, int rep, float* amax_out = nullptr) {
         w.layer = name;
         w.timed("splitk_reduce_kernel", 0.0, [&] {
-            return splitk_reduce_launch(c->p("fcm:" + name), c->fcm_slices.at(name), rows, N, c->v(name + "/biases"), relu ? 1 : 0, y, ldy, rep, nullptr, w.s, amax_out); });
+            return splitk_reduce_launch(c->p("fcm:" + name), c->fcm_slices.at(name), rows, N, c->v(name + "/biases"), relu ? 1 : 0, y, ldy, rep, nullptr, w.grp, w.s, amax_out); });
     };
     if (fcm) {  // audio-fc: the six frequency columns of conv5 (the first 512 channels of cat5's pixels) are six plain input ranges
         std::vector<FcmSeg> segs(6);
@@ -681,9 +675,9 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
     if (!c->freq_mask) {
         f.layer = "decoder";
         if (c->nin == 1)
-            f.timed("nosep_mix_kernel", 0.0, [&] { return nosep_mix_launch(audio, c->p("coeffs"), out, B, c->snd_size, c->snd_contx, c->snd_dur, 3, s); });
+            f.timed_no_group("nosep_mix_kernel", 0.0, [&] { return nosep_mix_launch(audio, c->p("coeffs"), out, B, c->snd_size, c->snd_contx, c->snd_dur, 3, s); });
         else
-            f.timed("nosep_mix_multi_kernel", 0.0, [&] {
+            f.timed_no_group("nosep_mix_multi_kernel", 0.0, [&] {
                 return nosep_mix_multi_launch(audio, c->p("coeffs"), out, B, c->snd_size, c->snd_contx, c->snd_dur, c->nin, c->nout, s); });
         return f.rc;
     }
@@ -741,7 +735,7 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
         f.layer = "separation/cat1-planes";
         f.timed("h2_pack_rows_kernel", 0.0, [&] {
             return h2_pack_rows_launch(c->p("cat1"), (long)c->enc_h[1] * W1 * C1, (long)W1 * C1, C1, 10, B, 7, W1, C1, f.cat_amax(1, 0), f.cat_amax(1, 1), c->p("cat1p"),
-                                       f.cat_a_inv(1), f.h2_sat_count(), s); });
+                                       f.cat_a_inv(1), f.h2_sat_count(), f.grp, s); });
         const Fwd::H2Filter w = f.h2_filter("separation/deconv1");
         const void* planes = c->p("cat1p");
         const float* a_inv = f.cat_a_inv(1);
@@ -757,12 +751,12 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
     if (c->nin > 1) {
         f.timed("mask_istft_hoa_kernel+ola_mix_hoa_kernel", 0.0, [&] {
             return mask_istft_hoa_launch(c->p("dmask"), 23L * 1024 * nmask, 1, c->p("spec"), c->p("coeffs"), B, c->nsep, c->nin, c->nout, out,
-                                         c->p("frames"), s); });
+                                         c->p("frames"), f.grp, s); });
         return f.rc;
     }
     f.timed("mask_istft_kernel+ola_mix_kernel", 0.0, [&] {
         return mask_istft_mix_launch(c->p("dmask"), 23L * 1024 * c->nsep, 1, c->p("spec"), c->p("coeffs"), B, c->nsep, out,
-                                     c->p("frames"), s, ebuf); });
+                                     c->p("frames"), f.grp, s, ebuf); });
     return f.rc;
 }
 int sagen_forward_u8_impl(sagen_ctx* c, const float* audio, const uint8_t* video_u8, const float* flow, float* out, hipStream_t s) {

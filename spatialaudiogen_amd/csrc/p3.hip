@@ -254,7 +254,7 @@ static int aligned_grid(long total, int unit_threads, int amort = 1) {
 }
 
 int p3_pack_launch(const float* x, const float* scale, const float* shift, const BnRef& bn, const float* residual, int relu,
-                   float* y, void* p3, int B, int H, int W, int C, hipStream_t s, int fmt, const P3hScale* h2, int s2d) {
+                   float* y, void* p3, int B, int H, int W, int C, const GroupInfo& gi, hipStream_t s, int fmt, const P3hScale* h2, int s2d) {
     if (C % 16 || C > P3_MAX_C) return fail(SAGEN_ERR_UNSUPPORTED, "p3_pack: C=%d must be a multiple of 16, at most %d", C, P3_MAX_C);
     if (!y && !p3) return fail(SAGEN_ERR_NULL, "p3_pack: no output");
     const long nrows = (long)B * H;
@@ -267,7 +267,6 @@ int p3_pack_launch(const float* x, const float* scale, const float* shift, const
     // (measured with three batches in flight, same box, tools/ab_p3_amort.sh: 1 / 2 / 4 items per thread = 2 508-2 524 / 2 519-2 529 / 2 536-2 544
     //  ambisonic-s/s - the pass alone is no faster with fewer workgroups, but it leaves the CUs to the other batches' matrix kernels sooner)
     const int amort = amort_env > 0 ? amort_env : 4;
-    const GroupInfo gi = cur_group();
     if (fmt == 1)
         hipLaunchKernelGGL(p3_pack_kernel<true>, dim3(aligned_grid(total, C / 8, amort), 1, gi.G), dim3(256), 0, s, x, scale, shift, bn, residual, relu, y,
                            (char*)p3, nrows, W, C, *h2, gi, s2d);
@@ -319,11 +318,10 @@ __global__ __launch_bounds__(256) void h2_pack_rows_kernel(const float* __restri
 }
 
 int h2_pack_rows_launch(const float* x, long x_bstride, long x_rstride, int ldx, int row0, int B, int R, int W, int C, const float* amax0,
-                        const float* amax1, void* planes, float* a_inv, unsigned* sat_count, hipStream_t s) {
+                        const float* amax1, void* planes, float* a_inv, unsigned* sat_count, const GroupInfo& gi, hipStream_t s) {
     if (!x || !amax0 || !planes || !a_inv) return fail(SAGEN_ERR_NULL, "h2_pack_rows: null argument");
     if (C % 16 || ldx % 4 || ((uintptr_t)x % 16)) return fail(SAGEN_ERR_UNSUPPORTED, "h2_pack_rows: C %% 16, ldx %% 4 and a 16-byte aligned tensor are required");
     const long total = (long)B * R * (W + 1) * (C / 8);
-    const GroupInfo gi = cur_group();
     hipLaunchKernelGGL(h2_pack_rows_kernel, dim3((int)std::min<long>(cdiv(total, 256), 2048), 1, gi.G), dim3(256), 0, s, x, x_bstride, x_rstride, ldx, row0,
                        B, R, W, C, amax0, amax1, (char*)planes, a_inv, sat_count, gi);
     SAGEN_LAUNCH_CHECK();
@@ -406,7 +404,6 @@ int p3_maxpool_launch(const float* x, const float* scale, const float* shift, co
     const int pth = std::max((Ho - 1) * 2 + 3 - H, 0), ptw = std::max((Wo - 1) * 2 + 3 - W, 0);
     const long total = (long)B * Ho * (Wo + 1) * (C / 8);
     if (fmt == 1 && p3 && !(h2 && h2->a_inv)) return fail(SAGEN_ERR_NULL, "p3_maxpool: the fp16x2 format needs a slot for its scale");
-    if (cur_group().G > 1) return fail(SAGEN_ERR_UNSUPPORTED, "p3_maxpool: no grouped launch (the grouped forward runs the fused stem kernels)");
     if (fmt == 1)
         hipLaunchKernelGGL(p3_maxpool_kernel<true>, dim3(aligned_grid(total, C / 8)), dim3(256), 0, s, x, scale, shift, bn, y, (char*)p3, B, H,
                            W, C, Ho, Wo, pth / 2, ptw / 2, *h2);

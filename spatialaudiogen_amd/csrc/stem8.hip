@@ -352,12 +352,11 @@ __global__ __launch_bounds__(S8_THREADS, 2) void stem8pool_kernel(const char* __
     }
 }
 
-int stem8_prep_launch(const unsigned char* x, void* plane, int B, hipStream_t s, float* zero_ptr, long zero_n, int half) {
+int stem8_prep_launch(const unsigned char* x, void* plane, int B, const GroupInfo& gi, hipStream_t s, float* zero_ptr, long zero_n, int half) {
     if (!x || !plane) return fail(SAGEN_ERR_NULL, "stem8_prep: null argument");
     if (((uintptr_t)x % 4) || ((uintptr_t)plane % 16)) return fail(SAGEN_ERR_UNSUPPORTED, "stem8_prep: the frames must be 4-byte aligned, the plane 16-byte aligned");
     const long total = (long)B * S8_UH * S8_UW / 4;       // one thread per four plane pixels
     const int grid = (int)std::min<long>(cdiv(total, 256), 256L * 16);
-    const GroupInfo gi = cur_group();
     if (half) hipLaunchKernelGGL(stem8_prep_kernel<true>, dim3(grid, 1, gi.G), dim3(256), 0, s, x, reinterpret_cast<u32x2*>(plane), B, zero_ptr, zero_ptr ? zero_n : 0L, gi);
     else hipLaunchKernelGGL(stem8_prep_kernel<false>, dim3(grid, 1, gi.G), dim3(256), 0, s, x, reinterpret_cast<u32x2*>(plane), B, zero_ptr, zero_ptr ? zero_n : 0L, gi);
     SAGEN_LAUNCH_CHECK();
@@ -366,7 +365,7 @@ int stem8_prep_launch(const unsigned char* x, void* plane, int B, hipStream_t s,
 
 // plane: stem8_prep's output; wp: the stem's packed filter (fp32 [64][224] followed by its bf16x3 planes); pooled [B,56,112,64] RAW
 // (max or min per channel by the sign of gamma: BN + ReLU follow on the pooled tensor); stats: fp64 (sum, sumsq) of the raw output
-int stem8pool_launch(const void* plane, const float* wp, const float* gamma, float* pooled, double* stats, int B, hipStream_t s) {
+int stem8pool_launch(const void* plane, const float* wp, const float* gamma, float* pooled, double* stats, int B, const GroupInfo& gi, hipStream_t s) {
     if (!plane || !wp || !gamma || !pooled || !stats) return fail(SAGEN_ERR_NULL, "stem8pool: null argument");
     static bool attr_set = false;
     if (!attr_set) {
@@ -375,15 +374,15 @@ int stem8pool_launch(const void* plane, const float* wp, const float* gamma, flo
     }
     const char* planes = reinterpret_cast<const char*>(wp + 64 * 224);
     const int npatch = B * 7 * 16;
-    hipLaunchKernelGGL(stem8pool_kernel<0>, dim3(2 * std::min(npatch, 256), 1, cur_group().G), dim3(S8_THREADS), S8_LDS, s, reinterpret_cast<const char*>(plane), wp, planes, gamma,
-                       pooled, stats, B, 0L, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, cur_group());
+    hipLaunchKernelGGL(stem8pool_kernel<0>, dim3(2 * std::min(npatch, 256), 1, gi.G), dim3(S8_THREADS), S8_LDS, s, reinterpret_cast<const char*>(plane), wp, planes, gamma,
+                       pooled, stats, B, 0L, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, gi);
     SAGEN_LAUNCH_CHECK();
     return SAGEN_OK;
 }
 
 // MODE 2: plane = stem8_prep's fp16 plane (half = 1); wp = the packed fp32 filter (for the constant term), wh2 = its two fp16 planes, w_inv = 2^-kw
 int stem8pool_h2_launch(const void* plane, const float* wp, const void* wh2, const float* w_inv, const float* gamma, float* pooled, double* stats, int B,
-                        hipStream_t s) {
+                        const GroupInfo& gi, hipStream_t s) {
     if (!plane || !wp || !wh2 || !w_inv || !gamma || !pooled || !stats) return fail(SAGEN_ERR_NULL, "stem8pool_h2: null argument");
     static bool attr_set = false;
     if (!attr_set) {
@@ -391,13 +390,14 @@ int stem8pool_h2_launch(const void* plane, const float* wp, const void* wh2, con
         attr_set = true;
     }
     const int npatch = B * 7 * 16;
-    hipLaunchKernelGGL((stem8pool_kernel<0, 2>), dim3(2 * std::min(npatch, 256), 1, cur_group().G), dim3(S8_THREADS), S8_LDS, s, reinterpret_cast<const char*>(plane), wp,
-                       reinterpret_cast<const char*>(wh2), gamma, pooled, stats, B, 0L, (const float*)nullptr, w_inv, (float*)nullptr, cur_group());
+    hipLaunchKernelGGL((stem8pool_kernel<0, 2>), dim3(2 * std::min(npatch, 256), 1, gi.G), dim3(S8_THREADS), S8_LDS, s, reinterpret_cast<const char*>(plane), wp,
+                       reinterpret_cast<const char*>(wh2), gamma, pooled, stats, B, 0L, (const float*)nullptr, w_inv, (float*)nullptr, gi);
     SAGEN_LAUNCH_CHECK();
     return SAGEN_OK;
 }
 
-// the same contraction without the pool: y0 [B,112,224,64] = the raw stem output (training step), statistics as above
+// the same contraction without the pool: y0 [B,112,224,64] = the raw stem output, statistics as above.  This one and stem8rawpool_launch
+// serve the training step only, which has no grouped launch: they take no group and hand the kernel a one-group GroupInfo
 int stem8raw_launch(const void* plane, const float* wp, float* y0, double* stats, int B, hipStream_t s) {
     if (!plane || !wp || !y0 || !stats) return fail(SAGEN_ERR_NULL, "stem8raw: null argument");
     static bool attr_set = false;
@@ -407,8 +407,8 @@ int stem8raw_launch(const void* plane, const float* wp, float* y0, double* stats
     }
     const char* planes = reinterpret_cast<const char*>(wp + 64 * 224);
     const int npatch = B * 7 * 16;
-    hipLaunchKernelGGL(stem8pool_kernel<1>, dim3(2 * std::min(npatch, 256), 1, cur_group().G), dim3(S8_THREADS), S8_LDS, s, reinterpret_cast<const char*>(plane), wp, planes,
-                       (const float*)nullptr, y0, stats, B, 0L, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, cur_group());
+    hipLaunchKernelGGL(stem8pool_kernel<1>, dim3(2 * std::min(npatch, 256)), dim3(S8_THREADS), S8_LDS, s, reinterpret_cast<const char*>(plane), wp, planes,
+                       (const float*)nullptr, y0, stats, B, 0L, (const float*)nullptr, (const float*)nullptr, (float*)nullptr, GroupInfo());
     SAGEN_LAUNCH_CHECK();
     return SAGEN_OK;
 }
@@ -423,8 +423,8 @@ int stem8rawpool_launch(const void* plane, const float* wp, const float* gamma, 
     }
     const char* planes = reinterpret_cast<const char*>(wp + 64 * 224);
     const int npatch = B * 7 * 16;
-    hipLaunchKernelGGL(stem8pool_kernel<2>, dim3(2 * std::min(npatch, 256), 1, cur_group().G), dim3(S8_THREADS), S8_LDS, s, reinterpret_cast<const char*>(plane), wp, planes,
-                       gamma, pooled, stats, B, 0L, (const float*)nullptr, (const float*)nullptr, y0, cur_group());
+    hipLaunchKernelGGL(stem8pool_kernel<2>, dim3(2 * std::min(npatch, 256)), dim3(S8_THREADS), S8_LDS, s, reinterpret_cast<const char*>(plane), wp, planes,
+                       gamma, pooled, stats, B, 0L, (const float*)nullptr, (const float*)nullptr, y0, GroupInfo());
     SAGEN_LAUNCH_CHECK();
     return SAGEN_OK;
 }
@@ -485,11 +485,10 @@ __global__ __launch_bounds__(256) void stem16_prep_kernel(const float* __restric
 
 // x: float frames [B,224,448,3]; planes: 2 * stem8_plane_bytes(B) bytes; part: S16_PARTS floats; a_inv: where 2^-ka goes;
 // zero_ptr / zero_n: a buffer the first launch clears on the way (the batch-norm accumulators)
-int stem16_prep_launch(const float* x, void* planes, float* part, float* a_inv, int B, hipStream_t s, float* zero_ptr, long zero_n) {
+int stem16_prep_launch(const float* x, void* planes, float* part, float* a_inv, int B, const GroupInfo& gi, hipStream_t s, float* zero_ptr, long zero_n) {
     if (!x || !planes || !part || !a_inv) return fail(SAGEN_ERR_NULL, "stem16_prep: null argument");
     const long n = (long)B * 224 * 448 * 3;
     if (n % 4 || ((uintptr_t)x % 16)) return fail(SAGEN_ERR_UNSUPPORTED, "stem16_prep: the frames must be 16-byte aligned");
-    const GroupInfo gi = cur_group();
     hipLaunchKernelGGL(stem16_amax_kernel, dim3(S16_PARTS, 1, gi.G), dim3(256), 0, s, x, n / 4, part, zero_ptr, zero_ptr ? zero_n : 0L, gi);
     const long total = (long)B * S8_UH * S8_UW;
     char* p = reinterpret_cast<char*>(planes);
@@ -501,7 +500,7 @@ int stem16_prep_launch(const float* x, void* planes, float* part, float* a_inv, 
 
 // planes: stem16_prep's output; wh2: the stem's filter as two fp16 planes [224/16][2][64][16] of w * 2^kw; a_inv / w_inv: the scales
 int stem16pool_launch(const void* planes, const void* wh2, const float* gamma, float* pooled, double* stats, const float* a_inv, const float* w_inv,
-                      int B, hipStream_t s) {
+                      int B, const GroupInfo& gi, hipStream_t s) {
     if (!planes || !wh2 || !gamma || !pooled || !stats || !a_inv || !w_inv) return fail(SAGEN_ERR_NULL, "stem16pool: null argument");
     static bool attr_set = false;
     if (!attr_set) {
@@ -509,8 +508,8 @@ int stem16pool_launch(const void* planes, const void* wh2, const float* gamma, f
         attr_set = true;
     }
     const int npatch = B * 7 * 16;
-    hipLaunchKernelGGL((stem8pool_kernel<0, 1>), dim3(2 * std::min(npatch, 256), 1, cur_group().G), dim3(S8_THREADS), S8_LDS, s, reinterpret_cast<const char*>(planes),
-                       (const float*)nullptr, reinterpret_cast<const char*>(wh2), gamma, pooled, stats, B, (long)stem8_plane_bytes(B), a_inv, w_inv, (float*)nullptr, cur_group());
+    hipLaunchKernelGGL((stem8pool_kernel<0, 1>), dim3(2 * std::min(npatch, 256), 1, gi.G), dim3(S8_THREADS), S8_LDS, s, reinterpret_cast<const char*>(planes),
+                       (const float*)nullptr, reinterpret_cast<const char*>(wh2), gamma, pooled, stats, B, (long)stem8_plane_bytes(B), a_inv, w_inv, (float*)nullptr, gi);
     SAGEN_LAUNCH_CHECK();
     return SAGEN_OK;
 }

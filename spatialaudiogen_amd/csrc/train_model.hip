@@ -251,7 +251,7 @@ struct Bwd : Fwd {
     int cslot = 0;
     std::string redws = "t:redws";                                // scratch of this launcher's channel reductions
     bool split_ok = getenv("SAGEN_BWD_NOSPLIT") == nullptr;      // debugging: no split-K in the data-gradient contractions
-    Bwd(sagen_ctx* ctx, hipStream_t st) { c = ctx; s = st; }
+    Bwd(sagen_ctx* ctx, hipStream_t st) : Fwd(ctx, st) {}
 
     // where variable v's gradient goes; the caller is about to enqueue the kernel that writes it (bucket milestones: ms_flush)
     float* grad(const std::string& v) {

@@ -830,7 +830,7 @@ int wgrad_launch(const WgradDesc& d_in, hipStream_t s) {
 int wgrad_reduce_launch(const WgradDesc& d, hipStream_t s) {
     static const bool use_ref = getenv("SAGEN_WGRAD_REF") != nullptr;
     if (d.splitk <= 1 || use_ref) return SAGEN_OK;
-    return splitk_reduce_launch(d.ws, d.splitk, d.TH * d.TW * d.Cg, d.Cd, nullptr, 0, d.out, d.Cd, 1, nullptr, s);
+    return splitk_reduce_launch(d.ws, d.splitk, d.TH * d.TW * d.Cg, d.Cd, nullptr, 0, d.out, d.Cd, 1, nullptr, GroupInfo(), s);
 }
 
 }  // namespace sagen

@@ -113,6 +113,35 @@ def test_grouped_autotune_and_forced_dh_split_keep_the_groups_exact(T):
     assert T.equal(grp.inference_ops(a, v), want)
 
 
+def test_tuning_on_fewer_groups_leaves_every_group_exact(T, monkeypatch):
+    """SAGEN_TUNE_GROUPS=1: the tuner times its candidates - their reducers too - on the first group only and then puts the group count
+    back.  A count left lowered, or a reducer run for another count than its contraction, would leave groups 1 and 2 stale or wrong."""
+    from spatialaudiogen_amd.model import SptAudioGen
+    monkeypatch.setenv('SAGEN_TUNE_GROUPS', '1')              # read per context, when it is created
+    enc, B, G = ['audio', 'video'], 2, 3
+    P = init_weights(variable_specs(enc), seed=14, mode='test')
+    inp = synth_inputs(G * B, enc, seed=80)
+    for g in range(G):
+        inp['audio'][g * B:(g + 1) * B] *= (1.0, 0.37, 1.9)[g % 3]
+    a, v = T.as_tensor(inp['audio']).cuda(), _u8(T, inp['video']).cuda()
+    grp = SptAudioGen(1, encoders=enc, separation='unet_mask', groups=G)
+    grp.load_variables(P)
+    plan = grp.autotune(a, v)
+    assert len(plan) >= 30
+    one = SptAudioGen(1, encoders=enc, separation='unet_mask')
+    one.load_variables(P)
+    one.inference_ops(a[:B], v[:B])
+    names = SptAudioGen.tile_names()
+    for layer, tile, sk, _ in plan:
+        one.plan_set(B, layer, names.index(tile), sk)
+    want = T.cat([one.inference_ops(a[g * B:(g + 1) * B], v[g * B:(g + 1) * B]) for g in range(G)], 0)
+    got = grp.inference_ops(a, v)
+    for g in range(G):
+        assert T.equal(got[g * B:(g + 1) * B], want[g * B:(g + 1) * B]), (g, float((got - want)[g * B:(g + 1) * B].abs().max()))
+    assert T.equal(grp.inference_ops(a, v), got)
+    assert grp.counter(B, 'fp16x2_saturations') == 0
+
+
 def test_grouped_contexts_refuse_what_they_cannot_run(T):
     from spatialaudiogen_amd.model import SptAudioGen
     from spatialaudiogen_amd._lib import SagenError

@@ -24,7 +24,7 @@ open(entry, 'w').write('''
 namespace sagen { char* err_buf() { static thread_local char b[512]; return b; }
 int fail(int code, const char* fmt, ...) { va_list ap; va_start(ap, fmt); vsnprintf(err_buf(), 512, fmt, ap); va_end(ap); fprintf(stderr, "%%s\\n", err_buf()); return code; } }
 using namespace sagen;
-extern "C" int p3dbg_pack(const float* x, void* p3, int B, int H, int W, int C, void* s) { return p3_pack_launch(x, nullptr, nullptr, BnRef(), nullptr, 0, nullptr, p3, B, H, W, C, (hipStream_t)s); }
+extern "C" int p3dbg_pack(const float* x, void* p3, int B, int H, int W, int C, void* s) { return p3_pack_launch(x, nullptr, nullptr, BnRef(), nullptr, 0, nullptr, p3, B, H, W, C, GroupInfo(), (hipStream_t)s); }
 extern "C" int p3dbg_conv(const void* p3, const float* w, float* y, double* stats, void* trace, int B, int H, int W, int C, int N, int tile, void* s) {
     IgemmDesc d;
     d.w = w; d.y = y; d.stats = stats; d.w_split = 1;
