@@ -513,6 +513,68 @@ int sagen_resample_fir(const float* x, int64_t x0, int64_t n_in, int c_in, const
 int sagen_window_rms(const float* x, int64_t n, int channels, int channel, int64_t first, int64_t hop, int64_t length, int64_t count,
                      double* rms, void* stream);
 
+/* ---- baseline JPEG decode ---------------------------------------------------------------------------------------------------
+ * The reference reads every frame with skimage / PIL on the host (feeder.py:18-23 behind the video and flow readers; the scraping
+ * tools likewise) - libjpeg.  sagen_jpeg_decode takes the FILE BYTES of n frames on the device and writes out [n][h][w][3] uint8
+ * RGB, the layout sagen_reproject, sagen_optical_flow, sagen_overlay_blend and sagen_forward_u8 read, byte for byte what libjpeg's
+ * default decode path gives (PIL's Image.open(...).convert('RGB')): integer arithmetic end to end.
+ *
+ * Scope: baseline sequential DCT (SOF0), 8-bit samples, Huffman coding, ONE interleaved scan; components = 1 (grey, replicated to
+ * R = G = B; hs = vs = 1) or 3 (YCbCr, luma sampling (hs, vs) in {(1, 1), (2, 1), (2, 2)}, chroma (1, 1)); an optional restart
+ * interval.  All frames of a call share width, height, components, hs, vs; tables, restart interval and scan length are per frame.
+ * The marker walk is the caller's (spatialaudiogen_amd/jpeg.py); the library sees:
+ *   bytes     [total_bytes] uint8 DEVICE: the files (or just their scans), concatenated; 4-byte aligned, total_bytes a multiple of 4
+ *             (the caller pads): the entropy stage refills its bit window by aligned 32-bit loads and reads nothing outside
+ *   frames    [n] sagen_jpeg_frame DEVICE (64 bytes each)
+ *   segments  [n_segments][2] int32 DEVICE: (frame, offset of the segment's first byte inside that frame's scan).  A frame without
+ *             restart interval has one segment at offset 0; with an interval of R MCUs it has ceil(MCUs / R), segment k > 0 starting
+ *             right behind the marker FF D0+((k-1) & 7); a segment ends 2 bytes before the next one, the last at the scan's end.
+ *             Frame f owns the rows first_segment .. first_segment + n_segments - 1
+ *   qtabs     [n_qtabs][64] uint16 DEVICE: quantisation tables in the file's (zigzag) order
+ *   hufftabs  [n_hufftabs][272] uint8 DEVICE: 16 counts (codes of length 1..16) + 256 symbols, as in DHT (unused symbols: any value)
+ *   status    [n] int32 DEVICE: 0, or a set of SAGEN_JPEG_ST_* bits; a frame with a non-zero status has unspecified pixels, every
+ *             other frame of the call is exact
+ * Entropy decode: one lane per segment: Huffman decode (8-bit lookahead table + code-length search), EXTEND, DC prediction per
+ * component reset at every segment, EOB / ZRL, FF 00 unstuffing, coefficients to natural order.  Dequantisation coef * q[k], the
+ * "islow" inverse DCT (CONST_BITS 13, PASS1_BITS 2: columns (x + 1024) >> 11, rows (x + 2^17) >> 18, + 128, clamped), "fancy"
+ * triangle chroma upsampling on the ceil(w / hs) x ceil(h / vs) plane (edges replicated at THOSE bounds), and
+ * R = y + ((91881 cr + 32768) >> 16), G = y + ((-22554 cb - 46802 cr + 32768) >> 16), B = y + ((116130 cb + 32768) >> 16), clamped.
+ * Every >> is an arithmetic shift of a signed 32-bit integer.  For coefficients an encoder can make from 8-bit samples every
+ * product stays inside 32 bits; where a hostile stream overflows them the arithmetic wraps modulo 2^32 (defined, pixels unspecified).
+ * Hostile bytes: every loop is bounded by the geometry (MCUs x blocks x 64 coefficients x 16 code bits); a lane that needs bits
+ * past its segment's end reads zeros and sets SAGEN_JPEG_ST_OVERRUN; descriptors are checked on the device before they are used
+ * (SAGEN_JPEG_ST_DESC: offsets outside bytes, table indices outside the tables, a segment list that is not the frame's).
+ * Returns: n == 0 SAGEN_OK, nothing touched; a null argument SAGEN_ERR_NULL; SAGEN_ERR_SHAPE for n < 0, w or h < 1, total_bytes < 0
+ * or not a multiple of 4, n_segments < n, a table count < 1, bytes / frames / segments / qtabs / scratch misaligned (4, 8, 4, 2, 16
+ * bytes; status 4); SAGEN_ERR_UNSUPPORTED for components / sampling outside the scope, w or h above 16384, n > 65535, more than
+ * 2^31 - 1 blocks, output bytes or file bytes per call, more than 65536 tables of a kind; SAGEN_ERR_WORKSPACE for scratch smaller than sagen_jpeg_decode_scratch_bytes(...).  A refused
+ * call writes nothing.  sagen_jpeg_decode_scratch_bytes is 0 for a geometry the call would refuse. */
+enum {
+    SAGEN_JPEG_ST_OVERRUN = 1,   /* bits needed past the end of a segment (truncated stream) */
+    SAGEN_JPEG_ST_CODE = 2,      /* a bit pattern that is no code of the table */
+    SAGEN_JPEG_ST_INDEX = 4,     /* a run past coefficient 63 */
+    SAGEN_JPEG_ST_MARKER = 8,    /* a marker inside a segment, or not the expected restart marker in front of it */
+    SAGEN_JPEG_ST_DESC = 16,     /* the frame's descriptor or segment rows are inconsistent */
+    SAGEN_JPEG_ST_TABLE = 32,    /* a Huffman table that is no prefix code (or lists more than 256 symbols) */
+    SAGEN_JPEG_ST_RANGE = 64,    /* a magnitude category above baseline's (DC 11, AC 10), or a DC value outside 16 bits */
+    SAGEN_JPEG_ST_TRAILING = 128 /* bytes left in a segment after its last MCU */
+};
+typedef struct sagen_jpeg_frame {
+    int64_t scan_offset;        /* offset in `bytes` of the first entropy-coded byte (behind the SOS header) */
+    int32_t scan_bytes;         /* length of the entropy-coded data, restart markers included, the EOI marker not */
+    int32_t restart_interval;   /* MCUs per segment; 0: none */
+    int32_t first_segment;      /* row of `segments` */
+    int32_t n_segments;
+    int32_t qtab[3];            /* per component: row of qtabs */
+    int32_t dctab[3];           /* per component: row of hufftabs */
+    int32_t actab[3];
+    int32_t reserved;           /* 0 */
+} sagen_jpeg_frame;             /* 64 bytes */
+size_t sagen_jpeg_decode_scratch_bytes(int n, int w, int h, int components, int hs, int vs, int n_hufftabs);
+int sagen_jpeg_decode(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_frame* frames, int n, const int32_t* segments,
+                      int n_segments, const uint16_t* qtabs, int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, int w, int h,
+                      int components, int hs, int vs, uint8_t* out, int32_t* status, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- moving point sources: encode to ambisonics, binauralise, track ------------------------------------------------------
  * The front end of the reference's ambisonics toolbox: AmbiEncoder.encode / encode_frame / encode_v2 (pyutils/ambisonics/
  * encoder.py:10-55), SourceBinauralizer over VirtualStereoMic and Convolvotron, static and per frame (binauralizer.py:12-121), and

@@ -10,6 +10,7 @@ SAGEN_ENC_AUDIO, SAGEN_ENC_VIDEO, SAGEN_ENC_FLOW = 1, 2, 4
 SAGEN_SEP_NONE, SAGEN_SEP_FREQ_MASK = 0, 1
 SAGEN_SOURCES_MIC, SAGEN_SOURCES_HRIR = 0, 1
 SAGEN_PROJ_ER, SAGEN_PROJ_CUBE, SAGEN_PROJ_EAC, SAGEN_PROJ_VIEW = 0, 1, 2, 3
+SAGEN_JPEG_STATUS = {1: 'overrun', 2: 'code', 4: 'index', 8: 'marker', 16: 'descriptor', 32: 'table', 64: 'range', 128: 'trailing'}
 
 
 class SagenError(RuntimeError):
@@ -41,6 +42,12 @@ class SagenProjection(C.Structure):
 class SagenFlowParams(C.Structure):
     _fields_ = [('levels', C.c_int32), ('warps', C.c_int32), ('iters', C.c_int32), ('wrap', C.c_int32), ('fuse', C.c_int32),
                 ('alpha', C.c_double)]
+
+
+class SagenJpegFrame(C.Structure):
+    _fields_ = [('scan_offset', C.c_int64), ('scan_bytes', C.c_int32), ('restart_interval', C.c_int32), ('first_segment', C.c_int32),
+                ('n_segments', C.c_int32), ('qtab', C.c_int32 * 3), ('dctab', C.c_int32 * 3), ('actab', C.c_int32 * 3),
+                ('reserved', C.c_int32)]
 
 
 # every symbol include/sagen.h declares: name -> (restype, argtypes)
@@ -114,6 +121,8 @@ SIGNATURES = {
     'sagen_flow_encode_scratch_bytes': (_SZ, [_I] * 3),
     'sagen_flow_encode': (C.c_int, [_P, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     'sagen_resample_fir': (C.c_int, [_P, _I64, _I64, _I, _P, _I, _I, _I, _I, _P, _I, _I64, _I64, _P, _P]),
+    'sagen_jpeg_decode_scratch_bytes': (_SZ, [_I] * 7),
+    'sagen_jpeg_decode': (C.c_int, [_P, _I64, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
     'sagen_window_rms': (C.c_int, [_P, _I64, _I, _I, _I64, _I64, _I64, _I64, _P, _P]),
     'sagen_source_track': (C.c_int, [_P, _P, _P, _P, _I, C.c_double, _I64, _I64, _I64, _P, _I, _P, _P, _P]),
     'sagen_encode_sources': (C.c_int, [_P, _I64, _P, _P, _P, _P, _I, C.c_double, _I, _I, C.c_double, _I64, _I64, _P, _P]),

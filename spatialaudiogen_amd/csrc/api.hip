@@ -5,6 +5,7 @@
 #include "project_core.h"
 #include "flow_core.h"
 #include "resample_core.h"
+#include "jpeg_core.h"
 #include <new>
 #include <cstdlib>
 #include <algorithm>
@@ -698,6 +699,28 @@ int sagen_resample_fir(const float* x, int64_t x0, int64_t n_in, int c_in, const
         return fail(rc, "sagen_resample_fir: %s (x0=%ld n_in=%ld c_in=%d L=%d M=%d H=%d T=%d c_out=%d n0=%ld n=%ld)", why, (long)x0, (long)n_in,
                     c_in, L, M, H, T, c_out, (long)n0, (long)n);
     return rc;
+}
+
+size_t sagen_jpeg_decode_scratch_bytes(int n, int w, int h, int components, int hs, int vs, int n_hufftabs) {
+    JpegGeom g;
+    const char* why;
+    if (n <= 0 || n_hufftabs < 1 || n_hufftabs > 65536 || jpeg_geom_fill(g, n, w, h, components, hs, vs, &why) != SAGEN_OK) return 0;
+    return jpeg_scratch_layout(g, n_hufftabs).total;
+}
+
+int sagen_jpeg_decode(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_frame* frames, int n, const int32_t* segments,
+                      int n_segments, const uint16_t* qtabs, int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, int w, int h,
+                      int components, int hs, int vs, uint8_t* out, int32_t* status, void* scratch, size_t scratch_bytes, void* stream) {
+    if (n == 0) return SAGEN_OK;
+    JpegGeom g;
+    const char* why;
+    const int rc = jpeg_args_check(g, bytes, total_bytes, frames, n, segments, n_segments, qtabs, n_qtabs, hufftabs, n_hufftabs, w, h, components,
+                                   hs, vs, out, status, scratch, scratch_bytes, &why);
+    if (rc != SAGEN_OK)
+        return fail(rc, "sagen_jpeg_decode: %s (n=%d %dx%d components=%d sampling %dx%d total_bytes=%ld n_segments=%d n_qtabs=%d n_hufftabs=%d "
+                    "scratch_bytes=%zu)", why, n, w, h, components, hs, vs, (long)total_bytes, n_segments, n_qtabs, n_hufftabs, scratch_bytes);
+    return jpeg_decode_launch(bytes, total_bytes, frames, segments, n_segments, qtabs, n_qtabs, hufftabs, n_hufftabs, g, out, status, scratch,
+                              (hipStream_t)stream);
 }
 
 int sagen_window_rms(const float* x, int64_t n, int channels, int channel, int64_t first, int64_t hop, int64_t length, int64_t count,

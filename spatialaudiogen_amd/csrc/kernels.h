@@ -411,6 +411,15 @@ int window_rms_launch(const float* x, int channels, int channel, long long first
                       double* rms, hipStream_t s);
 
 // -----------------------------------------------------------------------------------------
+// baseline JPEG decode (jpeg.hip): sagen_jpeg_decode of include/sagen.h; JpegGeom is jpeg_core.h's, checked and filled by
+// jpeg_args_check; scratch as jpeg_scratch_layout carves it
+// -----------------------------------------------------------------------------------------
+struct JpegGeom;
+int jpeg_decode_launch(const uint8_t* bytes, long long total_bytes, const sagen_jpeg_frame* frames, const int32_t* segments, int n_segments,
+                       const uint16_t* qtabs, int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, const JpegGeom& g, uint8_t* out,
+                       int32_t* status, void* scratch, hipStream_t s);
+
+// -----------------------------------------------------------------------------------------
 // training-step pieces (train.hip): stft loss + gradient w.r.t. the prediction, fused Adam over a flat bucket
 // -----------------------------------------------------------------------------------------
 int stft_loss_grad_launch(const float* pred, const float* gt, const float* mask, int B, float* grad, double* loss, hipStream_t s);

@@ -24,6 +24,7 @@
 #include "../csrc/project_core.h"
 #include "../csrc/flow_core.h"
 #include "../csrc/resample_core.h"
+#include "../csrc/jpeg_core.h"
 
 namespace {
 
@@ -822,6 +823,28 @@ int sagen_window_rms(const float* x, int64_t n, int channels, int channel, int64
         for (int l = 0; l < RMS_LANES; ++l) p[l] = rms_partial(x, first + i * hop, channels, channel, length, l);
         rms[i] = rms_finish_host(p, length);
     }
+    return SAGEN_OK;
+}
+
+/* Baseline JPEG decode (include/sagen.h: sagen_jpeg_decode; PIL / libjpeg behind feeder.py:18-23 in the reference): the five stages
+ * of csrc/jpeg.hip as plain loops over the integer core the device uses (csrc/jpeg_core.h: jpeg_decode_host) */
+size_t sagen_jpeg_decode_scratch_bytes(int n, int w, int h, int components, int hs, int vs, int n_hufftabs) {
+    sagen::JpegGeom g;
+    const char* why;
+    if (n <= 0 || n_hufftabs < 1 || n_hufftabs > 65536 || sagen::jpeg_geom_fill(g, n, w, h, components, hs, vs, &why) != SAGEN_OK) return 0;
+    return sagen::jpeg_scratch_layout(g, n_hufftabs).total;
+}
+
+int sagen_jpeg_decode(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_frame* frames, int n, const int32_t* segments,
+                      int n_segments, const uint16_t* qtabs, int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, int w, int h,
+                      int components, int hs, int vs, uint8_t* out, int32_t* status, void* scratch, size_t scratch_bytes, void*) {
+    if (n == 0) return SAGEN_OK;
+    sagen::JpegGeom g;
+    const char* why;
+    const int rc = sagen::jpeg_args_check(g, bytes, total_bytes, frames, n, segments, n_segments, qtabs, n_qtabs, hufftabs, n_hufftabs, w, h,
+                                          components, hs, vs, out, status, scratch, scratch_bytes, &why);
+    if (rc != SAGEN_OK) return fail(rc, "sagen_jpeg_decode: %s", why);
+    sagen::jpeg_decode_host(bytes, total_bytes, frames, segments, n_segments, qtabs, n_qtabs, hufftabs, n_hufftabs, g, out, status, scratch);
     return SAGEN_OK;
 }
 

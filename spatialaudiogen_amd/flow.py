@@ -95,8 +95,9 @@ class FlowEstimator(object):
         return ops.optical_flow(torch.cat([first, frames], 0), self.params.struct(h, w))
 
 
-def write_flow_folder(video_dir, flow_dir, params=None, block=64, fmt='jpg', device=None):
-    """Flow folder of the frames %06d.jpg of video_dir: flow_dir/%06d.<fmt> + flow_dir/flow_limits.npy.  Returns (n, h, w, levels)."""
+def write_flow_folder(video_dir, flow_dir, params=None, block=64, fmt='jpg', device=None, decode='host'):
+    """Flow folder of the frames %06d.jpg of video_dir: flow_dir/%06d.<fmt> + flow_dir/flow_limits.npy.  Returns (n, h, w, levels).
+    decode 'device': the frames are decoded on the device (jpeg.load_frames_device) instead of by PIL on the host; same pixels."""
     import torch
     from .overlay import frame_names, load_frames
     from .project import save_frames
@@ -107,9 +108,12 @@ def write_flow_folder(video_dir, flow_dir, params=None, block=64, fmt='jpg', dev
     est = FlowEstimator(params, device)
     from . import ops
     limits, prev, hw = [], None, None
+    if decode == 'device':
+        from .jpeg import JpegDecoder
+        decoder = JpegDecoder(est.device)
     for first, stop in block_ranges(len(names), block):
         start = first if prev is None else first + 1
-        frames = torch.as_tensor(load_frames(names[start:stop])).to(est.device)
+        frames = decoder.decode(names[start:stop]) if decode == 'device' else torch.as_tensor(load_frames(names[start:stop])).to(est.device)
         flow = est.process(frames, prev)
         rgb, lim = ops.flow_encode(flow)
         save_frames(flow_dir, rgb.cpu().numpy(), start, fmt)
@@ -143,6 +147,7 @@ def parse_arguments(argv=None):
     parser.add_argument('--format', default='jpg', choices=['jpg', 'png'], help='jpg (quality 95: what the feeder reads) or png (lossless)')
     parser.add_argument('--overwrite', action='store_true', help='Whether to replace a flow folder that is not empty.')
     parser.add_argument('--gpu', type=int, default=0, help='GPU id')
+    parser.add_argument('--decode', default='host', choices=['host', 'device'], help="where the input frames are decoded: host (PIL, one thread) or device (jpeg.py: the files' bytes go to the device; same pixels)")
     return parser.parse_args(argv)
 
 
@@ -171,7 +176,7 @@ def main(argv=None):
     _lib.lib()
     if not _lib.IS_CPU_TWIN:
         torch.cuda.set_device(args.gpu)
-    n, h, w, levels = write_flow_folder(args.video_dir, args.flow_dir, params, args.block, args.format)
+    n, h, w, levels = write_flow_folder(args.video_dir, args.flow_dir, params, args.block, args.format, decode=args.decode)
     print('wrote %d flow frames of %dx%d to %s (levels %d, warps %d, iters %d)' % (n, h, w, args.flow_dir, levels, params.warps, params.iters))
 
 

@@ -1,0 +1,334 @@
+"""Baseline JPEG frames decoded on the device (include/sagen.h: sagen_jpeg_decode, csrc/jpeg.hip): the host walks the markers,
+the device gets the file bytes and produces [N, H, W, 3] uint8, byte for byte what PIL's Image.open(...).convert('RGB') gives
+(libjpeg's default path).  It stands in for feeder.imread (feeder.py:18-23 in the reference) in front of the frame consumers.
+
+    parse(data)                         -> JpegInfo, JpegUnsupported(reason) outside the scope, ValueError for no JPEG at all
+    JpegDecoder(device).decode(items)   -> torch.uint8 [N, H, W, 3] on the device; items: bytes or paths
+    load_frames_device(names, device)   the drop-in for torch.as_tensor(overlay.load_frames(names)).to(device)
+
+Scope (the header has the details): SOF0, 8 bit, Huffman, one interleaved scan, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0, optional
+restart interval.  A file outside it is decoded by feeder.imread and copied in, with one warning per decoder.
+"""
+import collections
+import ctypes as C
+import warnings
+
+import numpy as np
+
+from . import _lib
+
+JpegInfo = collections.namedtuple('JpegInfo', 'width height components hs vs qtabs dctabs actabs restart_interval scan_offset scan_bytes segments')
+JpegInfo.__doc__ = """What the device needs of one file.  qtabs: per component 64 uint16 in the file's (zigzag) order; dctabs / actabs: per
+component 272 bytes (16 counts + 256 symbols, unused symbols zero); scan_offset / scan_bytes: the entropy-coded data (restart markers
+included, EOI not); segments: int32 offsets inside the scan of each restart segment's first byte (one zero without an interval)."""
+
+FRAME_DTYPE = np.dtype([('scan_offset', '<i8'), ('scan_bytes', '<i4'), ('restart_interval', '<i4'), ('first_segment', '<i4'),
+                        ('n_segments', '<i4'), ('qtab', '<i4', 3), ('dctab', '<i4', 3), ('actab', '<i4', 3), ('reserved', '<i4')])
+assert FRAME_DTYPE.itemsize == C.sizeof(_lib.SagenJpegFrame) == 64
+HUFF_SPEC = 272
+MAX_DIM = 16384
+
+_SOF_NAMES = {0xC1: 'extended sequential DCT', 0xC2: 'progressive DCT', 0xC3: 'lossless', 0xC5: 'differential sequential DCT',
+              0xC6: 'differential progressive DCT', 0xC7: 'differential lossless', 0xC9: 'arithmetic coding', 0xCA: 'arithmetic coding',
+              0xCB: 'arithmetic coding', 0xCD: 'arithmetic coding', 0xCE: 'arithmetic coding', 0xCF: 'arithmetic coding'}
+
+
+class JpegFallbackWarning(UserWarning):
+    """A file outside the device decoder's scope was decoded on the host."""
+
+
+class JpegUnsupported(Exception):
+    """A JPEG file outside what the device decodes; .reason says why."""
+
+    def __init__(self, reason):
+        Exception.__init__(self, reason)
+        self.reason = reason
+
+
+def _be16(data, pos):
+    return (data[pos] << 8) | data[pos + 1]
+
+
+def parse(data):
+    """The marker walk: SOI, APPn, DQT, DHT, SOF0, DRI, SOS; restart markers and the end of the scan from one vectorised search."""
+    data = bytes(data)
+    if len(data) < 4 or data[0] != 0xFF or data[1] != 0xD8:
+        raise ValueError('not a JPEG file (no SOI marker)')
+    qt, dc, ac = {}, {}, {}
+    sof, restart, adobe = None, 0, None
+    pos, n = 2, len(data)
+    while True:
+        if pos + 4 > n:
+            raise ValueError('JPEG file ends before a scan')
+        if data[pos] != 0xFF:
+            raise ValueError('JPEG file: no marker at byte %d' % pos)
+        while pos < n and data[pos] == 0xFF:
+            pos += 1
+        if pos >= n:
+            raise ValueError('JPEG file ends inside a marker')
+        m = data[pos]
+        pos += 1
+        if m == 0x01 or 0xD0 <= m <= 0xD7:
+            continue
+        if m == 0xD9:
+            raise ValueError('JPEG file ends before a scan')
+        if pos + 2 > n:
+            raise ValueError('JPEG file ends inside a marker segment')
+        length = _be16(data, pos)
+        if length < 2 or pos + length > n:
+            raise ValueError('JPEG file: marker segment of %d bytes at byte %d' % (length, pos))
+        body = data[pos + 2:pos + length]
+        if m in _SOF_NAMES:
+            raise JpegUnsupported(_SOF_NAMES[m])
+        if m == 0xC0:
+            if sof is not None or len(body) < 6 or len(body) != 6 + 3 * body[5]:
+                raise ValueError('JPEG file: bad frame header')
+            if body[0] != 8:
+                raise JpegUnsupported('%d-bit samples' % body[0])
+            sof = (_be16(body, 1), _be16(body, 3), [(body[6 + 3 * i], body[7 + 3 * i] >> 4, body[7 + 3 * i] & 15, body[8 + 3 * i]) for i in range(body[5])])
+        elif m == 0xC4:
+            i = 0
+            while i < len(body):
+                if i + 17 > len(body):
+                    raise ValueError('JPEG file: bad Huffman table')
+                counts = body[i + 1:i + 17]
+                total = sum(counts)
+                if total > 256 or i + 17 + total > len(body) or (body[i] & 15) > 3 or (body[i] >> 4) > 1:
+                    raise ValueError('JPEG file: bad Huffman table')
+                (ac if body[i] >> 4 else dc)[body[i] & 15] = counts + body[i + 17:i + 17 + total] + bytes(256 - total)
+                i += 17 + total
+        elif m == 0xDB:
+            i = 0
+            while i < len(body):
+                if body[i] >> 4:
+                    raise JpegUnsupported('16-bit quantisation tables')
+                if i + 65 > len(body) or (body[i] & 15) > 3:
+                    raise ValueError('JPEG file: bad quantisation table')
+                qt[body[i] & 15] = np.frombuffer(body, np.uint8, 64, i + 1).astype(np.uint16)
+                i += 65
+        elif m == 0xDD:
+            if len(body) != 2:
+                raise ValueError('JPEG file: bad restart interval')
+            restart = _be16(body, 0)
+        elif m == 0xEE and len(body) >= 12 and body[:5] == b'Adobe':
+            adobe = body[11]
+        elif m == 0xDA:
+            break
+        pos += length
+    if sof is None:
+        raise ValueError('JPEG file: a scan before the frame header')
+    height, width, comps = sof
+    if len(comps) == 4:
+        raise JpegUnsupported('four components (CMYK / YCCK)')
+    if len(comps) not in (1, 3):
+        raise JpegUnsupported('%d components' % len(comps))
+    if width < 1 or height < 1:
+        raise ValueError('JPEG file: an empty frame (or a height left to a DNL marker)')
+    if width > MAX_DIM or height > MAX_DIM:
+        raise JpegUnsupported('a dimension above %d' % MAX_DIM)
+    if len(body) < 1 or len(body) != 4 + 2 * body[0]:
+        raise ValueError('JPEG file: bad scan header')
+    if body[0] != len(comps):
+        raise JpegUnsupported('more than one scan')
+    ss, se, ahal = body[1 + 2 * body[0]:]
+    if (ss, se, ahal) != (0, 63, 0):
+        raise JpegUnsupported('a scan of part of the spectrum')
+    if len(comps) == 3:
+        if [c[0] for c in comps] == [ord('R'), ord('G'), ord('B')]:
+            raise JpegUnsupported('component ids R, G, B (no YCbCr)')
+        if adobe is not None and adobe != 1:
+            raise JpegUnsupported('Adobe marker with transform %d (no YCbCr)' % adobe)
+        hs, vs = comps[0][1], comps[0][2]
+        if (hs, vs) not in ((1, 1), (2, 1), (2, 2)) or any((c[1], c[2]) != (1, 1) for c in comps[1:]):
+            raise JpegUnsupported('sampling factors %s' % ', '.join('%dx%d' % (c[1], c[2]) for c in comps))
+    else:
+        hs, vs = 1, 1                                     # one component: the scan is not interleaved, whatever the factors say
+    qtabs, dctabs, actabs = [], [], []
+    for i, (cid, _, _, tq) in enumerate(comps):
+        if body[1 + 2 * i] != cid:
+            raise ValueError('JPEG file: the scan names component %d, the frame %d' % (body[1 + 2 * i], cid))
+        td, ta = body[2 + 2 * i] >> 4, body[2 + 2 * i] & 15
+        if tq not in qt or td not in dc or ta not in ac:
+            raise ValueError('JPEG file: component %d uses a table the file does not define' % cid)
+        qtabs.append(qt[tq]), dctabs.append(dc[td]), actabs.append(ac[ta])
+    scan_offset = pos + length
+    # the scan ends at the first FF that is followed by neither 00 (a stuffed FF), D0..D7 (a restart marker) nor FF (fill)
+    a = np.frombuffer(data, np.uint8, n - scan_offset, scan_offset)
+    ff = np.flatnonzero(a[:-1] == 0xFF) if a.size > 1 else np.zeros(0, np.int64)
+    nxt = a[ff + 1]
+    ends = ff[(nxt != 0) & (nxt != 0xFF) & ((nxt < 0xD0) | (nxt > 0xD7))]
+    if ends.size == 0:
+        raise ValueError('JPEG file: the scan does not end (truncated file)')
+    scan_bytes = int(ends[0])
+    if a[scan_bytes + 1] != 0xD9:
+        raise JpegUnsupported('more than one scan')
+    while scan_bytes > 0 and a[scan_bytes - 1] == 0xFF:    # fill bytes in front of EOI belong to the marker
+        scan_bytes -= 1
+    inside = ff[ff < scan_bytes]
+    rst = inside[(a[inside + 1] >= 0xD0) & (a[inside + 1] <= 0xD7)]
+    segments = np.concatenate([np.zeros(1, np.int64), rst + 2]).astype(np.int32)
+    mcus = -(-width // (8 * hs)) * -(-height // (8 * vs))
+    want = -(-mcus // restart) if restart else 1
+    if segments.size != want:
+        raise ValueError('JPEG file: %d restart markers, a restart interval of %d MCUs over %d MCUs needs %d' % (segments.size - 1, restart, mcus, want - 1))
+    return JpegInfo(width, height, len(comps), hs, vs, qtabs, dctabs, actabs, restart, scan_offset, scan_bytes, segments)
+
+
+Packed = collections.namedtuple('Packed', 'buffer bytes_at total_bytes frames_at n segments_at n_segments qtabs_at n_qtabs hufftabs_at n_hufftabs geometry')
+Packed.__doc__ = """One call's host side: `buffer` (numpy uint8) holds frames | segments | qtabs | hufftabs | file bytes at the *_at offsets
+(each a multiple of 16), total_bytes is padded to a multiple of 4; geometry = (width, height, components, hs, vs)."""
+
+
+def _align16(x):
+    return (x + 15) // 16 * 16
+
+
+def pack(datas, infos, buffer_factory=None):
+    """Descriptors and tables of frames of ONE geometry, tables de-duplicated, everything in one staging buffer (buffer_factory(nbytes)
+    -> writable numpy uint8, e.g. the view of a pinned tensor; default: plain numpy)."""
+    geometry = tuple(infos[0][:5])
+    if any(tuple(i[:5]) != geometry for i in infos):
+        raise ValueError('pack() takes frames of one geometry')
+    qindex, hindex = {}, {}
+    frames = np.zeros(len(infos), FRAME_DTYPE)
+    seg_rows, offset = [], 0
+    for f, (d, i) in enumerate(zip(datas, infos)):
+        fr = frames[f]
+        fr['scan_offset'], fr['scan_bytes'], fr['restart_interval'] = offset + i.scan_offset, i.scan_bytes, i.restart_interval
+        fr['first_segment'], fr['n_segments'] = sum(r.shape[0] for r in seg_rows), i.segments.size
+        seg_rows.append(np.stack([np.full(i.segments.size, f, np.int32), i.segments], 1))
+        for c in range(i.components):
+            fr['qtab'][c] = qindex.setdefault(i.qtabs[c].tobytes(), len(qindex))
+            fr['dctab'][c] = hindex.setdefault(i.dctabs[c], len(hindex))
+            fr['actab'][c] = hindex.setdefault(i.actabs[c], len(hindex))
+        offset += len(d)
+    total = (offset + 3) // 4 * 4
+    segs = np.concatenate(seg_rows, 0)
+    parts = [frames.tobytes(), segs.tobytes(), b''.join(qindex), b''.join(hindex)]     # (dicts keep insertion order: index order)
+    at, size = [], 0
+    for p in parts:
+        at.append(size)
+        size = _align16(size + len(p))
+    buf = (buffer_factory or (lambda nbytes: np.zeros(nbytes, np.uint8)))(size + total)
+    for a, p in zip(at, parts):
+        buf[a:a + len(p)] = np.frombuffer(p, np.uint8)
+    pos = size
+    for d in datas:
+        buf[pos:pos + len(d)] = np.frombuffer(d, np.uint8)
+        pos += len(d)
+    buf[pos:size + total] = 0
+    return Packed(buf, size, total, at[0], len(infos), at[1], segs.shape[0], at[2], len(qindex), at[3], len(hindex), geometry)
+
+
+def decode_packed(packed, staged, out=None):
+    """sagen_jpeg_decode on `staged`, the uint8 tensor holding packed.buffer where the library reads (device memory; the host with
+    the CPU twin).  Returns (out [n, h, w, 3] uint8, status [n] int32) on that device; nothing is synchronised."""
+    import torch
+    from .ops import _ptr, _stream
+    l = _lib.lib()
+    w, h, comps, hs, vs = packed.geometry
+    n = packed.n
+    if out is None:
+        out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=staged.device)
+    status = torch.empty(n, dtype=torch.int32, device=staged.device)
+    nbytes = int(l.sagen_jpeg_decode_scratch_bytes(n, w, h, comps, hs, vs, packed.n_hufftabs))
+    scratch = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=staged.device)
+    base = staged.data_ptr()
+    at = lambda off: C.c_void_p(base + off)
+    _lib.check(l.sagen_jpeg_decode(at(packed.bytes_at), packed.total_bytes, at(packed.frames_at), n, at(packed.segments_at), packed.n_segments,
+                                   at(packed.qtabs_at), packed.n_qtabs, at(packed.hufftabs_at), packed.n_hufftabs, w, h, comps, hs, vs,
+                                   _ptr(out), _ptr(status), _ptr(scratch), nbytes, _stream()))
+    return out, status
+
+
+def status_text(code):
+    return ' + '.join(name for bit, name in sorted(_lib.SAGEN_JPEG_STATUS.items()) if code & bit) or 'ok'
+
+
+class JpegDecoder(object):
+    """decode(items) -> uint8 [N, H, W, 3] on the device, in the order of `items` (bytes objects or paths of files).  Frames of
+    several geometries (sampling, grey / colour) are decoded a group at a time; all must have one size.  `timing`, when set to a
+    dict, receives 'parse' and 'pack' in host seconds of the last call."""
+
+    def __init__(self, device=None):
+        import torch
+        _lib.lib()
+        self.device = torch.device(device if device is not None else ('cpu' if _lib.IS_CPU_TWIN else 'cuda'))
+        self._warned = False
+        self.timing = None
+
+    def _staging(self, nbytes):
+        import torch
+        self._pinned = torch.empty(nbytes, dtype=torch.uint8, pin_memory=self.device.type == 'cuda')
+        return self._pinned.numpy()
+
+    def decode(self, items):
+        import time
+        import torch
+        t0 = time.perf_counter()
+        names = [it if isinstance(it, str) else '<item %d>' % k for k, it in enumerate(items)]
+        datas = []
+        for it in items:
+            if isinstance(it, str):
+                with open(it, 'rb') as f:
+                    datas.append(f.read())
+            else:
+                datas.append(bytes(it))
+        groups, fallback, size = collections.OrderedDict(), [], None
+        for k, d in enumerate(datas):
+            try:
+                info = parse(d)
+                this = (info.width, info.height)
+                groups.setdefault(tuple(info[:5]), []).append((k, info))
+            except JpegUnsupported as e:
+                if not self._warned:
+                    warnings.warn('%s is decoded on the host (%s); further files of this kind are not reported' % (names[k], e.reason), JpegFallbackWarning)
+                    self._warned = True
+                fallback.append(k)
+                this = _host_size(d)
+            size = size or this
+            if this != size:
+                raise ValueError('%s is %dx%d, the first frame %dx%d (all frames must have one size)' % ((names[k],) + this + size))
+        t1 = time.perf_counter()
+        if not datas:
+            return torch.empty((0, 0, 0, 3), dtype=torch.uint8, device=self.device)
+        out = torch.empty((len(datas), size[1], size[0], 3), dtype=torch.uint8, device=self.device)
+        pending, t_pack = [], 0.
+        for members in groups.values():
+            idx = [k for k, _ in members]
+            tp = time.perf_counter()
+            packed = pack([datas[k] for k in idx], [i for _, i in members], self._staging)
+            t_pack += time.perf_counter() - tp
+            staged = self._pinned.to(self.device, non_blocking=True)             # the one copy of this group
+            whole = idx == list(range(len(datas)))
+            got, status = decode_packed(packed, staged, out if whole else None)
+            if not whole:
+                out[torch.as_tensor(idx, device=self.device)] = got
+            pending.append((idx, status, self._pinned))                           # (the staging buffer lives until the copy has run)
+        for k in fallback:
+            out[k] = torch.as_tensor(_host_decode(datas[k])).to(self.device)
+        for idx, status, _ in pending:
+            bad = status.cpu().numpy()
+            for j in np.flatnonzero(bad):
+                raise IOError('%s: the JPEG stream is damaged (%s)' % (names[idx[j]], status_text(int(bad[j]))))
+        if self.timing is not None:
+            self.timing.update(parse=t1 - t0, pack=t_pack)
+        return out
+
+
+def _host_size(data):
+    import io
+    from PIL import Image
+    with Image.open(io.BytesIO(data)) as im:
+        return im.size
+
+
+def _host_decode(data):
+    import io
+    from .feeder import imread
+    return np.array(imread(io.BytesIO(data)))                  # (a writable copy: PIL's buffer is read-only)
+
+
+def load_frames_device(names, device=None, decoder=None):
+    """[len(names), H, W, 3] uint8 on the device: what torch.as_tensor(overlay.load_frames(names)).to(device) holds."""
+    return (decoder or JpegDecoder(device)).decode(list(names))

@@ -200,6 +200,7 @@ def parse_arguments(argv=None):
     parser.add_argument('--overwrite', action='store_true', help='Whether to replace frames already in the output folder.')
     parser.add_argument('--gpu', type=int, default=0, help='GPU id')
     parser.add_argument('--block', type=int, default=50, help='frames per device call')
+    parser.add_argument('--decode', default='host', choices=['host', 'device'], help="where the input frames are decoded: host (PIL, one thread) or device (jpeg.py: the files' bytes go to the device; same pixels)")
     return parser.parse_args(argv)
 
 
@@ -226,8 +227,13 @@ def main(argv=None):
     ov = Overlay(data.shape[1], audio_rate=rate, angular_res=args.angular_res)
     ov.process(torch.as_tensor(data.astype(np.float32)).to(ov.device), None)
     written = 0
+    if args.decode == 'device':
+        from .jpeg import JpegDecoder
+        decoder = JpegDecoder(ov.device)
     for i in range(0, len(names), args.block):
-        out = ov.process(None, torch.as_tensor(load_frames(names[i:i + args.block])).to(ov.device)).cpu().numpy()
+        block = names[i:i + args.block]
+        frames = decoder.decode(block) if args.decode == 'device' else torch.as_tensor(load_frames(block)).to(ov.device)
+        out = ov.process(None, frames).cpu().numpy()
         save_frames(args.output_dir, out, written)
         written += out.shape[0]
     if args.save_maps:

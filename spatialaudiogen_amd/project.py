@@ -264,6 +264,7 @@ def parse_arguments(argv=None):
     parser.add_argument('--overwrite', action='store_true', help='Whether to replace frames already in the output folder.')
     parser.add_argument('--gpu', type=int, default=0, help='GPU id')
     parser.add_argument('--block', type=int, default=16, help='frames per device call')
+    parser.add_argument('--decode', default='host', choices=['host', 'device'], help="where the input frames are decoded: host (PIL, one thread) or device (jpeg.py: the files' bytes go to the device; same pixels)")
     return parser.parse_args(argv)
 
 
@@ -306,8 +307,12 @@ def main(argv=None):
     turned = any(np.any(np.asarray(getattr(args, k)) != 0.) for k in ('yaw', 'pitch', 'roll'))
     rot = view_trajectory(frame_angles(args.yaw, n), frame_angles(args.pitch, n), frame_angles(args.roll, n)) if turned else None
     pr = Projector(src, dst, args.size, args.supersample)
+    if args.decode == 'device':
+        from .jpeg import JpegDecoder
+        decoder = JpegDecoder(pr.device)
     for i in range(0, n, args.block):
-        frames = torch.as_tensor(load_frames(names[i:i + args.block])).to(pr.device)
+        block = names[i:i + args.block]
+        frames = decoder.decode(block) if args.decode == 'device' else torch.as_tensor(load_frames(block)).to(pr.device)
         out = pr.process(frames, None if rot is None else rot[i:i + args.block]).cpu().numpy()
         save_frames(args.output_dir, out, i, args.format)
     S = pr.supersample or auto_supersample(src, (h, w), dst, pr.size)
