@@ -254,8 +254,7 @@ static int conv2d_op(ConvOp& o, const float* x, int batch, int h, int w, int cin
         o.pack_taps = kh * kw; o.pack_cin = cin; o.pack_cpad = cin;
     }
     d.w_split = 1;                                      // (the op runs pack_split_launch behind pack_conv_launch)
-    static const bool no_p3 = getenv("SAGEN_NO_P3") != nullptr || getenv("SAGEN_FP32_ONLY") != nullptr;
-    if (!no_p3 && room_for_planes && sh == 1 && sw == 1 && padding == 1 && cin % 16 == 0 && igemm_p3_eligible(d) &&
+    if (!process_switches().no_p3 && !process_switches().fp32_only && room_for_planes && sh == 1 && sw == 1 && padding == 1 && cin % 16 == 0 && igemm_p3_eligible(d) &&
         p3_bytes(batch, h, w, cin) < (1UL << 31)) {
         // dense 3x3 stride-1 SAME: one elementwise pass applies the input BN+ReLU (if any) and writes the three bf16
         // planes; the contraction then runs LDS-DMA -> MFMA only (conv3p.hip)

@@ -15,8 +15,7 @@ namespace sagen {
 static int aligned_grid(long n4, int C4) {
     // SAGEN_BWD_AMORT items per thread at least: fewer, longer workgroups leave CUs to the weight gradients on the second stream
     // (training step on one box, tools/ab_bwd_amort.sh: 1 / 2 / 4 / 8 / 16 / 32 items = 6.09-6.11 / 6.06-6.08 / 6.01 / 5.98-6.01 / 6.07 / 6.28 ms)
-    static const int amort = getenv("SAGEN_BWD_AMORT") ? std::max(1, atoi(getenv("SAGEN_BWD_AMORT"))) : 4;
-    long g = std::min<long>(cdiv(n4, 256L * amort), 256L * 16);
+    long g = std::min<long>(cdiv(n4, 256L * process_switches().bwd_amort), 256L * 16);
     if ((g * 256) % C4) {
         long a = 256, b = C4;
         while (b) { const long t = a % b; a = b; b = t; }
@@ -33,11 +32,8 @@ __device__ __forceinline__ float4 add4(float4 a, float4 b) { return make_float4(
 // and no same-address atomic chains: 4096 workgroups x 128 fp64 atomics on 128 addresses took 300 us per batch-norm layer).
 // Requires 256 % C4 == 0 (thread t owns channels 4*(t % C4)).
 constexpr int RED_MAX_BLOCKS = 1024;              // capacity of the partial rows (scratch, t:mxpart); the launches use red_blocks() of them
-// (SAGEN_RED_BLOCKS: A/B of the reductions' parallelism - 512 workgroups = two per CU)
-static int red_blocks() {
-    static const int n = getenv("SAGEN_RED_BLOCKS") ? std::min(RED_MAX_BLOCKS, std::max(64, atoi(getenv("SAGEN_RED_BLOCKS")))) : 512;
-    return n;
-}
+static_assert(RED_MAX_BLOCKS == 1024, "the SAGEN_RED_BLOCKS row of switches.h clamps to this capacity");
+static int red_blocks() { return (int)process_switches().red_blocks; }
 template <int NV>
 __device__ __forceinline__ void channel_partials(const float4 (&v)[NV], int C4, float* part) {
     __shared__ float4 red[NV][256];
@@ -171,8 +167,7 @@ int relu_bwd_launch(const float* ga, int lda, const float* gb, int ldb, const fl
     if (((uintptr_t)ga | (uintptr_t)gb | (uintptr_t)act | (uintptr_t)dy) % 16) return fail(SAGEN_ERR_UNSUPPORTED, "relu_bwd: operands must be 16-byte aligned");
     const int C4 = Cp / 4;
     const long n4 = R * C4;
-    static const bool no_small = getenv("SAGEN_RELU_BWD_TWO_LAUNCHES") != nullptr;
-    if (colsum && !no_small && n4 <= 32768 && R <= (1 << 20)) {
+    if (colsum && !process_switches().relu_bwd_two_launches && n4 <= 32768 && R <= (1 << 20)) {
         hipLaunchKernelGGL(relu_bwd_small_kernel, dim3(cdiv(C4, 32)), dim3(256), 0, s, ga, lda, gb, ldb, act, ldact, dy, lddy, (int)R, C4, colsum,
                            colsum_f32, C, band_rows, batch_rows, row0);
         SAGEN_LAUNCH_CHECK();
@@ -658,8 +653,7 @@ int maxpool_bn_bwd_launch(const float* y0, const BnRef& bn, const float* pooled,
     const int pth = std::max((Ho - 1) * 2 + 3 - H, 0), ptw = std::max((Wo - 1) * 2 + 3 - W, 0);
     const long total = (long)B * H * W * (C / 4);
     // (gather-heavy: more, shorter workgroups than the streaming reductions; rows of 2C floats)
-    static const int gmax = getenv("SAGEN_POOLBWD_GRID") ? atoi(getenv("SAGEN_POOLBWD_GRID")) : 2048;
-    int grid = (int)std::max<long>(1, std::min<long>(cdiv(total, 256 * 4), gmax));
+    int grid = (int)std::max<long>(1, std::min<long>(cdiv(total, 256 * 4), (int)process_switches().poolbwd_grid));
     if (pooled_raw) {                                  // the sums over the pooled grid (the forward kept each window's raw extremum)
         const long ptotal = (long)B * Ho * Wo * (C / 4);
         grid = reduce_grid(ptotal, C / 4);

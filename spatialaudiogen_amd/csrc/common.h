@@ -6,6 +6,7 @@
 #include <cstdio>
 #include <cstring>
 #include "../../include/sagen.h"
+#include "switches.h"
 
 namespace sagen {
 

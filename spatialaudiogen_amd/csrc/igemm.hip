@@ -374,9 +374,9 @@ bool igemm_tile_ok(const IgemmDesc& d, IgemmTile t) {
 }
 
 IgemmTile igemm_pick_tile(const IgemmDesc& d) {
-    static const char* force = getenv("SAGEN_FORCE_TILE");               // tuning knob: IgemmTile index
-    if (force && d.M > 128 && d.N >= 64 && igemm_tile_ok(d, (IgemmTile)atoi(force))) return (IgemmTile)atoi(force);
-    static const bool fp32_only = getenv("SAGEN_FP32_ONLY") != nullptr;
+    const long force = process_switches().force_tile;                    // tuning knob: IgemmTile index
+    if (force != SW_UNSET && d.M > 128 && d.N >= 64 && igemm_tile_ok(d, (IgemmTile)force)) return (IgemmTile)force;
+    const bool fp32_only = process_switches().fp32_only;
     if (d.xp3 == nullptr && d.x == nullptr && conv3s_ok(d)) return TILE_P3S_128x128;         // only the space-to-depth planes were provided
     if (d.mm_out != nullptr) return (d.xp3 != nullptr && d.xp3_fmt == 1 && d.wh2 != nullptr && conv3g_ok(d)) ? TILE_P3GH_MM_64x128_K2 : TILE_B3_64x128;
     auto blocks = [&](IgemmTile t) { return (long)cdiv(d.M, igemm_tile_bm(t)) * cdiv(d.N, igemm_tile_bn(t)) * d.splitk; };

@@ -106,9 +106,13 @@ struct sagen_ctx {
     std::map<std::string, Choice> plan;
     std::map<std::string, bool> materialize;     // conv_2 layers: apply the producer's BN+ReLU in a separate pass?
     bool tuning = false;
-    bool fp32_only = false;                      // SAGEN_FP32_ONLY=1: never use the bf16x3 tiles
-    bool use_p3 = true;                          // 3x3 stride-1 trunk convs read pre-split bf16 planes (conv3p.hip); SAGEN_NO_P3=1 disables
-    int p3_from_stage = 3;                       // ... from this ResNet stage on (2..5; SAGEN_P3_FROM_STAGE): see resnet()
+    Switches sw;                                 // this context's copy of the environment switches (switches.h), read by sagen_create_impl
+    bool use_p3 = true;                          // (this and the next five: computed from `sw` by derive_settings, model.hip) 3x3 stride-1 trunk convs read pre-split planes (conv3p.hip / conv3h.hip)
+    int p3_from_stage = 3;                       // ... from this ResNet stage on (2..5): see resnet()
+    bool stem_fused = true;                      // inference: 7x7/2 stem + max-pool as one kernel (stempool.hip)
+    bool use_p3g = true;                         // the block merges of stages 3, 4 also write planes for the NEXT stage's stride-2 conv_1 + shortcut (conv3g.hip)
+    int dec_planes_min_batch = 16;               // the scatter-form decoder contracts fp16x2 planes from this batch size on (sagen_set_option("decoder_planes", 1 / 0): always / never)
+    bool use_fcm = false;                        // inference: the skinny FC layers (bottleneck / localisation / fc-feats) run fcm_kernel (fcm.hip) chained through partials
     hipEvent_t tune_e0 = nullptr, tune_e1 = nullptr;
     // second, context-owned stream: the audio chain (and the flow trunk) run under the video trunk
     hipStream_t aux = nullptr;
@@ -137,12 +141,11 @@ struct sagen_ctx {
     // [shared: packed filters, job tables][per-batch region of group 0][... of group 1] ...: `grp_off` floats of shared buffers, then
     // G copies of `grp_floats` floats; bufs / p() describe group 0, group g's copy of a per-batch buffer lies g * grp_floats further on
     int G = 1;
-    int tune_groups = 0;                   // groups a tuning pass launches per candidate (SAGEN_TUNE_GROUPS; 0 = all, the default: same box, 15 per call: tuned on all 3 153 - 3 160 ambisonic-s/s in a 14 s process, on 4 groups 3 122 - 3 136 in 10 s, on 2 3 063 - 3 073)
     int inter_group = 0;                   // sagen_set_option("intermediate_group"): the group sagen_get_intermediate reads
     size_t grp_off = 0, grp_floats = 0;
     // did an option move the path off the kernels that take a group dimension?  (the forward adds what it alone knows: the stems, the decoder)
     static bool off_grouped(const sagen_ctx* c) {
-        return c->use_fcm || c->sk_fused || c->fp32_only || !c->use_h2 || !c->use_p3 || !c->use_p3g || c->p3_from_stage > 2 || c->no_lean_trunk;
+        return c->use_fcm || c->sw.sk_fused || c->sw.fp32_only || !c->sw.use_h2 || !c->use_p3 || !c->use_p3g || c->p3_from_stage > 2 || c->sw.no_lean_trunk;
     }
     GroupInfo group_info() const {
         GroupInfo gi;
@@ -166,36 +169,18 @@ struct sagen_ctx {
     int pack_blocks = 0, pack_blocks_bwd = 0;
     bool train_mode = false;
     bool train_ready = false;
-    bool stem_fused = true;                // inference: 7x7/2 stem + max-pool as one kernel (stempool.hip); SAGEN_NO_STEMPOOL=1 disables
     bool materialize_mask = false;         // sagen_set_option("materialize_mask"): keep deconv1 -> mask as two kernels so that the logits exist
     bool mask_fused_last = false;          // the last forward ran the fused decoder tail: "separation/deconv1" holds no logits
     bool video_u8 = false;                 // this call's video frames are uint8 (sagen_forward_u8): normalisation fused into the pad pass
-    bool train_h2 = true;                  // the training step's forward also runs the trunk's stride-1 3x3 convs on the fp16x2 planes (SAGEN_TRAIN_NO_H2=1: bf16x3)
-    bool use_h2 = true;                    // inference: the planes of the trunk are two fp16 planes (conv3h.hip: three products per multiply) instead of three bf16 planes; SAGEN_NO_H2=1 / sagen_set_option("fp16x2", 0)
-    bool train_h2d = true;                 // ... and its backward runs the stride-1 3x3 data gradients on fp16x2 planes of dy, written by the batch-norm backward (SAGEN_TRAIN_NO_H2D=1: bf16x3 on fp32 dy)
-    bool no_aud_planes = false;            // SAGEN_NO_AUDIO_PLANES=1: conv2 .. conv5 of the audio encoder stay on the register-staged kernels (fp32 operand, in-loop split) instead of conv3g_kernel on fp16x2 planes of cat_l's encoder half (round 6)
-    bool no_dh_split = false;              // SAGEN_NO_DH_SPLIT=1: the tuner does not consider conv3h_kernel's dh-split (one filter row per workgroup, round 6)
-    bool sk_fused = false;                 // SAGEN_SK_FUSED=1: split-K partials are combined inside the contraction (last-arriver, igemm_epilogue) instead of by a reducer launch - bit-identical, measured no faster
-    bool train_h2w = true;                 // ... and the weight gradients of those layers run on the planes too (wgrad3h.hip): the forward retains its activation planes (SAGEN_TRAIN_NO_H2W=1: bf16x3 on the fp32 tensors)
     std::map<std::string, int> h2d_slot;   // per data-gradient filter: index of its 2^-kw in the "t:h2d" table
     std::vector<H2Job> h2d_jobs;
     int h2d_blocks = 0;
     std::map<std::string, int> h2_slot;    // per layer: index of its 2^-kw in the "h2s" table
     std::vector<H2Job> h2_jobs;            // the batched fp16x2 filter pack (host copy of the job table)
     int h2_blocks = 0;
-    bool use_p3g = true;                   // the block merges of stages 3, 4 also write planes for the NEXT stage's stride-2 conv_1 + shortcut (conv3g.hip); opt-in: SAGEN_P3G=1 / sagen_set_option("plane_gather", 1) - measured no faster than igemm3_kernel
     bool rawpool_last = false;             // the last training forward kept the pooled raw stem output in "rx0" (stem8pool_kernel<raw+pool>)
-    bool train_rawpool = true;             // the training forward's stem writes the raw output AND its pooled extremum (SAGEN_TRAIN_NO_RAWPOOL=1: a pool pass of its own)
-    bool train_bands = true;               // the training step's decoder on the live rows only, forward and backward (SAGEN_TRAIN_NO_BANDS=1: full tensors)
     int dec_lo[7] = {0, 0, 0, 0, 0, 0, 0}, dec_hi[7] = {0, 0, 0, 0, 0, 0, 0};      // rows of cat_l the last forward's decoder read (the backward of the same step follows them)
-    bool use_s2d = true;                   // lean trunk: a stage's last merge writes its planes in space-to-depth form where the plan runs the next stage's stride-2 conv_1 on the space-to-depth conv3h_kernel (conv3s.hip); SAGEN_NO_S2D=1 / sagen_set_option("plane_s2d", 0): the gathered kernel everywhere
-    bool no_scatter = false, no_d1_planes = false, no_lean_trunk = false;      // SAGEN_NO_DECONV_SCATTER / SAGEN_NO_DECONV1_PLANES / SAGEN_NO_LEAN_TRUNK, read when the context is created
-    int dec_planes_min_batch = 16;         // the scatter-form decoder contracts fp16x2 planes from this batch size on (sagen_set_option("decoder_planes", 1 / 0): always / never)
-    bool use_fcm = false;                  // inference: the skinny FC layers (bottleneck / localisation / fc-feats) run fcm_kernel (fcm.hip) chained through partials; SAGEN_NO_FCM=1: the round-4 contraction + reducer launches
     std::map<std::string, int> fcm_slices; // per FC layer: K slices of its fcm launch
-    bool stem8h = true;                    // uint8 frames: one fp16 plane x two fp16 filter planes (stem8.hip, MODE 2); sagen_set_option("u8_stem_h2", 0) / SAGEN_NO_STEM8_H2=1: the bf16 plane x three bf16 filter planes of round 4
-    bool stem16 = true;                    // float frames run the fp16x2 variant of that kernel (stem8.hip, F16: two planes of the frame scaled by its exact maximum); sagen_set_option("f16_fast_stem", 0) / SAGEN_NO_STEM16=1: igemm3s2_kernel + the pool pass
-    bool stem8 = true;                     // uint8 frames run the one-operand-plane stem (stem8.hip); sagen_set_option("u8_fast_stem", 0) / SAGEN_NO_STEM8=1: the general kernels
     size_t tws_floats = 0;
     float* tws = nullptr;
     std::map<std::string, Buf> tbufs;
@@ -381,7 +366,7 @@ struct Fwd {
             }
             // the partials are combined by the contraction itself (last-arriver, igemm_epilogue) unless statistics ride on the reducer
             const long tiles = (long)cdiv(d.M, igemm_tile_bm(tile)) * cdiv(d.N, igemm_tile_bn(tile));
-            if (c->sk_fused && sk > 1 && !d.stats && !d.amax_out && d.N % 4 == 0 && d.ldy % 4 == 0 && ((uintptr_t)d.y % 16) == 0 && (!d.bias || ((uintptr_t)d.bias % 16) == 0) &&
+            if (c->sw.sk_fused && sk > 1 && !d.stats && !d.amax_out && d.N % 4 == 0 && d.ldy % 4 == 0 && ((uintptr_t)d.y % 16) == 0 && (!d.bias || ((uintptr_t)d.bias % 16) == 0) &&
                 tiles <= SK_TICKETS && c->bufs.count(wsname + ":tk")) {
                 e.sk_ticket = reinterpret_cast<int*>(c->ws + c->bufs.at(wsname + ":tk").off);
                 e.sk_rep = rep;
@@ -430,10 +415,10 @@ struct Fwd {
     Choice tune(const IgemmDesc& d_in, int rep, bool allow_split) {
         // grouped contexts: with SAGEN_TUNE_GROUPS=n the candidates are timed on the first n groups only (this object's group and the
         // descriptor's, lowered for the duration) - a shorter tuning pass; the default times the launches the forward will run (the
-        // choice between tiles does depend on the group count: see sagen_ctx::tune_groups)
+        // choice between tiles does depend on the group count: see Switches::tune_groups)
         IgemmDesc d = d_in;
         const int G = grp.G;
-        if (c->tune_groups > 0 && G > c->tune_groups) d.grp.G = grp.G = c->tune_groups;
+        if (c->sw.tune_groups > 0 && G > c->sw.tune_groups) d.grp.G = grp.G = c->sw.tune_groups;
         const Choice best = time_candidates(d, rep, allow_split);
         grp.G = G;
         return best;
@@ -451,21 +436,19 @@ struct Fwd {
             // stage 4: 80 vs 83) but its 121 KiB of LDS make it the only workgroup of a CU, and with a second batch in flight the
             // forward gets slower (1 560 vs 1 610-1 637 ambisonic-s/s) - a candidate only for the training step, which has one batch in
             // flight (7.27 -> 7.23 ms per step on one box), or when asked for (SAGEN_P3PP=1)
-            static const bool p3pp = getenv("SAGEN_P3PP") != nullptr;
-            if (!p3pp && !c->train_mode && (igemm_tile_traits(tile) & TF_TWO_TEAM)) continue;
+            if (!c->sw.p3pp && !c->train_mode && (igemm_tile_traits(tile) & TF_TWO_TEAM)) continue;
             // conv3hr_kernel (three-deep activation ring) measured equal to conv3h_kernel on every layer: left out of
             // the tuner so that equal candidates do not split a layer family over two kernel names from run to run (SAGEN_P3HR=1 adds it)
-            static const bool p3hr = getenv("SAGEN_P3HR") != nullptr;
             // (round 6: with ten batches per launch the wait for the activation images is no longer hidden - tools/trace_conv3h.py: 500 - 1 400 of a
             //  2 000 - 3 000-cycle group - and the deeper ring measures 0 - 2 % ahead on the headline, same box: a candidate of grouped contexts)
-            if (!p3hr && c->G == 1 && (igemm_tile_traits(tile) & TF_RING3)) continue;
+            if (!c->sw.p3hr && c->G == 1 && (igemm_tile_traits(tile) & TF_RING3)) continue;
             const int nk = d.Kpad / igemm_tile_bk(tile);
             if (bn > 32 && bn >= 2 * d.N) continue;                     // mostly-empty N tile
             if (bm > 32 && bm >= 4 * d.M) continue;
             for (int sk : SKS) {
                 if (sk > 1 && (!allow_split || !dense)) break;
                 if (sk > 1 && igemm_tile_p3(tile)) {                     // plane-fed kernels: only conv3h_kernel's dh-split (3)
-                    if (!igemm_tile_dh_split(tile) || sk > 3 || c->no_dh_split) break;
+                    if (!igemm_tile_dh_split(tile) || sk > 3 || c->sw.no_dh_split) break;
                     if (sk != 3) continue;
                 }
                 if (sk > 1 && ((nk / sk < 4 && !igemm_tile_p3(tile)) || (size_t)sk * d.M * d.N > ws_capacity())) break;
@@ -500,7 +483,7 @@ struct Fwd {
     int contract(const IgemmDesc& d_in, int rep = 1, bool allow_split = true) {
         if (rc) return 0;
         IgemmDesc d = d_in;
-        d.w_split = c->fp32_only ? 0 : 1;          // every bound filter carries its bf16x3 planes
+        d.w_split = c->sw.fp32_only ? 0 : 1;          // every bound filter carries its bf16x3 planes
         d.grp = grp;                               // ... and every contraction of this object its group
         if (rep > 1 && !dense_out(d)) { rc = fail(SAGEN_ERR_UNSUPPORTED, "replicated store needs a dense plain epilogue"); return 0; }
         Choice ch;
@@ -638,7 +621,7 @@ struct Fwd {
 
     // fp16x2 planes (conv3h.hip) for this forward?  (the training step's forward too, unless SAGEN_TRAIN_NO_H2=1: its backward reads the
     // retained fp32 activations, not the planes)
-    bool h2() const { return c->use_h2 && c->use_p3 && !c->fp32_only && (!c->train_mode || c->train_h2); }
+    bool h2() const { return c->sw.use_h2 && c->use_p3 && !c->sw.fp32_only && (!c->train_mode || c->sw.train_h2); }
     // a layer's fp16x2 filter planes ("pkh:"; scatter: "pkhs:", the scatter form of a transposed conv) and where the pack wrote their 2^-kw
     struct H2Filter { const void* w2; const float* w_inv; };
     bool has_h2_filter(const std::string& name) const { return c->h2_slot.count(name) != 0; }
@@ -723,11 +706,11 @@ struct Fwd {
         // uint8 frames: the centred bf16 plane u - 128 IS the exact operand (x = (u' + 0.5) / 255): one plane, three products (stem8.hip)
         // (a grouped context has no other stem: its autotune pass runs the fused kernels too - they take no tile from the plan)
         const bool tune_general = c->tuning && c->G == 1;
-        const bool fast8 = c->video_u8 && scope == "video_encoder" && c->stem8 && !tune_general && !c->fp32_only && !c->train_mode;
+        const bool fast8 = c->video_u8 && scope == "video_encoder" && c->sw.stem8 && !tune_general && !c->sw.fp32_only && !c->train_mode;
         // ... with the filter as two fp16 planes where they exist: two products per multiply instead of three (stem8.hip, MODE 2)
-        const bool fast8h = fast8 && c->stem8h && h2() && has_h2_filter(scope + "/conv1/conv");
+        const bool fast8h = fast8 && c->sw.stem8h && h2() && has_h2_filter(scope + "/conv1/conv");
         // float frames (the flow encoder; video handed over as float32): the same kernel on two fp16 planes of the frame (stem8.hip, F16)
-        const bool fast16 = !fast8 && !(c->video_u8 && scope == "video_encoder") && c->stem16 && !tune_general && !c->fp32_only && !c->train_mode && h2() &&
+        const bool fast16 = !fast8 && !(c->video_u8 && scope == "video_encoder") && c->sw.stem16 && !tune_general && !c->sw.fp32_only && !c->train_mode && h2() &&
                             c->use_p3 && c->p3_from_stage <= 2 && c->bufs.count("s16:part" + sfx) != 0 && has_h2_filter(scope + "/conv1/conv");
         // the batch-norm accumulators start at zero: cleared by the trunk's first kernel where that is stem8_prep / stem16_amax, else by a fill
         if (!fast8 && !fast16 && !rc && hipMemsetAsync(c->p("bnacc" + sfx), 0, c->bufs.at("bnacc" + sfx).n * sizeof(float), s) != hipSuccess)
@@ -738,7 +721,7 @@ struct Fwd {
         // fp32 except the trunk's end: the merges read their identity residual from the block-input planes (in place: buffer "p3"
         // holds block inputs / outputs, "p3b" the conv_2 inputs) and write planes only - 4 bytes per element less per merge, no fp32
         // copy of the pooled tensor.  The planes carry the value conv_1 saw (22 significant bits + the residual's sign).
-        const bool no_lean = c->no_lean_trunk;
+        const bool no_lean = c->sw.no_lean_trunk;
         const bool lean = !no_lean && h2() && pool_planes && c->use_p3g && c->bufs.count("p3b" + sfx) != 0 && !c->train_mode;
         float* const s16_a_inv = c->p("h2s") + H2S_S16_A_INV + (sfx.empty() ? 0 : 1);        // 2^-ka of the frame planes
         if (fast16)
@@ -759,7 +742,7 @@ struct Fwd {
         }
         {
             const std::string name = scope + "/conv1/conv";
-            const bool fused = c->stem_fused && !c->tuning && !c->fp32_only && !(c->use_p3 && c->p3_from_stage <= 2);
+            const bool fused = c->stem_fused && !c->tuning && !c->sw.fp32_only && !(c->use_p3 && c->p3_from_stage <= 2);
             if (fast8 || fast16) {
                 H = 112; W = 224;
                 layer = name + "+pool";
@@ -900,7 +883,7 @@ struct Fwd {
                     // from the intact residual planes - so that the candidates of both families are timed on real operands
                     bool s2d_out = false, rows_out = true;
                     const std::string next_c1 = scope + "/conv" + std::to_string(st + 3) + "_1/conv_1";
-                    if (lean && to_next_stage && c->use_s2d && !(Ho & 1) && !(Wo & 1) && c->h2_slot.count(next_c1) != 0 &&
+                    if (lean && to_next_stage && c->sw.use_s2d && !(Ho & 1) && !(Wo & 1) && c->h2_slot.count(next_c1) != 0 &&
                         c->h2_slot.count(scope + "/conv" + std::to_string(st + 3) + "_1/shortcut") != 0) {
                         auto it = c->plan.find(next_c1);
                         s2d_out = c->tuning || (it != c->plan.end() && igemm_tile_s2d((IgemmTile)it->second.tile));
@@ -973,7 +956,7 @@ struct Fwd {
     // ReLU masks), the pool output "t:x0"; the raw stem output "y0" and the BN accumulators are never reused anyway.
     // With train_h2w the planes the forward writes for conv3h_kernel are RETAINED per layer ("t:pl:a1:k": input of block k's conv_2,
     // "t:pl:x:k": input of block k's stride-1 conv_1; scales in "t:h2a": slot k / 8 + k): the weight gradients contract them (wgrad3h.hip).
-    bool h2w() const { return c->train_mode && c->train_h2w && c->train_h2d && h2() && c->p3_from_stage <= 2 && wgrad_planes_enabled() && c->tbufs.count("t:h2a" + sfx) != 0; }
+    bool h2w() const { return c->train_mode && c->sw.train_h2w && c->sw.train_h2d && h2() && c->p3_from_stage <= 2 && wgrad_planes_enabled() && c->tbufs.count("t:h2a" + sfx) != 0; }
     void* pl_buf(const char* what, int k) { return c->p(std::string("t:pl:") + what + ":" + std::to_string(k) + sfx); }
     float* pl_a_inv(int slot) { return c->p("t:h2a" + sfx) + slot; }
     const float* resnet_train(const float* img, const std::string& scope) {
@@ -990,7 +973,7 @@ struct Fwd {
         int H = 0, W = 0;
         // uint8 frames (sagen_train_step_u8): the stem's forward on the exact one-plane operand (stem8.hip, RAW: y0 is kept for the
         // backward); the float xpad above is still what the stem's weight gradient contracts
-        const bool fast8 = c->video_u8 && scope == "video_encoder" && c->stem8 && !c->tuning && !c->fp32_only && c->tbufs.count("t:s8plane" + sfx) != 0;
+        const bool fast8 = c->video_u8 && scope == "video_encoder" && c->sw.stem8 && !c->tuning && !c->sw.fp32_only && c->tbufs.count("t:s8plane" + sfx) != 0;
         if (fast8) {
             layer = scope + "/plane";
             timed("stem8_prep_kernel", 0.0, [&] { return stem8_prep_launch(reinterpret_cast<const unsigned char*>(img), c->p("t:s8plane" + sfx), B, grp, s); });
@@ -1004,7 +987,7 @@ struct Fwd {
             // ... and, where the pooled tensor goes on as planes, the pool of the raw output in the same kernel (max, or min where gamma < 0:
             // relu(bn(.)) is monotone per channel, so BN + ReLU of the pooled raw tensor IS maxpool(relu(bn(y0))), bit for bit) - the pool
             // pass no longer reads the 205 MB raw tensor a second time
-            const bool rawpool = fast8 && keep && c->train_rawpool && c->bufs.count("rx0" + sfx) != 0;
+            const bool rawpool = fast8 && keep && c->sw.train_rawpool && c->bufs.count("rx0" + sfx) != 0;
             if (scope == "video_encoder") c->rawpool_last = rawpool;
             if (rawpool) {
                 H = 112; W = 224;
@@ -1085,7 +1068,7 @@ struct Fwd {
                 if (planes_ai) hs1.a_inv = const_cast<float*>(planes_ai);
                 // with retained planes nobody reads the fp32 a1: conv_2 and its weight gradient take the planes, conv_1's batch-norm
                 // backward re-derives the ReLU mask from y1 (unless a debugging switch asks for the fp32 tensor)
-                static const bool a1_wanted = getenv("SAGEN_BN_READ_ACT") != nullptr || getenv("SAGEN_TRAIN_KEEP_A1") != nullptr;
+                const bool a1_wanted = c->sw.bn_read_act || c->sw.train_keep_a1;
                 float* a1w = (keep && p3_here && !a1_wanted && !wgrad_reads_fp32_operands()) ? nullptr : a1;
                 if (p3_here) timed("p3_pack_kernel", 0.0, [&] { return p3_pack_launch(y1, nullptr, nullptr, bn1, nullptr, 1, a1w, planes, B, Ho, Wo, cout, grp, s, p3_fmt(), &hs1); });
                 else timed_no_group("bn_apply_relu_kernel", 0.0, [&] { return bn_apply_relu_launch(y1, nullptr, nullptr, bn1, nullptr, a1, (long)B * Ho * Wo, cout, s); });

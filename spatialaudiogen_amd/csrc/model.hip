@@ -7,6 +7,43 @@
 // create / destroy
 // ------------------------------------------------------------------------------------------------
 void sagen_destroy_impl(sagen_ctx* c);
+// the skinny FC layers fcm_kernel (fcm.hip) would run at inference
+struct FcmLayer { std::string name; int rows, K, N; };
+static std::vector<FcmLayer> fcm_layers(const sagen_ctx* c) {
+    const int B = c->B;
+    std::vector<FcmLayer> ls{{"bottleneck/audio-fc", 3 * B, c->enc_w[5] * c->enc_c[5], 1024}};
+    if (c->has_video) ls.push_back({"bottleneck/video-fc", B, 7 * 14 * 128, 512});
+    if (c->has_flow) ls.push_back({"bottleneck/flow-fc", B, 7 * 14 * 128, 512});
+    int fin = c->Cb;
+    for (int i = 0; i < c->cfg.n_loc_units; ++i) { ls.push_back({"localization/fc" + std::to_string(i + 1), 3 * B, fin, c->cfg.loc_units[i]}); fin = c->cfg.loc_units[i]; }
+    ls.push_back({"localization/fc" + std::to_string(c->cfg.n_loc_units + 1), 3 * B, fin, c->nout * c->nin * (c->nsep + 1)});
+    if (c->freq_mask) ls.push_back({"separation/fc-feats", 3 * B, c->Cb, 512});
+    return ls;
+}
+// the settings of a context that are computed from its switches (and its geometry), not read
+static void derive_settings(sagen_ctx* c) {
+    const Switches& sw = c->sw;
+    c->use_p3 = !sw.fp32_only && !sw.no_p3;
+    // with two fp16 planes a plane pass writes 4 bytes per element - what the fp32 pass it replaces writes - so the planes pay from
+    // stage 2 on (measured, same box: 2 034 against 1 943 ambisonic-s/s); with three bf16 planes (6 bytes) only from stage 3
+    c->p3_from_stage = sw.want_p3_from_stage != SW_UNSET ? (int)sw.want_p3_from_stage : ((sw.use_h2 && c->use_p3) ? 2 : 3);
+    // fused stem + pool (stempool.hip): +0.8 % for a host that runs one forward at a time; with several batches in flight
+    // (SAGEN_ONE_STREAM=1 hosts, bench.py) its one-workgroup-per-CU LDS footprint blocks co-residency and it is a wash (-0.3 %)
+    c->stem_fused = !sw.no_stempool && (!sw.one_stream || sw.stempool);
+    // conv3g_kernel for the stride-2 conv_1 + shortcut of the first block of stages 3-5 (the previous stage's last merge then writes its
+    // output as planes ONLY).  Measured per layer, batch 32 (profiles/r04_layers_p3g*.txt): on three bf16 planes no faster than
+    // igemm3_kernel (56 / 58 / 72 us against 57 / 57 / 66) - on two fp16 planes 43 / 41 / 48 us against 60 / 61 / 74, shortcuts
+    // 24 / 14 / 13 against 25 / 19 / 18: on with the fp16x2 planes, opt-in (SAGEN_P3G=1) without them
+    c->use_p3g = c->use_p3 && (sw.p3g || (sw.use_h2 && !sw.no_p3g));
+    if (sw.no_decoder_planes) c->dec_planes_min_batch = 1 << 30;
+    // OPT-IN (SAGEN_FCM=1): measured slower than the general kernels it replaces (audio-fc 33 vs 15 us, video-fc 22 vs 18, fc2 / fc3 17 vs
+    // 9 - 10; only fc1 + fc-feats in one launch wins, 19 vs 23): these layers are bound by the latency of a short dependent launch
+    // (~6 us, what a reducer takes), not by how their arithmetic is fed
+    bool fcm = sw.fcm && !sw.sk_fused && 3 * c->B <= FCM_MAX_M;
+    if (fcm)
+        for (const FcmLayer& l : fcm_layers(c)) fcm = fcm && fcm_pick_slices(l.K, (long)l.K * l.N) > 0;
+    c->use_fcm = fcm;
+}
 int sagen_groups_impl(const sagen_ctx* c) { return c->G; }
 int sagen_create_impl(sagen_ctx** out, const sagen_config* cfg, int groups) {
     if (!out || !cfg) return fail(SAGEN_ERR_NULL, "sagen_create: null argument");
@@ -39,38 +76,6 @@ int sagen_create_impl(sagen_ctx** out, const sagen_config* cfg, int groups) {
     sagen_ctx* c = new sagen_ctx();
     c->G = groups;
 
-    c->fp32_only = getenv("SAGEN_FP32_ONLY") != nullptr;
-    c->use_p3 = !c->fp32_only && getenv("SAGEN_NO_P3") == nullptr;
-    if (const char* e = getenv("SAGEN_P3_FROM_STAGE")) c->p3_from_stage = atoi(e);
-    // fused stem + pool (stempool.hip): +0.8 % for a host that runs one forward at a time; with several batches in flight
-    // (SAGEN_ONE_STREAM=1 hosts, bench.py) its one-workgroup-per-CU LDS footprint blocks co-residency and it is a wash (-0.3 %)
-    c->stem_fused = getenv("SAGEN_NO_STEMPOOL") == nullptr && (getenv("SAGEN_ONE_STREAM") == nullptr || getenv("SAGEN_STEMPOOL") != nullptr);
-    c->stem8 = getenv("SAGEN_NO_STEM8") == nullptr;
-    c->stem16 = getenv("SAGEN_NO_STEM16") == nullptr;
-    c->stem8h = getenv("SAGEN_NO_STEM8_H2") == nullptr;
-    c->use_h2 = getenv("SAGEN_NO_H2") == nullptr;
-    c->train_h2 = getenv("SAGEN_TRAIN_NO_H2") == nullptr;
-    c->train_h2d = getenv("SAGEN_TRAIN_NO_H2D") == nullptr;
-    c->train_h2w = getenv("SAGEN_TRAIN_NO_H2W") == nullptr;
-    c->sk_fused = getenv("SAGEN_SK_FUSED") != nullptr;
-    c->no_dh_split = getenv("SAGEN_NO_DH_SPLIT") != nullptr;
-    c->no_aud_planes = getenv("SAGEN_NO_AUDIO_PLANES") != nullptr;
-    if (const char* e = getenv("SAGEN_TUNE_GROUPS")) c->tune_groups = atoi(e);
-    c->no_scatter = getenv("SAGEN_NO_DECONV_SCATTER") != nullptr;
-    c->train_bands = getenv("SAGEN_TRAIN_NO_BANDS") == nullptr;
-    c->train_rawpool = getenv("SAGEN_TRAIN_NO_RAWPOOL") == nullptr;
-    c->no_d1_planes = getenv("SAGEN_NO_DECONV1_PLANES") != nullptr;
-    c->no_lean_trunk = getenv("SAGEN_NO_LEAN_TRUNK") != nullptr;
-    c->use_s2d = getenv("SAGEN_NO_S2D") == nullptr;
-    if (getenv("SAGEN_NO_DECODER_PLANES") != nullptr) c->dec_planes_min_batch = 1 << 30;
-    // with two fp16 planes a plane pass writes 4 bytes per element - what the fp32 pass it replaces writes - so the planes pay from
-    // stage 2 on (measured, same box: 2 034 against 1 943 ambisonic-s/s); with three bf16 planes (6 bytes) only from stage 3
-    if (getenv("SAGEN_P3_FROM_STAGE") == nullptr) c->p3_from_stage = (c->use_h2 && c->use_p3) ? 2 : 3;
-    // conv3g_kernel for the stride-2 conv_1 + shortcut of the first block of stages 3-5 (the previous stage's last merge then writes its
-    // output as planes ONLY).  Measured per layer, batch 32 (profiles/r04_layers_p3g*.txt): on three bf16 planes no faster than
-    // igemm3_kernel (56 / 58 / 72 us against 57 / 57 / 66) - on two fp16 planes 43 / 41 / 48 us against 60 / 61 / 74, shortcuts
-    // 24 / 14 / 13 against 25 / 19 / 18: on with the fp16x2 planes, opt-in (SAGEN_P3G=1) without them
-    c->use_p3g = c->use_p3 && (getenv("SAGEN_P3G") != nullptr || (c->use_h2 && getenv("SAGEN_NO_P3G") == nullptr));
     c->cfg = *cfg;
     c->B = cfg->batch;
     c->has_video = cfg->encoders & SAGEN_ENC_VIDEO;
@@ -89,6 +94,8 @@ int sagen_create_impl(sagen_ctx** out, const sagen_config* cfg, int groups) {
         c->enc_c[l + 1] = AENC_F[l];
     }
     c->Cb = 1024 + (c->has_video ? 512 : 0) + (c->has_flow ? 512 : 0);
+    c->sw = read_switches();
+    derive_settings(c);
 
     // ---- variable inventory ----
     {
@@ -180,30 +187,13 @@ int sagen_create_impl(sagen_ctx** out, const sagen_config* cfg, int groups) {
     c->alloc("bott", (size_t)B * 3 * c->Cb);
     for (int i = 0; i < cfg->n_loc_units; ++i) c->alloc("loc" + std::to_string(i + 1), (size_t)B * 3 * cfg->loc_units[i]);
     c->alloc("coeffs", (size_t)B * 3 * c->nout * c->nin * (c->nsep + 1));
-    {   // fcm_kernel (fcm.hip) for the skinny FC layers at inference: partial buffers [slices][rows][N] per layer
-        struct L { std::string name; int rows, K, N; };
-        std::vector<L> ls;
-        ls.push_back({"bottleneck/audio-fc", 3 * B, c->enc_w[5] * c->enc_c[5], 1024});
-        if (c->has_video) ls.push_back({"bottleneck/video-fc", B, 7 * 14 * 128, 512});
-        if (c->has_flow) ls.push_back({"bottleneck/flow-fc", B, 7 * 14 * 128, 512});
-        int fin = c->Cb;
-        for (int i = 0; i < cfg->n_loc_units; ++i) { ls.push_back({"localization/fc" + std::to_string(i + 1), 3 * B, fin, cfg->loc_units[i]}); fin = cfg->loc_units[i]; }
-        ls.push_back({"localization/fc" + std::to_string(cfg->n_loc_units + 1), 3 * B, fin, c->nout * c->nin * (c->nsep + 1)});
-        if (c->freq_mask) ls.push_back({"separation/fc-feats", 3 * B, c->Cb, 512});
-        // OPT-IN (SAGEN_FCM=1): measured slower than the general kernels it replaces (audio-fc 33 vs 15 us, video-fc 22 vs 18, fc2 / fc3 17 vs
-        // 9 - 10; only fc1 + fc-feats in one launch wins, 19 vs 23): these layers are bound by the latency of a short dependent launch
-        // (~6 us, what a reducer takes), not by how their arithmetic is fed
-        bool ok = getenv("SAGEN_FCM") != nullptr && !c->sk_fused && 3 * B <= FCM_MAX_M;
-        for (const L& l : ls) ok = ok && fcm_pick_slices(l.K, (long)l.K * l.N) > 0;
-        c->use_fcm = ok;
-        if (ok)
-            for (const L& l : ls) {
-                int ns = fcm_pick_slices(l.K, (long)l.K * l.N);
-                if (l.name == "separation/fc-feats") ns = c->fcm_slices.at("localization/fc1");      // (one launch with fc1: the same slicing)
-                c->fcm_slices[l.name] = ns;
-                c->alloc("fcm:" + l.name, (size_t)ns * l.rows * l.N);
-            }
-    }
+    if (c->use_fcm)         // fcm_kernel (fcm.hip) for the skinny FC layers at inference: partial buffers [slices][rows][N] per layer
+        for (const FcmLayer& l : fcm_layers(c)) {
+            int ns = fcm_pick_slices(l.K, (long)l.K * l.N);
+            if (l.name == "separation/fc-feats") ns = c->fcm_slices.at("localization/fc1");      // (one launch with fc1: the same slicing)
+            c->fcm_slices[l.name] = ns;
+            c->alloc("fcm:" + l.name, (size_t)ns * l.rows * l.N);
+        }
     c->alloc("splitk", std::max<size_t>((size_t)16 << 20, (size_t)B * 56 * 112 * 64 * 2));   // fp32 split-K partials (up to 2 splits of the largest conv), checked per use
     if (c->freq_mask) {
         // rows 10..16 of cat1 as fp16x2 planes (the operand of deconv1 on conv3g_kernel) + the words around them: H2_AMAX_FLOATS floats (H2_AMAX_SLOTS lines) each for the exact
@@ -259,10 +249,9 @@ int sagen_create_impl(sagen_ctx** out, const sagen_config* cfg, int groups) {
     c->expose("localization/coeffs", "coeffs", 0, {B, 3, c->nout * c->nin, c->nsep + 1}, c->nsep + 1);      // [B, 3, nout, nin, nsep+1] (model.py:257)
     if (c->freq_mask) c->expose("separation/deconv1", "dmask", 0, {B, 23, 1024, c->nsep * c->nin}, c->nsep * c->nin);
     // second stream + fork/join events (host-side objects; no device memory)
-    // SAGEN_AUX_PRIO=low|high: the second stream below / above the default priority (experiment: the dispatcher then prefers one branch)
     int prio_lo = 0, prio_hi = 0;
     (void)hipDeviceGetStreamPriorityRange(&prio_lo, &prio_hi);       // (least, greatest): numerically lower = higher priority
-    const char* aux_prio = getenv("SAGEN_AUX_PRIO");
+    const char* aux_prio = c->sw.aux_prio;
     const int prio = aux_prio && aux_prio[0] == 'l' ? prio_lo : (aux_prio && aux_prio[0] == 'h' ? prio_hi : 0);
     if ((aux_prio ? hipStreamCreateWithPriority(&c->aux, hipStreamNonBlocking, prio) : hipStreamCreateWithFlags(&c->aux, hipStreamNonBlocking)) != hipSuccess ||
         hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
@@ -381,7 +370,7 @@ int sagen_repack_part(sagen_ctx* c, hipStream_t s, int part) {
     if (part == 1) return ne > 0 ? pack_multi_launch(jobs, ne, be, s) : SAGEN_OK;
     if (part == 2) rc = n > ne ? pack_multi_launch(jobs + ne, n - ne, c->pack_blocks - be, s, be) : SAGEN_OK;
     else rc = pack_multi_launch(jobs, n, c->pack_blocks, s);
-    if (rc || c->fp32_only || !c->use_p3) return rc;
+    if (rc || c->sw.fp32_only || !c->use_p3) return rc;
     // the fp16x2 filter planes of the trunks' 3x3 convs and 1x1 projections, from the fp32 packs just written: two launches for all
     // of them (bind; every training step)
     if (c->h2_jobs.empty()) {
@@ -412,8 +401,7 @@ int sagen_repack_part(sagen_ctx* c, hipStream_t s, int part) {
 int sagen_repack_impl(sagen_ctx* c, hipStream_t s) { return sagen_repack_part(c, s, 0); }
 // does sagen_forward_impl fork onto the context's second stream?  (the training step's split repack relies on it)
 bool sagen_forward_forks(const sagen_ctx* c) {
-    static const bool one_stream = getenv("SAGEN_ONE_STREAM") != nullptr;
-    return c->aux && !c->tuning && !one_stream && (c->has_video || c->has_flow);
+    return c->aux && !c->tuning && !c->sw.one_stream && (c->has_video || c->has_flow);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -431,7 +419,7 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
     if (c->G > 1) {
         if (c->train_mode) return fail(SAGEN_ERR_UNSUPPORTED, "the training step has no grouped launch");
         if (!c->freq_mask || sagen_ctx::off_grouped(c) ||
-            (c->has_video && !c->video_u8 && !c->stem16) || (c->has_video && c->video_u8 && !c->stem8) || (c->has_flow && !c->stem16))
+            (c->has_video && !c->video_u8 && !c->sw.stem16) || (c->has_video && c->video_u8 && !c->sw.stem8) || (c->has_flow && !c->sw.stem16))
             return fail(SAGEN_ERR_UNSUPPORTED, "grouped forward: an option moved the path off the kernels that take a group dimension "
                         "(fp16x2 / planes_from_stage / plane_gather / u8_fast_stem / f16_fast_stem must keep their defaults)");
     }
@@ -460,10 +448,9 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
 
     // deconv1 on fp16x2 planes of cat1 (conv3g_kernel + fused decoder tail): the planes' scale is the EXACT maximum of cat1, published by
     // the epilogues of its two producers (conv1: encoder half, deconv2: decoder half) into words zeroed here
-    const bool no_d1p = c->no_d1_planes;
     // (the opt-in in-launch split-K combine, SAGEN_SK_FUSED=1, has no reducer to publish a maximum from: it keeps the round-4 decoder)
-    bool d1_planes = !no_d1p && !c->sk_fused && c->freq_mask && !c->train_mode && !c->materialize_mask && !c->fp32_only && c->nsep == 32 && c->nin == 1 && f.h2() &&
-                     c->bufs.count("cat1p") != 0 && c->h2_slot.count("separation/deconv1") != 0 && getenv("SAGEN_NO_MASKFUSE") == nullptr;
+    bool d1_planes = !c->sw.no_d1_planes && !c->sw.sk_fused && c->freq_mask && !c->train_mode && !c->materialize_mask && !c->sw.fp32_only && c->nsep == 32 && c->nin == 1 && f.h2() &&
+                     c->bufs.count("cat1p") != 0 && c->h2_slot.count("separation/deconv1") != 0 && !c->sw.no_maskfuse;
     if (d1_planes && !c->tuning) {             // a plan that names a register-staged tile for deconv1 keeps the round-4 path (no pack pass)
         auto it = c->plan.find("separation/deconv1");
         if (it != c->plan.end() && !igemm_tile_p3((IgemmTile)it->second.tile)) d1_planes = false;
@@ -473,9 +460,8 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
     // (from 16 windows on: at deploy.py's batch of 10 the four pack launches cost what the plane-fed GEMMs save - 6 450 against 6 630 ambisonic-s/s)
     // (the training step's forward too, on its live bands - its backward reads the fp32 concat buffers the gather passes write either way;
     //  SAGEN_TRAIN_NO_DEC_PLANES=1: the register-staged kernels on fp32 operands, as up to round 5)
-    static const bool train_no_decp = getenv("SAGEN_TRAIN_NO_DEC_PLANES") != nullptr;
-    const bool dec_planes = !no_decp && c->B >= c->dec_planes_min_batch && !c->sk_fused && c->freq_mask && !(c->train_mode && (train_no_decp || !c->train_bands)) &&
-                            !c->fp32_only && f.h2() && c->bufs.count("catp") != 0 && !c->no_scatter;
+    const bool dec_planes = !no_decp && c->B >= c->dec_planes_min_batch && !c->sw.sk_fused && c->freq_mask && !(c->train_mode && (c->sw.train_no_dec_planes || !c->sw.train_bands)) &&
+                            !c->sw.fp32_only && f.h2() && c->bufs.count("catp") != 0 && !c->sw.no_scatter;
     const bool want_amax = d1_planes || dec_planes;
     // (the words are cleared by the STFT launch below - the first kernel of the stream that carries the audio chain - not by a fill)
 
@@ -531,7 +517,7 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
         // Round 6: conv2 .. conv5 on fp16x2 planes of cat_l's encoder half (conv3g_kernel: three products per multiply, no operand split in
         // the K loop) - the planes' scale is that half's EXACT maximum, published by conv_l's epilogue (as for the decoder, round 5).  With
         // several batches per launch these layers were the register-staged family's largest share (40 - 76 TFLOP/s: 11 % of a grouped call)
-        bool aud_planes = l >= 1 && want_amax && !c->no_aud_planes && f.h2() && c->bufs.count("aencp") != 0 && g.has_h2_filter(name) &&
+        bool aud_planes = l >= 1 && want_amax && !c->sw.no_aud_planes && f.h2() && c->bufs.count("aencp") != 0 && g.has_h2_filter(name) &&
                           conv3g_ok_desc(d, c->enc_c[l]);
         if (aud_planes && !c->tuning) {             // a plan that names a register-staged tile keeps the fp32 operand (no pack pass)
             auto it = c->plan.find(name);
@@ -623,8 +609,7 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
 
     // localization (model.py:241-271).  With the mask decoder present the localisation FCs and the deconv chain are
     // independent consumers of the bottleneck: second fork, the FCs go to the context's stream.
-    static const bool no_fork2 = getenv("SAGEN_NO_FORK2") != nullptr;
-    const bool fork2 = forked && c->freq_mask && !no_fork2;
+    const bool fork2 = forked && c->freq_mask && !c->sw.no_fork2;
     const int nlast_fcm = c->nout * c->nin * (c->nsep + 1);
     if (fcm) {
         // fc1 and fc-feats read the same rows (the bottleneck): one launch; the feats tile (cat5, six frequency columns: the decoder's
@@ -693,8 +678,7 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
     // taps) and rows 1..4 of cat3: each layer contracts the band of input rows it needs and gathers the output rows that are read.
     // SAGEN_FP32_ONLY keeps the round-4 form on the full tensors.  The training step follows the same bands, forward AND backward
     // (train_model.hip: the dead rows carry no gradient; the buffers behind them are zeroed once, at sagen_train_bind).
-    const bool no_scatter = c->no_scatter;
-    const bool lean = (!c->train_mode || c->train_bands) && !c->fp32_only && !no_scatter;
+    const bool lean = (!c->train_mode || c->sw.train_bands) && !c->sw.fp32_only && !c->sw.no_scatter;
     int need_lo[7], need_hi[7];                          // rows of cat_l that the layer below reads
     for (int l = 1; l <= 5; ++l) { need_lo[l] = 0; need_hi[l] = c->enc_h[l]; }
     if (lean) {
@@ -720,8 +704,7 @@ int sagen_forward_impl(sagen_ctx* c, const float* audio, const float* video, con
     // deconv1: only output rows 44..66 (mask frames 1..23) reach the cropped window -> grid rows a = 11..16.
     // Inference: sigmoid and the track-weighted sums run in its epilogue (igemm_epilogue_maskmix) and the 94 MB of logits are never
     // written; the training step keeps them (the adjoint reads them), and so does sagen_set_option("materialize_mask", 1).
-    static const bool no_maskfuse = getenv("SAGEN_NO_MASKFUSE") != nullptr;
-    const bool fused_tail = !no_maskfuse && !c->train_mode && !c->materialize_mask && !c->fp32_only && c->nsep == 32 && c->nin == 1;
+    const bool fused_tail = !c->sw.no_maskfuse && !c->train_mode && !c->materialize_mask && !c->sw.fp32_only && c->nsep == 32 && c->nin == 1;
     c->mask_fused_last = fused_tail;
     if (fork2 && fused_tail) {                           // the epilogue needs the localisation coefficients (three small FCs, long done)
         SAGEN_HIP_CHECK(hipEventRecord(c->ev_join, c->aux));
@@ -783,7 +766,7 @@ void sagen_destroy_impl(sagen_ctx* c) {
 // times every (tile, split-K) candidate of every contraction on the given inputs and stores the plan
 int sagen_autotune_impl(sagen_ctx* c, const float* audio, const float* video, const float* flow, float* out, hipStream_t s) {
     if (!c) return fail(SAGEN_ERR_NULL, "sagen_autotune: null ctx");
-    if (getenv("SAGEN_NO_AUTOTUNE")) return SAGEN_OK;
+    if (c->sw.no_autotune) return SAGEN_OK;
     if (!c->tune_e0) {
         SAGEN_HIP_CHECK(hipEventCreate(&c->tune_e0));
         SAGEN_HIP_CHECK(hipEventCreate(&c->tune_e1));
@@ -871,16 +854,12 @@ int sagen_set_option_impl(sagen_ctx* c, const char* name, int value) {
         c->inter_group = value;
         return SAGEN_OK;
     }
-    if (n == "u8_fast_stem") { c->stem8 = value != 0; return SAGEN_OK; }
-    if (n == "f16_fast_stem") { c->stem16 = value != 0; return SAGEN_OK; }
-    if (n == "u8_stem_h2") { c->stem8h = value != 0; return SAGEN_OK; }
-    if (n == "train_bands") { c->train_bands = value != 0; return SAGEN_OK; }
-    if (n == "train_rawpool") { c->train_rawpool = value != 0; return SAGEN_OK; }
-    if (n == "fp16x2") { c->use_h2 = value != 0; return SAGEN_OK; }
     if (n == "planes_from_stage") { if (value < 2 || value > 6) return fail(SAGEN_ERR_SHAPE, "planes_from_stage in 2..6"); c->p3_from_stage = value; return SAGEN_OK; }
     if (n == "decoder_planes") { c->dec_planes_min_batch = value ? 1 : (1 << 30); return SAGEN_OK; }
     if (n == "plane_gather") { c->use_p3g = c->use_p3 && value != 0; return SAGEN_OK; }
-    if (n == "plane_s2d") { c->use_s2d = value != 0; return SAGEN_OK; }
+#define X(member, kind, dflt, env, opt, doc) if (sw_set(c->sw.member, opt, name, value)) return SAGEN_OK;
+    SAGEN_SWITCHES(X)                      // the rows of switches.h that name an option
+#undef X
     return fail(SAGEN_ERR_UNSUPPORTED, "sagen_set_option: unknown option %s", name);
 }
 

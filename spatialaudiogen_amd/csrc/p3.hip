@@ -263,10 +263,9 @@ int p3_pack_launch(const float* x, const float* scale, const float* shift, const
     if (fmt == 1 && p3 && !(h2 && h2->a_inv)) return fail(SAGEN_ERR_NULL, "p3_pack: the fp16x2 format needs a slot for its scale");
     if (s2d && (fmt != 1 || !p3 || (H & 1) || (W & 1) || p3 == (h2 ? h2->res_planes : nullptr)))
         return fail(SAGEN_ERR_UNSUPPORTED, "p3_pack: the space-to-depth form needs fp16x2 planes of an even-sized tensor, not in place");
-    static const int amort_env = getenv("SAGEN_P3_AMORT") ? atoi(getenv("SAGEN_P3_AMORT")) : 0;
     // (measured with three batches in flight, same box, tools/ab_p3_amort.sh: 1 / 2 / 4 items per thread = 2 508-2 524 / 2 519-2 529 / 2 536-2 544
     //  ambisonic-s/s - the pass alone is no faster with fewer workgroups, but it leaves the CUs to the other batches' matrix kernels sooner)
-    const int amort = amort_env > 0 ? amort_env : 4;
+    const int amort = process_switches().p3_amort > 0 ? (int)process_switches().p3_amort : 4;
     if (fmt == 1)
         hipLaunchKernelGGL(p3_pack_kernel<true>, dim3(aligned_grid(total, C / 8, amort), 1, gi.G), dim3(256), 0, s, x, scale, shift, bn, residual, relu, y,
                            (char*)p3, nrows, W, C, *h2, gi, s2d);

@@ -24,9 +24,9 @@ static inline int ceil16(int x) { return (x + 15) / 16 * 16; }
 enum PkdKind { PKD_NONE = 0, PKD_FLIPT, PKD_STRIDED, PKD_DECONV, PKD_ROWS };
 
 // the stride-1 3x3 data gradients of the trunks on fp16x2 planes (needs the plane kernels and the fp16x2 format of the forward)
-static bool h2d_on(const sagen_ctx* c) { return c->train_h2d && c->train_h2 && c->use_h2 && c->use_p3 && !c->fp32_only; }
+static bool h2d_on(const sagen_ctx* c) { return c->sw.train_h2d && c->sw.train_h2 && c->sw.use_h2 && c->use_p3 && !c->sw.fp32_only; }
 // ... and their weight gradients (wgrad3h.hip; the forward then retains its activation planes)
-static bool h2w_on(const sagen_ctx* c) { return h2d_on(c) && c->train_h2w && c->p3_from_stage <= 2 && wgrad_planes_enabled(); }
+static bool h2w_on(const sagen_ctx* c) { return h2d_on(c) && c->sw.train_h2w && c->p3_from_stage <= 2 && wgrad_planes_enabled(); }
 
 struct PkdSpec { PkdKind kind = PKD_NONE; int N = 0, K = 0, kh = 0, kw = 0, sh = 1, sw = 1, a = 0, b = 0; };
 
@@ -65,8 +65,7 @@ static PkdSpec pkd_spec(const VarSpec& vs) {
 // those of stages 4 and 5 88 -> 98 and 92 -> 137 us: four contractions of 196 tiles each, no split-K into a strided output - so the
 // 3x3 goes phase-wise only where a phase still fills the chip (>= 512 tiles of 64 x 64).
 static bool dgrad_phased(int batch, const std::string& n, const PkdSpec& p) {
-    static const bool off = getenv("SAGEN_DGRAD_UNPHASED") != nullptr;
-    if (off || p.kind != PKD_STRIDED || p.sh != 2 || p.sw != 2 || n.rfind("audio_encoder/", 0) == 0 || p.kh != p.kw) return false;
+    if (process_switches().dgrad_unphased || p.kind != PKD_STRIDED || p.sh != 2 || p.sw != 2 || n.rfind("audio_encoder/", 0) == 0 || p.kh != p.kw) return false;
     if (p.kh == 1) return true;
     if (p.kh != 3) return false;
     const size_t at = n.find("_encoder/conv");
@@ -74,8 +73,7 @@ static bool dgrad_phased(int batch, const std::string& n, const PkdSpec& p) {
     const int st = n[at + 13] - '2';                              // "convS_1": stage index S - 2
     if (st < 1 || st > 3) return false;
     const long tiles = (long)cdiv(batch * RS_H[st] * RS_W[st], 64) * cdiv(p.a, 64);
-    static const long need = getenv("SAGEN_DGRAD_PHASE_TILES") ? atol(getenv("SAGEN_DGRAD_PHASE_TILES")) : 512;      // (tests: 0 = always)
-    return tiles >= need;
+    return tiles >= process_switches().dgrad_phase_tiles;
 }
 static int phase_taps(int k, int r) { return (k - r + 1) / 2; }      // taps dp >= 0 with r + 2 dp < k
 
@@ -250,8 +248,8 @@ static int repack_dgrad(sagen_ctx* c, hipStream_t s) {
 struct Bwd : Fwd {
     int cslot = 0;
     std::string redws = "t:redws";                                // scratch of this launcher's channel reductions
-    bool split_ok = getenv("SAGEN_BWD_NOSPLIT") == nullptr;      // debugging: no split-K in the data-gradient contractions
-    Bwd(sagen_ctx* ctx, hipStream_t st) : Fwd(ctx, st) {}
+    bool split_ok;                                                // (SAGEN_BWD_NOSPLIT: no split-K in the data-gradient contractions)
+    Bwd(sagen_ctx* ctx, hipStream_t st) : Fwd(ctx, st), split_ok(!ctx->sw.bwd_nosplit) {}
 
     // where variable v's gradient goes; the caller is about to enqueue the kernel that writes it (bucket milestones: ms_flush)
     float* grad(const std::string& v) {
@@ -430,8 +428,7 @@ struct Bwd : Fwd {
             const BnRef bn = bn_ref(li, bn_name, npix);
             double* acc = bnb_acc(li);
             layer = "bnbwd:" + bn_name;
-            static const bool no_self = getenv("SAGEN_BN_READ_ACT") != nullptr;
-            const int sm = self_mask && !no_self;
+            const int sm = self_mask && !c->sw.bn_read_act;
             const float* a = (sm || relu_bits) ? nullptr : act;     // (the one-bit mask replaces the fp32 activation: 1/32 of its bytes, twice)
             float* mx = c->p("t:mxpart" + sfx);
             int nb = 0;
@@ -456,8 +453,7 @@ struct Bwd : Fwd {
         const BnRef bn = bn_ref(li, bn_name, npix);
         double* acc = bnb_acc(li);
         layer = "bnbwd:" + bn_name;
-        static const bool no_self = getenv("SAGEN_BN_READ_ACT") != nullptr;     // (A/B: read the retained activation for its sign)
-        const int sm = self_mask && !no_self;
+        const int sm = self_mask && !c->sw.bn_read_act;
         const float* a = sm ? nullptr : act;
         timed("bn_bwd_reduce_kernel", 0.0, [&] { return bn_bwd_reduce_launch(ga, gb, a, y, bn, npix, C, acc, c->p(redws), s, sm); });
         timed("bn_bwd_apply_kernel", 0.0, [&] {
@@ -489,11 +485,10 @@ struct Bwd : Fwd {
             const int li1 = 1 + 2 * k, li2 = 2 + 2 * k;
             // out = relu(bn2(y2) + shortcut)
             const bool planes_on = h2d_on(c) && c->tbufs.count("t:DPc0" + sfx) != 0;
-            static const bool no_relu_bits = getenv("SAGEN_TRAIN_NO_RELU_BITS") != nullptr;      // (A/B: conv_2's batch-norm backward reads the fp32 block output for its ReLU mask)
             void* DP2 = planes_on ? dp_buf(0, k & 1) : nullptr;
             void* DP1 = planes_on ? dp_buf(1, k & 1) : nullptr;
             const bool P2 = bn_bwd(pfx + "/conv_2", li2, ga, gb, out, y2, npix, cout, DY, Z, false, Ho, Wo, DP2, planes_on ? dp_a_inv(0, k & 1) : nullptr, h2w() && !wgrad_reads_fp32_operands(),
-                                   h2w() && !no_relu_bits ? reinterpret_cast<const unsigned char*>(c->p("t:mb:" + ks)) : nullptr);
+                                   h2w() && !c->sw.train_no_relu_bits ? reinterpret_cast<const unsigned char*>(c->p("t:mb:" + ks)) : nullptr);
             {
                 WgradDesc w = wdesc(a1, Ho, Wo, cout, cout, DY, Ho, Wo, cout, cout, 3, 3, 1, 1, -1, -1);
                 if (P2 && h2w()) w = with_planes(w, pl_buf("a1", k), pl_a_inv(k), DP2, dp_a_inv(0, k & 1));
@@ -527,8 +522,7 @@ struct Bwd : Fwd {
         float* dz0 = c->p("t:dz0" + sfx);
         const BnRef bn0 = bn_ref(0, name, (long)B * 112 * 224);
         layer = "poolbwd:" + scope;
-        static const bool unfused = getenv("SAGEN_STEM_BWD_UNFUSED") != nullptr;
-        if (unfused) {
+        if (c->sw.stem_bwd_unfused) {
             timed("maxpool_bwd_kernel", 0.0, [&] { return maxpool_bwd_launch(c->p("y0" + sfx), bn0, c->p("t:x0" + sfx), ga, gb, dz0, B, 112, 224, 64, s); });
             bn_bwd(name, 0, dz0, nullptr, nullptr, c->p("y0" + sfx), (long)B * 112 * 224, 64, dz0, nullptr);       // (in place: elementwise)
         } else {
@@ -798,17 +792,14 @@ int sagen_train_step_impl(sagen_ctx* c, const float* audio, const float* video, 
     if (!c->train_ready) return fail(SAGEN_ERR_WORKSPACE, "sagen_train_step: call sagen_train_bind first");
     // the optimiser updated the variables in place: re-pack the filters.  With two streams only the stems' packs run here; the rest
     // (123 MB of variables -> 430 MB of packs, ~190 us) runs on the second stream behind the STFT, under pad + stem + pool of this one
-    static const bool no_split_repack = getenv("SAGEN_NO_SPLIT_REPACK") != nullptr;
-    const bool split_repack = !no_split_repack && c->ev_pack && c->ev_fork && !c->profiling && sagen_forward_forks(c) && c->train_ready;
+    const bool split_repack = !c->sw.no_split_repack && c->ev_pack && c->ev_fork && !c->profiling && sagen_forward_forks(c) && c->train_ready;
     int rc = split_repack ? sagen_repack_part(c, s, 1) : sagen_repack_impl(c, s);
     c->late_repack = split_repack && !rc;
     // the data-gradient packs are first needed after the forward: on the second stream, under it
-    static const bool one_stream_pack = getenv("SAGEN_BWD_ONE_STREAM") != nullptr;
-    const bool pack_aux = c->aux && c->ev_fork && !one_stream_pack && !c->tuning && !c->profiling;
+    const bool pack_aux = c->aux && c->ev_fork && !c->sw.bwd_one_stream && !c->tuning && !c->profiling;
     // ... enqueued BEHIND the forward's own work on that stream: the main stream's first matrix launch waits for the STFT of the
     // second stream, and with the packs in front of it the stem started 0.2 ms late
-    static const bool packs_first = getenv("SAGEN_DGRAD_PACKS_FIRST") != nullptr;      // (A/B: the round-3 order)
-    if (!rc && pack_aux && packs_first) {
+    if (!rc && pack_aux && c->sw.dgrad_packs_first) {
         SAGEN_HIP_CHECK(hipEventRecord(c->ev_fork, s));
         SAGEN_HIP_CHECK(hipStreamWaitEvent(c->aux, c->ev_fork, 0));
         rc = repack_dgrad(c, c->aux);
@@ -824,7 +815,7 @@ int sagen_train_step_impl(sagen_ctx* c, const float* audio, const float* video, 
     c->train_mode = false;
     if (rc) return rc;
     if (pack_aux) {                                    // (the forward joins the second stream only when it forked)
-        if (!packs_first) {
+        if (!c->sw.dgrad_packs_first) {
             SAGEN_HIP_CHECK(hipStreamWaitEvent(c->aux, c->ev_fork, 0));      // (a forked forward has long passed a later record of it)
             rc = repack_dgrad(c, c->aux);
             if (rc) return rc;
@@ -838,11 +829,10 @@ int sagen_train_step_impl(sagen_ctx* c, const float* audio, const float* video, 
     b.timed("stft_loss_grad_kernel", 0.0, [&] { return stft_loss_grad_launch(pred, target, mask, c->B, c->p("t:dpred"), loss, s); });
     if (b.rc) return b.rc;
     if (loss_out) SAGEN_HIP_CHECK(hipMemcpyAsync(loss_out, loss, sizeof(double), hipMemcpyDeviceToDevice, s));
-    static const bool one_stream = getenv("SAGEN_BWD_ONE_STREAM") != nullptr;
     Bwd w(c, c->aux);
     w.redws = "t:redws2"; w.cslot = CACC_SLOTS / 2; w.wsname = "splitk_aux";      // its own scratch: it runs concurrently with `b`
     // (with the per-launch profiler on, everything stays on one stream: the events then time unoverlapped launches)
-    if (c->aux && !one_stream && !c->tuning && !c->profiling) b.wg = &w;
+    if (c->aux && !c->sw.bwd_one_stream && !c->tuning && !c->profiling) b.wg = &w;
     if (!c->ms_bucket.empty()) {
         c->ms_left = c->ms_count;
         std::fill(c->ms_done.begin(), c->ms_done.end(), 0);
@@ -931,7 +921,7 @@ int sagen_train_get_buffer_impl(const sagen_ctx* c, const char* name, const floa
 int sagen_train_autotune_impl(sagen_ctx* c, const float* audio, const float* video, const float* flow, const float* target,
                               const float* mask, hipStream_t s) {
     if (!c) return fail(SAGEN_ERR_NULL, "sagen_train_autotune: null ctx");
-    if (getenv("SAGEN_NO_AUTOTUNE")) return SAGEN_OK;
+    if (c->sw.no_autotune) return SAGEN_OK;
     if (!c->tune_e0) {
         SAGEN_HIP_CHECK(hipEventCreate(&c->tune_e0));
         SAGEN_HIP_CHECK(hipEventCreate(&c->tune_e1));

@@ -691,16 +691,12 @@ __global__ __launch_bounds__(256) void wgrad_ref_kernel(const WgradDesc d) {
 }
 
 // SAGEN_FP32_ONLY / SAGEN_WGRAD_F32: the exact fp32 MFMA kernel; default: the bf16x3 kernel (fp32-equivalent, finite inputs)
-static bool wgrad_exact() {
-    static const bool exact = getenv("SAGEN_FP32_ONLY") != nullptr || getenv("SAGEN_WGRAD_F32") != nullptr;
-    return exact;
-}
+static bool wgrad_exact() { return process_switches().fp32_only || process_switches().wgrad_f32; }
 static bool wgrad_rowtap(const WgradDesc& d);
 static bool wgrad_planes(const WgradDesc& d);
 int wgrad3h_dispatch(const WgradDesc& d, int bm, unsigned blocks, hipStream_t s);      // (wgrad3h.hip)
 const char* wgrad_kernel_name(const WgradDesc& d) {
-    static const bool ref = getenv("SAGEN_WGRAD_REF") != nullptr;
-    return ref ? "wgrad_ref_kernel" : (wgrad_exact() ? "wgrad_kernel" : (wgrad_planes(d) ? "wgrad3h_kernel" : (wgrad_rowtap(d) ? "wgrad3r_kernel" : "wgrad3_kernel")));
+    return wgrad_reads_fp32_operands() ? "wgrad_ref_kernel" : (wgrad_exact() ? "wgrad_kernel" : (wgrad_planes(d) ? "wgrad3h_kernel" : (wgrad_rowtap(d) ? "wgrad3r_kernel" : "wgrad3_kernel")));
 }
 
 static unsigned magic_of(int dv) { return dv <= 1 ? 0u : (unsigned)((1ull << 32) / (unsigned)dv + 1ull); }
@@ -709,18 +705,14 @@ size_t wgrad_ws_floats(const WgradDesc& d, int splitk) { return splitk > 1 ? (si
 
 // the filter-row kernel runs dense 3-wide stride-1 rows with SAME padding (one pad pixel either side), rows of >= 12 pixels
 static bool wgrad_rowtap(const WgradDesc& d) {
-    static const bool off = getenv("SAGEN_WGRAD_NOROW") != nullptr;
-    return !off && !wgrad_exact() && d.TW == 3 && d.tsw == 1 && d.sw == 1 && d.w0 == -1 && d.WG == d.Wd && d.Wd >= 12;
+    return !process_switches().wgrad_norow && !wgrad_exact() && d.TW == 3 && d.tsw == 1 && d.sw == 1 && d.w0 == -1 && d.WG == d.Wd && d.Wd >= 12;
 }
 // ... and on fp16x2 planes when the caller has both operands in that form: 3x3, SAME in both directions, channels in whole 32s
 bool wgrad_planes_enabled() {
-    static const bool off = getenv("SAGEN_WGRAD_NO_H2") != nullptr || getenv("SAGEN_WGRAD_NOROW") != nullptr;
-    return !off && !wgrad_exact();
+    return !process_switches().wgrad_no_h2 && !process_switches().wgrad_norow && !wgrad_exact();
 }
-bool wgrad_reads_fp32_operands() {          // the reference kernel reads the fp32 tensors whatever planes the descriptor carries
-    static const bool ref = getenv("SAGEN_WGRAD_REF") != nullptr;
-    return ref;
-}
+// SAGEN_WGRAD_REF: the reference kernel reads the fp32 tensors whatever planes the descriptor carries
+bool wgrad_reads_fp32_operands() { return process_switches().wgrad_ref; }
 static bool wgrad_planes(const WgradDesc& d) {
     return wgrad_planes_enabled() && wgrad_rowtap(d) && d.gp && d.dp && d.gp_a_inv && d.dp_a_inv && d.TH == 3 && d.tsh == 1 && d.sh == 1 && d.h0 == -1 &&
            d.HG == d.Hd && d.Cg % 32 == 0 && d.Cd % 32 == 0;
@@ -734,8 +726,7 @@ static WgradShape wgrad_shape(const WgradDesc& d) {
     const long P = w.row ? (long)d.B * d.Hd * (d.Wd + 1) : (long)d.B * d.Hd * d.Wd;
     // 32 / 16 gathered channels, a column of filter rows (the stem / the audio conv1 after their horizontal taps were folded into the
     // channels): four / eight rows per tile
-    static const bool nofold = getenv("SAGEN_WGRAD_NOFOLD") != nullptr;
-    w.fold = (!nofold && !wgrad_exact() && !w.row && d.TW == 1 && d.TH >= 2 && (d.Cg == 32 || d.Cg == 16)) ? 128 / d.Cg : 1;
+    w.fold = (!process_switches().wgrad_nofold && !wgrad_exact() && !w.row && d.TW == 1 && d.TH >= 2 && (d.Cg == 32 || d.Cg == 16)) ? 128 / d.Cg : 1;
     if (w.fold > 1) w.bm = 128;
     w.ntile = w.fold > 1 ? (long)cdiv(d.TH, w.fold) * cdiv(d.Cd, w.bn)
                          : (long)d.TH * (w.row ? 1 : d.TW) * cdiv(d.Cg, w.bm) * cdiv(d.Cd, w.bn);
@@ -746,8 +737,7 @@ static WgradShape wgrad_shape(const WgradDesc& d) {
 // what wgrad_launch would run for d (the op-level tests assert it per case): "<family><BM,BN> fold=F splitk=S"
 void wgrad_describe(const WgradDesc& d, char* buf, size_t n) {
     const WgradShape w = wgrad_shape(d);
-    static const bool ref = getenv("SAGEN_WGRAD_REF") != nullptr;
-    if (ref) snprintf(buf, n, "wgrad_ref_kernel fold=1 splitk=1");
+    if (wgrad_reads_fp32_operands()) snprintf(buf, n, "wgrad_ref_kernel fold=1 splitk=1");
     else snprintf(buf, n, "%s<%d,%d> fold=%d splitk=%d", wgrad_kernel_name(d), w.bm, w.bn, w.fold, std::max(1, d.splitk));
 }
 
@@ -758,7 +748,7 @@ int wgrad_pick_splitk(const WgradDesc& d, size_t ws_capacity_floats) {
     // every workgroup writes its whole tile and the reducer reads it back, 2 x (workgroups x tile bytes) of traffic.  Measured
     // on the 3x3 layers of stages 3-5 (2.4-9.4 MB of gradient, 64-98 KB per tile): 110 us with 1024 workgroups, of which 60 us is
     // partial-sum traffic, 94 us with 512; the stem (57 KB of gradient) 344 us with 1024, 467 us with 512.
-    static const long forced = getenv("SAGEN_WGRAD_WGS") ? std::max(64, atoi(getenv("SAGEN_WGRAD_WGS"))) : 0;
+    const long forced = process_switches().wgrad_wgs;
     const size_t per = (size_t)d.TH * d.TW * d.Cg * d.Cd;
     const long target = forced ? forced : ((1024 / w.ntile) * per * 4 > (32u << 20) ? 512 : 1024);
     long sk = std::max<long>(1, std::min<long>(target / w.ntile, w.nchunks / 8));
@@ -787,9 +777,8 @@ int wgrad_launch(const WgradDesc& d_in, hipStream_t s) {
     d.g_bytes = (unsigned)gb; d.d_bytes = (unsigned)db;
     d.magic_w = magic_of(shp.row ? d.Wd + 1 : d.Wd); d.magic_h = magic_of(d.Hd);
     d.fold = shp.fold;
-    static const bool use_ref = getenv("SAGEN_WGRAD_REF") != nullptr;
     const long total = (long)d.TH * d.TW * d.Cg * d.Cd;
-    if (use_ref) {
+    if (wgrad_reads_fp32_operands()) {
         hipLaunchKernelGGL(wgrad_ref_kernel, dim3(cdiv(total, 256)), dim3(256), 0, s, d);
         SAGEN_LAUNCH_CHECK();
         return SAGEN_OK;
@@ -828,8 +817,7 @@ int wgrad_launch(const WgradDesc& d_in, hipStream_t s) {
 
 // the fixed-order sum of the pixel-range partials (wgrad_launch runs it itself unless d.defer_reduce)
 int wgrad_reduce_launch(const WgradDesc& d, hipStream_t s) {
-    static const bool use_ref = getenv("SAGEN_WGRAD_REF") != nullptr;
-    if (d.splitk <= 1 || use_ref) return SAGEN_OK;
+    if (d.splitk <= 1 || wgrad_reads_fp32_operands()) return SAGEN_OK;
     return splitk_reduce_launch(d.ws, d.splitk, d.TH * d.TW * d.Cg, d.Cd, nullptr, 0, d.out, d.Cd, 1, nullptr, GroupInfo(), s);
 }
 
