@@ -575,6 +575,45 @@ int sagen_jpeg_decode(const uint8_t* bytes, int64_t total_bytes, const sagen_jpe
                       int n_segments, const uint16_t* qtabs, int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, int w, int h,
                       int components, int hs, int vs, uint8_t* out, int32_t* status, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- baseline JPEG encode ---------------------------------------------------------------------------------------------------
+ * The reference gets its frame folders from ffmpeg's "%06d.jpg" extraction (scraping/preprocess.py:183-196) and leaves every later
+ * frame write to the host's libjpeg.  sagen_jpeg_encode takes n frames on the device and writes the ENTROPY-CODED DATA of each,
+ * what stands between the SOS header and FF D9, bit for bit what libjpeg's default path writes (PIL's save with optimize=False)
+ * for the same pixels, quantisation tables and sampling: integer arithmetic end to end.  Headers, FF D9 and the file are the
+ * caller's (spatialaudiogen_amd/jpeg.py).
+ *   frames   [n][h][w][3] uint8 RGB DEVICE for components == 3 (what sagen_reproject and sagen_flow_encode write); [n][h][w] grey
+ *            for components == 1
+ *   hs, vs   luma sampling factors, (1,1), (2,1) or (2,2); chroma is (1,1); grey is (1,1)
+ *   qtabs    [2][64] uint16 DEVICE, luma then chroma, in file (zigzag) order, entries 1..255; grey reads row 0 only.  An entry
+ *            outside 1..255 is found on the device and gives every frame SAGEN_JPEG_ENC_ST_RANGE; nothing divides by zero
+ *   out      [n][stride] uint8 DEVICE
+ *   sizes    [n] int32 DEVICE: the bytes frame f's stream needs (saturating at 2^31 - 1), filled even when that exceeds stride: then
+ *            nothing beyond out[f][stride - 1] is written, the status is CAPACITY and the frame's bytes are unspecified
+ *   status   [n] int32 DEVICE: 0 or a set of SAGEN_JPEG_ENC_ST_* bits; a frame with a non-zero status leaves every other exact
+ * The Huffman tables are the four of Annex K.3 - K.6, compiled in.  No restart intervals.
+ * Arithmetic: Y = (19595 R + 38470 G + 7471 B + 32768) >> 16, Cb = (-11059 R - 21709 G + 32768 B + 8388608 + 32767) >> 16,
+ * Cr = (32768 R - 27439 G - 5329 B + 8388608 + 32767) >> 16; the image's columns are replicated to whole blocks and its rows to a
+ * multiple of vs, chroma is the 2 x 2 or 2 x 1 box mean with the bias alternating by output column (1, 2 / 0, 1), then the
+ * COMPONENT's last row is replicated to whole blocks; the "islow" forward DCT (CONST_BITS 13, PASS1_BITS 2) on samples - 128;
+ * (|c| + 4 q) / (8 q) with the sign put back; DC differences per component over the whole frame; luma blocks of an MCU that lie
+ * wholly outside the image repeat the DC in front of them and hold no AC.  Bits MSB first, the last byte filled with ones, 00
+ * behind every FF.
+ * sagen_jpeg_encode_max_bytes: the stride that can never be too small, 2 ceil(blocks 1658 / 8) + 2 (a block is at most 9 + 11
+ * bits of DC and 63 x (16 + 10) bits of AC; stuffing can double the bytes); 0 for a geometry outside the scope.
+ * Returns: n == 0 SAGEN_OK, nothing touched; a null argument SAGEN_ERR_NULL; SAGEN_ERR_SHAPE for n < 0, w or h < 1, stride < 1 or
+ * not a multiple of 4, out / sizes / status / qtabs / scratch misaligned (4, 4, 4, 2, 16 bytes); SAGEN_ERR_UNSUPPORTED for
+ * components / sampling outside the scope, w or h above 16384, n > 65535, stride > 2^28, more than 2^31 - 1 blocks or frame bytes
+ * per call; SAGEN_ERR_WORKSPACE for scratch smaller than sagen_jpeg_encode_scratch_bytes(...), which is 0 for a geometry the call
+ * would refuse.  A refused call writes nothing. */
+enum {
+    SAGEN_JPEG_ENC_ST_CAPACITY = 1, /* the stream needs more than `stride` bytes; sizes[f] holds what it needs */
+    SAGEN_JPEG_ENC_ST_RANGE = 2     /* a DC difference above category 11 or an AC value above category 10 (or a bad quantiser) */
+};
+size_t sagen_jpeg_encode_scratch_bytes(int n, int w, int h, int components, int hs, int vs, int64_t stride);
+int64_t sagen_jpeg_encode_max_bytes(int w, int h, int components, int hs, int vs);
+int sagen_jpeg_encode(const uint8_t* frames, int n, int w, int h, int components, int hs, int vs, const uint16_t* qtabs, uint8_t* out,
+                      int64_t stride, int32_t* sizes, int32_t* status, void* scratch, size_t scratch_bytes, void* stream);
+
 /* ---- moving point sources: encode to ambisonics, binauralise, track ------------------------------------------------------
  * The front end of the reference's ambisonics toolbox: AmbiEncoder.encode / encode_frame / encode_v2 (pyutils/ambisonics/
  * encoder.py:10-55), SourceBinauralizer over VirtualStereoMic and Convolvotron, static and per frame (binauralizer.py:12-121), and

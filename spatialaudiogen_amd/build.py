@@ -14,7 +14,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, 'csrc')
 OBJ = os.path.join(CSRC, 'build')
 LIB = os.path.join(HERE, 'libsagen_hip.so')
-SOURCES = ['conv3p.hip', 'conv3h.hip', 'conv3s.hip', 'conv3g.hip', 'p3.hip', 'igemm3dw.hip', 'igemm3s2.hip', 'stempool.hip', 'stem8.hip', 'igemm.hip', 'fcm.hip', 'igemm3.hip', 'elementwise.hip', 'fft.hip', 'eval.hip', 'evalx.hip', 'render.hip', 'overlay.hip', 'sources.hip', 'project.hip', 'flow.hip', 'resample.hip', 'jpeg.hip', 'train.hip', 'wgrad.hip', 'wgrad3h.hip', 'backward.hip', 'model.hip', 'train_model.hip', 'api.hip']
+SOURCES = ['conv3p.hip', 'conv3h.hip', 'conv3s.hip', 'conv3g.hip', 'p3.hip', 'igemm3dw.hip', 'igemm3s2.hip', 'stempool.hip', 'stem8.hip', 'igemm.hip', 'fcm.hip', 'igemm3.hip', 'elementwise.hip', 'fft.hip', 'eval.hip', 'evalx.hip', 'render.hip', 'overlay.hip', 'sources.hip', 'project.hip', 'flow.hip', 'resample.hip', 'jpeg.hip', 'jpeg_enc.hip', 'train.hip', 'wgrad.hip', 'wgrad3h.hip', 'backward.hip', 'model.hip', 'train_model.hip', 'api.hip']
 # every header of csrc/ (the listing source_digest() hashes) + the public one: editing any of them rebuilds every object
 HEADERS = sorted(os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith('.h')) + \
           [os.path.join(os.path.dirname(os.path.dirname(CSRC)), 'include', 'sagen.h')]
@@ -116,7 +116,7 @@ CPU_TWIN_LIB = os.path.join(HERE, 'libsagen_cpu.so')
 def build_cpu_twin(force=False):
     """libsagen_cpu.so: the op level of include/sagen.h in plain C++ on host pointers (csrc_cpu/sagen_cpu.cpp) - test infrastructure
     for a container without a GPU (SAGEN_LIB=<this file> python -m pytest tests/test_gpu_ops.py ...), never a fallback."""
-    if force or _stale(CPU_TWIN_LIB, [CPU_TWIN_SRC, HEADERS[-1], os.path.join(CSRC, 'emd_core.h'), os.path.join(CSRC, 'sources_core.h'), os.path.join(CSRC, 'project_core.h'), os.path.join(CSRC, 'flow_core.h'), os.path.join(CSRC, 'resample_core.h'), os.path.join(CSRC, 'jpeg_core.h')]):
+    if force or _stale(CPU_TWIN_LIB, [CPU_TWIN_SRC, HEADERS[-1], os.path.join(CSRC, 'emd_core.h'), os.path.join(CSRC, 'sources_core.h'), os.path.join(CSRC, 'project_core.h'), os.path.join(CSRC, 'flow_core.h'), os.path.join(CSRC, 'resample_core.h'), os.path.join(CSRC, 'jpeg_core.h'), os.path.join(CSRC, 'jpeg_enc_core.h')]):
         cxx = os.environ.get('CXX', 'g++')
         r = subprocess.run([cxx, '-O2', '-ffp-contract=off', '-std=c++17', '-shared', '-fPIC', '-Wall', CPU_TWIN_SRC, '-o', CPU_TWIN_LIB], capture_output=True, text=True)
         if r.returncode != 0:

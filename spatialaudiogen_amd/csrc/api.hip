@@ -6,6 +6,7 @@
 #include "flow_core.h"
 #include "resample_core.h"
 #include "jpeg_core.h"
+#include "jpeg_enc_core.h"
 #include <new>
 #include <cstdlib>
 #include <algorithm>
@@ -720,6 +721,32 @@ int sagen_jpeg_decode(const uint8_t* bytes, int64_t total_bytes, const sagen_jpe
                     "scratch_bytes=%zu)", why, n, w, h, components, hs, vs, (long)total_bytes, n_segments, n_qtabs, n_hufftabs, scratch_bytes);
     return jpeg_decode_launch(bytes, total_bytes, frames, segments, n_segments, qtabs, n_qtabs, hufftabs, n_hufftabs, g, out, status, scratch,
                               (hipStream_t)stream);
+}
+
+size_t sagen_jpeg_encode_scratch_bytes(int n, int w, int h, int components, int hs, int vs, int64_t stride) {
+    JpegEncGeom g;
+    const char* why;
+    if (n <= 0 || jpeg_enc_geom_fill(g, n, w, h, components, hs, vs, stride, &why) != SAGEN_OK) return 0;
+    return jpeg_enc_scratch_layout(g).total;
+}
+
+int64_t sagen_jpeg_encode_max_bytes(int w, int h, int components, int hs, int vs) {
+    JpegEncGeom g;
+    const char* why;
+    if (jpeg_enc_geom_fill(g, 1, w, h, components, hs, vs, 4, &why) != SAGEN_OK) return 0;
+    return jpeg_enc_max_bytes(g.blocks);
+}
+
+int sagen_jpeg_encode(const uint8_t* frames, int n, int w, int h, int components, int hs, int vs, const uint16_t* qtabs, uint8_t* out,
+                      int64_t stride, int32_t* sizes, int32_t* status, void* scratch, size_t scratch_bytes, void* stream) {
+    if (n == 0) return SAGEN_OK;
+    JpegEncGeom g;
+    const char* why;
+    const int rc = jpeg_enc_args_check(g, frames, n, w, h, components, hs, vs, qtabs, out, stride, sizes, status, scratch, scratch_bytes, &why);
+    if (rc != SAGEN_OK)
+        return fail(rc, "sagen_jpeg_encode: %s (n=%d %dx%d components=%d sampling %dx%d stride=%ld scratch_bytes=%zu)", why, n, w, h, components, hs,
+                    vs, (long)stride, scratch_bytes);
+    return jpeg_encode_launch(frames, g, qtabs, out, sizes, status, scratch, (hipStream_t)stream);
 }
 
 int sagen_window_rms(const float* x, int64_t n, int channels, int channel, int64_t first, int64_t hop, int64_t length, int64_t count,

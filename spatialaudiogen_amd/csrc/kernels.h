@@ -419,6 +419,12 @@ int jpeg_decode_launch(const uint8_t* bytes, long long total_bytes, const sagen_
                        const uint16_t* qtabs, int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, const JpegGeom& g, uint8_t* out,
                        int32_t* status, void* scratch, hipStream_t s);
 
+// baseline JPEG encode (jpeg_enc.hip): sagen_jpeg_encode of include/sagen.h; JpegEncGeom is jpeg_enc_core.h's, checked and filled by
+// jpeg_enc_args_check; scratch as jpeg_enc_scratch_layout carves it
+struct JpegEncGeom;
+int jpeg_encode_launch(const uint8_t* frames, const JpegEncGeom& g, const uint16_t* qtabs, uint8_t* out, int32_t* sizes, int32_t* status,
+                       void* scratch, hipStream_t s);
+
 // -----------------------------------------------------------------------------------------
 // training-step pieces (train.hip): stft loss + gradient w.r.t. the prediction, fused Adam over a flat bucket
 // -----------------------------------------------------------------------------------------

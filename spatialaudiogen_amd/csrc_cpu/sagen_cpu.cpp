@@ -25,6 +25,7 @@
 #include "../csrc/flow_core.h"
 #include "../csrc/resample_core.h"
 #include "../csrc/jpeg_core.h"
+#include "../csrc/jpeg_enc_core.h"
 
 namespace {
 
@@ -845,6 +846,34 @@ int sagen_jpeg_decode(const uint8_t* bytes, int64_t total_bytes, const sagen_jpe
                                           components, hs, vs, out, status, scratch, scratch_bytes, &why);
     if (rc != SAGEN_OK) return fail(rc, "sagen_jpeg_decode: %s", why);
     sagen::jpeg_decode_host(bytes, total_bytes, frames, segments, n_segments, qtabs, n_qtabs, hufftabs, n_hufftabs, g, out, status, scratch);
+    return SAGEN_OK;
+}
+
+/* Baseline JPEG encode (include/sagen.h: sagen_jpeg_encode; ffmpeg's "%06d.jpg" behind scraping/preprocess.py:183-196 in the
+ * reference, PIL / libjpeg behind the frame writers here): frame by frame, block by block, bit by bit over the integer core the device
+ * uses (csrc/jpeg_enc_core.h: jpeg_encode_host).  The scratch is checked as the device library checks it, and not used. */
+size_t sagen_jpeg_encode_scratch_bytes(int n, int w, int h, int components, int hs, int vs, int64_t stride) {
+    sagen::JpegEncGeom g;
+    const char* why;
+    if (n <= 0 || sagen::jpeg_enc_geom_fill(g, n, w, h, components, hs, vs, stride, &why) != SAGEN_OK) return 0;
+    return sagen::jpeg_enc_scratch_layout(g).total;
+}
+
+int64_t sagen_jpeg_encode_max_bytes(int w, int h, int components, int hs, int vs) {
+    sagen::JpegEncGeom g;
+    const char* why;
+    if (sagen::jpeg_enc_geom_fill(g, 1, w, h, components, hs, vs, 4, &why) != SAGEN_OK) return 0;
+    return sagen::jpeg_enc_max_bytes(g.blocks);
+}
+
+int sagen_jpeg_encode(const uint8_t* frames, int n, int w, int h, int components, int hs, int vs, const uint16_t* qtabs, uint8_t* out,
+                      int64_t stride, int32_t* sizes, int32_t* status, void* scratch, size_t scratch_bytes, void*) {
+    if (n == 0) return SAGEN_OK;
+    sagen::JpegEncGeom g;
+    const char* why;
+    const int rc = sagen::jpeg_enc_args_check(g, frames, n, w, h, components, hs, vs, qtabs, out, stride, sizes, status, scratch, scratch_bytes, &why);
+    if (rc != SAGEN_OK) return fail(rc, "sagen_jpeg_encode: %s", why);
+    sagen::jpeg_encode_host(frames, g, qtabs, out, sizes, status);
     return SAGEN_OK;
 }
 

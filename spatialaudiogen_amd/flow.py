@@ -1,7 +1,7 @@
 """Estimate dense optical flow on the device and write the flow folder of a clip.
 
     python -m spatialaudiogen_amd.flow VIDEO_DIR FLOW_DIR [--levels L] [--warps W] [--iters I] [--alpha A] [--no_wrap] [--block 64]
-        [--format {jpg,png}] [--overwrite]
+        [--format {jpg,png}] [--encode {host,device}] [--overwrite]
 
 VIDEO_DIR holds the frames %06d.jpg (what `python -m spatialaudiogen_amd.project ... --size 224 448` writes); FLOW_DIR receives
 %06d.jpg (or .png) and flow_limits.npy, float32 [n, 2]: the folder feeder.FlowFrames decodes and the flow encoder reads.  Frame k
@@ -95,9 +95,12 @@ class FlowEstimator(object):
         return ops.optical_flow(torch.cat([first, frames], 0), self.params.struct(h, w))
 
 
-def write_flow_folder(video_dir, flow_dir, params=None, block=64, fmt='jpg', device=None, decode='host'):
+def write_flow_folder(video_dir, flow_dir, params=None, block=64, fmt='jpg', device=None, decode='host', encode='host'):
     """Flow folder of the frames %06d.jpg of video_dir: flow_dir/%06d.<fmt> + flow_dir/flow_limits.npy.  Returns (n, h, w, levels).
-    decode 'device': the frames are decoded on the device (jpeg.load_frames_device) instead of by PIL on the host; same pixels."""
+    decode 'device': the frames are decoded on the device (jpeg.load_frames_device) instead of by PIL on the host; same pixels.
+    encode 'device' (jpg only): the flow frames are encoded on the device (jpeg.JpegEncoder) instead of by PIL on the host; same files."""
+    if encode == 'device' and fmt != 'jpg':
+        raise ValueError('encode=device writes jpg only (fmt=%s)' % fmt)
     import torch
     from .overlay import frame_names, load_frames
     from .project import save_frames
@@ -111,12 +114,18 @@ def write_flow_folder(video_dir, flow_dir, params=None, block=64, fmt='jpg', dev
     if decode == 'device':
         from .jpeg import JpegDecoder
         decoder = JpegDecoder(est.device)
+    if encode == 'device':
+        from .jpeg import JpegEncoder, save_frames_device
+        encoder = JpegEncoder(est.device)                             # quality 95, 4:2:0: what save_frames writes
     for first, stop in block_ranges(len(names), block):
         start = first if prev is None else first + 1
         frames = decoder.decode(names[start:stop]) if decode == 'device' else torch.as_tensor(load_frames(names[start:stop])).to(est.device)
         flow = est.process(frames, prev)
         rgb, lim = ops.flow_encode(flow)
-        save_frames(flow_dir, rgb.cpu().numpy(), start, fmt)
+        if encode == 'device':
+            save_frames_device(flow_dir, rgb, start, encoder)
+        else:
+            save_frames(flow_dir, rgb.cpu().numpy(), start, fmt)
         limits.append(lim.cpu().numpy())
         prev, hw = frames[-1], tuple(frames.shape[1:3])
     np.save(os.path.join(flow_dir, 'flow_limits.npy'), np.concatenate(limits, 0).astype(np.float32))
@@ -148,12 +157,16 @@ def parse_arguments(argv=None):
     parser.add_argument('--overwrite', action='store_true', help='Whether to replace a flow folder that is not empty.')
     parser.add_argument('--gpu', type=int, default=0, help='GPU id')
     parser.add_argument('--decode', default='host', choices=['host', 'device'], help="where the input frames are decoded: host (PIL, one thread) or device (jpeg.py: the files' bytes go to the device; same pixels)")
+    from .project import ENCODE_HELP
+    parser.add_argument('--encode', default='host', choices=['host', 'device'], help=ENCODE_HELP)
     return parser.parse_args(argv)
 
 
 def main(argv=None):
     args = parse_arguments(argv)
     from .overlay import frame_names, check_frame_sizes
+    if args.encode == 'device' and args.format != 'jpg':
+        raise SystemExit('flow: --encode device writes jpg only (--format %s)' % args.format)
     if args.block < 1:
         raise SystemExit('flow: --block takes a positive value')
     if not os.path.isdir(args.video_dir):
@@ -176,7 +189,7 @@ def main(argv=None):
     _lib.lib()
     if not _lib.IS_CPU_TWIN:
         torch.cuda.set_device(args.gpu)
-    n, h, w, levels = write_flow_folder(args.video_dir, args.flow_dir, params, args.block, args.format, decode=args.decode)
+    n, h, w, levels = write_flow_folder(args.video_dir, args.flow_dir, params, args.block, args.format, decode=args.decode, encode=args.encode)
     print('wrote %d flow frames of %dx%d to %s (levels %d, warps %d, iters %d)' % (n, h, w, args.flow_dir, levels, params.warps, params.iters))
 
 

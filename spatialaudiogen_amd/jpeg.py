@@ -8,6 +8,15 @@ the device gets the file bytes and produces [N, H, W, 3] uint8, byte for byte wh
 
 Scope (the header has the details): SOF0, 8 bit, Huffman, one interleaved scan, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0, optional
 restart interval.  A file outside it is decoded by feeder.imread and copied in, with one warning per decoder.
+
+And the way back (sagen_jpeg_encode, csrc/jpeg_enc.hip): frames on the device in, complete files out, byte for byte what PIL's
+Image.fromarray(f).save(path, quality=q, subsampling=s) writes on libjpeg (standard Huffman tables, no restart interval).  The device
+produces the entropy-coded data; the header and FF D9 are put around it here.
+
+    quality_tables(quality)             -> uint16 [2][64], natural order (libjpeg's scaling of Annex K.1 / K.2)
+    encode_header(w, h, components, hs, vs, qtabs) -> bytes: SOI .. SOS
+    JpegEncoder(device, quality, subsampling).encode(frames) -> list of bytes; frames uint8 [n, h, w, 3] or [n, h, w] on the device
+    save_frames_device(out_dir, frames, first, encoder)      the device form of project.save_frames(..., 'jpg')
 """
 import collections
 import ctypes as C
@@ -332,3 +341,136 @@ def _host_decode(data):
 def load_frames_device(names, device=None, decoder=None):
     """[len(names), H, W, 3] uint8 on the device: what torch.as_tensor(overlay.load_frames(names)).to(device) holds."""
     return (decoder or JpegDecoder(device)).decode(list(names))
+
+
+# ---- encode ----------------------------------------------------------------------------------------------------------------------------
+# Annex K.1 / K.2 in natural order; K.3 - K.6 as DHT holds them: 16 counts, then the symbols
+_STD_Q = np.array([[16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56, 14, 17, 22, 29, 51, 87, 80, 62,
+                    18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92, 49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99],
+                   [17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99, 99, 99, 99, 99] + [99] * 32], np.int64)
+_STD_HUFF = [bytes.fromhex(h) for h in (
+    '00010501010101010100000000000000000102030405060708090a0b',
+    '0002010303020403050504040000017d01020300041105122131410613516107227114328191a1082342b1c11552d1f02433627282090a161718191a25262728292a3435363738'
+    '393a434445464748494a535455565758595a636465666768696a737475767778797a838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3'
+    'c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa',
+    '00030101010101010101010000000000000102030405060708090a0b',
+    '00020102040403040705040400010277000102031104052131061241510761711322328108144291a1b1c109233352f0156272d10a162434e125f11718191a262728292a353637'
+    '38393a434445464748494a535455565758595a636465666768696a737475767778797a82838485868788898a92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9ba'
+    'c2c3c4c5c6c7c8c9cad2d3d4d5d6d7d8d9dae2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa')]          # DC0, AC0, DC1, AC1
+_NATURAL = np.array([0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28, 35, 42, 49, 56,
+                     57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63])
+SUBSAMPLING = {'4:4:4': (1, 1), '4:2:2': (2, 1), '4:2:0': (2, 2)}
+
+
+def quality_tables(quality):
+    """uint16 [2][64] in natural order: libjpeg's jpeg_set_quality (baseline: entries clamped to 1..255)."""
+    q = min(max(int(quality), 1), 100)
+    scale = 5000 // q if q < 50 else 200 - 2 * q
+    return np.clip((_STD_Q * scale + 50) // 100, 1, 255).astype(np.uint16)
+
+
+def _segment(marker, body):
+    return bytes([0xFF, marker, (len(body) + 2) >> 8, (len(body) + 2) & 255]) + body
+
+
+def encode_header(w, h, components, hs, vs, qtabs):
+    """SOI, the JFIF APP0 PIL writes without dpi, DQT per table, SOF0, DHT per table, SOS: everything in front of the entropy-coded data.
+    qtabs: [2][64] in natural order."""
+    if components not in (1, 3) or (components == 1 and (hs, vs) != (1, 1)) or (hs, vs) not in SUBSAMPLING.values():
+        raise ValueError('components %d with sampling %dx%d is outside baseline grey / 4:4:4 / 4:2:2 / 4:2:0' % (components, hs, vs))
+    qtabs = np.asarray(qtabs)
+    out = b'\xff\xd8' + _segment(0xE0, b'JFIF\0\x01\x01\0\0\x01\0\x01\0\0')
+    for i in range(1 if components == 1 else 2):
+        out += _segment(0xDB, bytes([i]) + qtabs[i][_NATURAL].astype(np.uint8).tobytes())
+    comps = [(1, (hs << 4) | vs, 0), (2, 0x11, 1), (3, 0x11, 1)][:components]
+    out += _segment(0xC0, bytes([8, h >> 8, h & 255, w >> 8, w & 255, components]) + b''.join(bytes(c) for c in comps))
+    for ident, spec in zip((0x00, 0x10, 0x01, 0x11), _STD_HUFF[:2 if components == 1 else 4]):
+        out += _segment(0xC4, bytes([ident]) + spec)
+    return out + _segment(0xDA, bytes([components]) + b''.join(bytes([c[0], c[2] * 0x11]) for c in comps) + b'\0\x3f\0')
+
+
+def encode_streams(frames, qtabs, hs, vs, stride, out=None):
+    """sagen_jpeg_encode on `frames` (uint8 [n, h, w, 3] or [n, h, w], device memory; the host with the CPU twin); qtabs uint16 [2][64] in
+    natural order (host).  Returns (out [n, stride] uint8, sizes [n] int32, status [n] int32) on that device; nothing is synchronised."""
+    import torch
+    from .ops import _ptr, _stream
+    l = _lib.lib()
+    if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or (frames.dim() == 4 and frames.shape[3] != 3):
+        raise TypeError('frames must be uint8 [n, h, w, 3] (RGB) or [n, h, w] (grey)')
+    frames = frames.contiguous()
+    n, h, w = (int(v) for v in frames.shape[:3])
+    comps = 3 if frames.dim() == 4 else 1
+    dev = frames.device
+    zz = torch.as_tensor(np.ascontiguousarray(np.asarray(qtabs, np.uint16)[:, _NATURAL]).view(np.int16)).to(dev)
+    if out is None:
+        out = torch.empty((n, stride), dtype=torch.uint8, device=dev)
+    sizes = torch.empty(n, dtype=torch.int32, device=dev)
+    status = torch.empty(n, dtype=torch.int32, device=dev)
+    nbytes = int(l.sagen_jpeg_encode_scratch_bytes(n, w, h, comps, hs, vs, stride))
+    scratch = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=dev)
+    _lib.check(l.sagen_jpeg_encode(_ptr(frames), n, w, h, comps, hs, vs, _ptr(zz), _ptr(out), stride, _ptr(sizes), _ptr(status), _ptr(scratch),
+                                   nbytes, _stream()))
+    return out, sizes, status
+
+
+class JpegEncoder(object):
+    """encode(frames) -> list of complete files (bytes), one per frame: what PIL writes for the same pixels at `quality` and `subsampling`
+    ('4:4:4', '4:2:2', '4:2:0'; grey frames [n, h, w] have none).  One device call per block of frames, one copy of sizes + status, one
+    copy of the streams cut at the longest; a frame whose stream does not fit the stride is encoded again, alone, at the bound."""
+
+    def __init__(self, device=None, quality=95, subsampling='4:2:0', stride=None):
+        import torch
+        _lib.lib()
+        if subsampling not in SUBSAMPLING:
+            raise ValueError('subsampling %r is none of %s' % (subsampling, ', '.join(sorted(SUBSAMPLING))))
+        self.device = torch.device(device if device is not None else ('cpu' if _lib.IS_CPU_TWIN else 'cuda'))
+        self.quality, self.subsampling, self.stride = quality, subsampling, stride
+        self.qtabs = quality_tables(quality)
+
+    def _fetch(self, out, longest):
+        """out[:, :longest] on the host, through a pinned buffer"""
+        import torch
+        if out.device.type != 'cuda':
+            return out[:, :longest].numpy()
+        pinned = torch.empty((out.shape[0], longest), dtype=torch.uint8, pin_memory=True)
+        pinned.copy_(out[:, :longest], non_blocking=True)
+        torch.cuda.current_stream().synchronize()
+        return pinned.numpy()
+
+    def encode(self, frames, first=0):
+        """`first`: the number of frames[0], for the message of a frame that cannot be coded."""
+        import torch
+        if not isinstance(frames, torch.Tensor) or frames.device.type != self.device.type:
+            raise TypeError('frames must be a uint8 tensor on %s' % self.device)
+        n = int(frames.shape[0])
+        if n == 0:
+            return []
+        h, w = int(frames.shape[1]), int(frames.shape[2])
+        comps = 3 if frames.dim() == 4 else 1
+        hs, vs = SUBSAMPLING[self.subsampling] if comps == 3 else (1, 1)
+        stride = self.stride if self.stride is not None else max((w * h * comps + 63) // 64 * 64, 4096)
+        head = encode_header(w, h, comps, hs, vs, self.qtabs)
+        out, sizes, status = encode_streams(frames, self.qtabs, hs, vs, stride)
+        both = torch.stack([sizes, status], 0).cpu().numpy()                      # the one copy of both
+        sizes, status = both[0], both[1]
+        for f in np.flatnonzero(status & _lib.SAGEN_JPEG_ENC_ST_RANGE):
+            raise ValueError('frame %d: a coefficient outside what baseline JPEG can code (DC category > 11 or AC category > 10)' % (first + f))
+        longest = int(min(sizes.max(), stride))
+        data = self._fetch(out, longest) if longest else np.zeros((n, 0), np.uint8)
+        files = [head + data[f, :sizes[f]].tobytes() + b'\xff\xd9' for f in range(n)]
+        for f in np.flatnonzero(status & _lib.SAGEN_JPEG_ENC_ST_CAPACITY):
+            bound = (int(_lib.lib().sagen_jpeg_encode_max_bytes(w, h, comps, hs, vs)) + 3) // 4 * 4
+            o, sz, st = encode_streams(frames[f:f + 1], self.qtabs, hs, vs, bound)
+            sz, st = int(sz.cpu()[0]), int(st.cpu()[0])
+            if st:
+                raise RuntimeError('frame %d: status %d at the stride that cannot be too small' % (first + f, st))
+            files[f] = head + self._fetch(o, sz)[0].tobytes() + b'\xff\xd9'
+        return files
+
+
+def save_frames_device(out_dir, frames, first, encoder):
+    """frames (uint8 [n, h, w, 3] on the encoder's device) -> out_dir/%06d.jpg from `first` on: project.save_frames without the raw copy."""
+    import os
+    for i, data in enumerate(encoder.encode(frames, first)):
+        with open(os.path.join(out_dir, '%06d.jpg' % (first + i)), 'wb') as f:
+            f.write(data)

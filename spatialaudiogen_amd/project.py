@@ -2,7 +2,7 @@
 stereo, and the pinhole view of a listener who turns their head.
 
     python -m spatialaudiogen_amd.project IN_DIR OUT_DIR --from {er,er_tb,cube,eac,eac_stereo} --to {er,cube,eac,view} --size H W
-        [--hfov DEG] [--yaw DEG ..] [--pitch DEG ..] [--roll DEG ..] [--supersample S] [--format {jpg,png}] [--overwrite]
+        [--hfov DEG] [--yaw DEG ..] [--pitch DEG ..] [--roll DEG ..] [--supersample S] [--format {jpg,png}] [--encode {host,device}] [--overwrite]
 
 IN_DIR holds the frames %06d.jpg; OUT_DIR receives %06d.jpg (or .png).  `--from eac --to er --size 224 448` turns an EAC clip into
 the video folder deploy and the feeder read.  `--to view --hfov 90 --yaw 0 90` writes what a listener sees whose head turns from 0
@@ -232,6 +232,11 @@ def save_frames(out_dir, frames, first, fmt):
         Image.fromarray(f).save(os.path.join(out_dir, '%06d.jpg' % (first + i)), quality=95)
 
 
+ENCODE_HELP = ("where the output frames are encoded (--format jpg only): host (PIL, one thread, after the raw frames came back) or device "
+               "(jpeg.py: only the files' bytes leave the device; the same files).  Measured on one MI355X, 224x448 at quality 95 (profiles/jpeg_encode_rate.jsonl): host 2 949 frames/s; device 44 575 in blocks of 16, "
+               "91 255 in blocks of 64, 111 778 in blocks of 256: it pays from --block 16, the smallest measured, up.")
+
+
 def prepare_output_dir(out_dir, overwrite):
     held = [f for f in os.listdir(out_dir) if f.endswith(('.png', '.jpg'))] if os.path.isdir(out_dir) else []
     if held and not overwrite:
@@ -265,12 +270,15 @@ def parse_arguments(argv=None):
     parser.add_argument('--gpu', type=int, default=0, help='GPU id')
     parser.add_argument('--block', type=int, default=16, help='frames per device call')
     parser.add_argument('--decode', default='host', choices=['host', 'device'], help="where the input frames are decoded: host (PIL, one thread) or device (jpeg.py: the files' bytes go to the device; same pixels)")
+    parser.add_argument('--encode', default='host', choices=['host', 'device'], help=ENCODE_HELP)
     return parser.parse_args(argv)
 
 
 def main(argv=None):
     args = parse_arguments(argv)
     from .overlay import frame_names, check_frame_sizes, load_frames
+    if args.encode == 'device' and args.format != 'jpg':
+        raise SystemExit('project: --encode device writes jpg only (--format %s)' % args.format)
     if args.dst == 'view' and args.hfov is None:
         raise SystemExit('project: --to view needs --hfov')
     if args.dst != 'view' and args.hfov is not None:
@@ -310,11 +318,17 @@ def main(argv=None):
     if args.decode == 'device':
         from .jpeg import JpegDecoder
         decoder = JpegDecoder(pr.device)
+    if args.encode == 'device':
+        from .jpeg import JpegEncoder, save_frames_device
+        encoder = JpegEncoder(pr.device)                              # quality 95, 4:2:0: what save_frames writes
     for i in range(0, n, args.block):
         block = names[i:i + args.block]
         frames = decoder.decode(block) if args.decode == 'device' else torch.as_tensor(load_frames(block)).to(pr.device)
-        out = pr.process(frames, None if rot is None else rot[i:i + args.block]).cpu().numpy()
-        save_frames(args.output_dir, out, i, args.format)
+        out = pr.process(frames, None if rot is None else rot[i:i + args.block])
+        if args.encode == 'device':
+            save_frames_device(args.output_dir, out, i, encoder)
+        else:
+            save_frames(args.output_dir, out.cpu().numpy(), i, args.format)
     S = pr.supersample or auto_supersample(src, (h, w), dst, pr.size)
     print('wrote %d frames of %dx%d to %s (%s -> %s, supersample %d)' % (n, pr.size[0], pr.size[1], args.output_dir, args.src, args.dst, S))
 
