@@ -116,7 +116,7 @@ CPU_TWIN_LIB = os.path.join(HERE, 'libsagen_cpu.so')
 def build_cpu_twin(force=False):
     """libsagen_cpu.so: the op level of include/sagen.h in plain C++ on host pointers (csrc_cpu/sagen_cpu.cpp) - test infrastructure
     for a container without a GPU (SAGEN_LIB=<this file> python -m pytest tests/test_gpu_ops.py ...), never a fallback."""
-    if force or _stale(CPU_TWIN_LIB, [CPU_TWIN_SRC, HEADERS[-1], os.path.join(CSRC, 'emd_core.h'), os.path.join(CSRC, 'sources_core.h'), os.path.join(CSRC, 'project_core.h'), os.path.join(CSRC, 'flow_core.h'), os.path.join(CSRC, 'resample_core.h'), os.path.join(CSRC, 'jpeg_core.h'), os.path.join(CSRC, 'jpeg_enc_core.h')]):
+    if force or _stale(CPU_TWIN_LIB, [CPU_TWIN_SRC] + HEADERS):      # it includes csrc/op_entries.h and, through it, the *_core.h
         cxx = os.environ.get('CXX', 'g++')
         r = subprocess.run([cxx, '-O2', '-ffp-contract=off', '-std=c++17', '-shared', '-fPIC', '-Wall', CPU_TWIN_SRC, '-o', CPU_TWIN_LIB], capture_output=True, text=True)
         if r.returncode != 0:

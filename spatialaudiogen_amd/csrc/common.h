@@ -7,6 +7,7 @@
 #include <cstring>
 #include "../../include/sagen.h"
 #include "switches.h"
+#include "host_sizes.h"
 
 namespace sagen {
 
@@ -49,7 +50,6 @@ __device__ __forceinline__ T* grp_ptr(T* p, const GroupInfo& gi, int g) {
 // (G = 1) in plain sight.  Launchers without the parameter run one group: Fwd refuses them in a grouped context (Fwd::timed_no_group).
 
 static inline int cdiv(long a, long b) { return (int)((a + b - 1) / b); }
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline int ilog2_exact(int x) {   // -1 if not a power of two
     if (x <= 0 || (x & (x - 1))) return -1;
     int l = 0;

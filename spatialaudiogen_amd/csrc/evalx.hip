@@ -227,8 +227,8 @@ __global__ __launch_bounds__(64) void evalx_emd_kernel(const float* __restrict__
     }
 }
 
-int evalx_emd_launch(const float* p, const float* q, int n_maps, int nodes, const double* cost, double* out, unsigned int* not_converged,
-                     hipStream_t s) {
+int run_eval_emd(const float* p, const float* q, int n_maps, int nodes, const double* cost, double* out, uint32_t* not_converged, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(evalx_emd_kernel, dim3(n_maps, 2), dim3(64), 0, s, p, q, nodes, cost, out, not_converged);
     SAGEN_LAUNCH_CHECK();
     return SAGEN_OK;

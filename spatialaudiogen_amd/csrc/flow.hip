@@ -259,7 +259,8 @@ void jacobi_dispatch(int depth, const FlowCoef* coef, const FlowUV* f0, const Fl
 
 int flow_auto_fuse() { return FLOW_AUTO_FUSE; }
 
-int optical_flow_launch(const uint8_t* frames, const FlowArgs& a, float* flow, void* scratch, hipStream_t s) {
+int run_optical_flow(const uint8_t* frames, const FlowArgs& a, float* flow, void* scratch, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     const int n = a.n_frames, pairs = n - 1, hw = a.h * a.w;
     const size_t pair_stride = (size_t)hw, pyr_stride = flow_level_pixels(a.h, a.w, a.levels), smooth_stride = (size_t)hw;
     // the (u, v) fields first: they are read and written in 16-byte pieces
@@ -307,7 +308,8 @@ int optical_flow_launch(const uint8_t* frames, const FlowArgs& a, float* flow, v
     return SAGEN_OK;
 }
 
-int flow_encode_launch(const float* flow, int n, int h, int w, uint8_t* rgb, float* limits, void* scratch, hipStream_t s) {
+int run_flow_encode(const float* flow, int n, int h, int w, uint8_t* rgb, float* limits, void* scratch, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     const int hw = h * w;
     float* parts = (float*)scratch;
     hipLaunchKernelGGL(flow_minmax_kernel, dim3(FLOW_ENC_PARTS, 1, n), dim3(FLOW_THREADS), 0, s, flow, parts, hw);

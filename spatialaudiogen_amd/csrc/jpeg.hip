@@ -97,9 +97,10 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_pixel_kernel(const uint8_t*
 
 }  // namespace
 
-int jpeg_decode_launch(const uint8_t* bytes, long long total_bytes, const sagen_jpeg_frame* frames, const int32_t* segments, int n_segments,
-                       const uint16_t* qtabs, int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, const JpegGeom& g, uint8_t* out,
-                       int32_t* status, void* scratch, hipStream_t s) {
+int run_jpeg_decode(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_frame* frames, const int32_t* segments, int n_segments,
+                    const uint16_t* qtabs, int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, const JpegGeom& g, uint8_t* out,
+                    int32_t* status, void* scratch, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     const JpegScratch lay = jpeg_scratch_layout(g, n_hufftabs);
     JpegHuff* huff = (JpegHuff*)((char*)scratch + lay.huff);
     int16_t* coef = (int16_t*)((char*)scratch + lay.coef);

@@ -276,8 +276,9 @@ __global__ __launch_bounds__(ENC_THREADS) void jpeg_enc_ff_sums_kernel(const int
 
 }  // namespace
 
-int jpeg_encode_launch(const uint8_t* frames, const JpegEncGeom& g, const uint16_t* qtabs, uint8_t* out, int32_t* sizes, int32_t* status,
-                       void* scratch, hipStream_t s) {
+int run_jpeg_encode(const uint8_t* frames, const JpegEncGeom& g, const uint16_t* qtabs, uint8_t* out, int32_t* sizes, int32_t* status,
+                    void* scratch, void* hip_stream) {       // (`stream` below is the unstuffed bit stream in scratch)
+    const hipStream_t s = (hipStream_t)hip_stream;
     const JpegEncScratch lay = jpeg_enc_scratch_layout(g);
     char* base = (char*)scratch;
     int16_t* coef = (int16_t*)(base + lay.coef);

@@ -1,6 +1,7 @@
 // Launcher declarations of every HIP kernel family of the path (gfx950).
 #pragma once
 #include "common.h"
+#include "op_backends.h"
 #include "wave_reduce.h"
 #include "igemm_tiles.h"
 
@@ -364,66 +365,12 @@ int eval_metrics_c_launch(const float* pred, const float* gt, int B, int C, floa
 size_t evalx_scratch_floats(int B, int C);
 int evalx_mel_env_launch(const float* pred, const float* gt, int B, int C, float* mel_lsd, float* env_mse, float* scratch,
                          hipStream_t s);
-// exact EMD-hat of map pairs p / q [n_maps][nodes] (nodes <= EMD_MAX_NODES) on cost [nodes][nodes]: out [n_maps][2] = dir, dir2
-int evalx_emd_launch(const float* p, const float* q, int n_maps, int nodes, const double* cost, double* out, unsigned int* not_converged,
-                     hipStream_t s);
 
 // -----------------------------------------------------------------------------------------
-// ambisonic rendering (render.hip): the rotated FIR matrix of include/sagen.h (sagen_render_fir), channels 4 or 9
+// the media ops (evalx.hip: EMD; render.hip, overlay.hip, sources.hip, project.hip, flow.hip, resample.hip, jpeg.hip, jpeg_enc.hip):
+// their launchers are the backends sagen::run_<op> of the shared entry points, declared in op_backends.h
 // -----------------------------------------------------------------------------------------
-int render_fir_launch(const float* x, long long n_hist, long long n, int channels, const float* taps, int outputs, int ntaps,
-                      const float* rot, int n_rot, int rot_hop, long long pos0, long long zero_before, float* y, hipStream_t s);
-
-// -----------------------------------------------------------------------------------------
-// power-map overlay (overlay.hip): sagen_power_map_windows / sagen_overlay_blend of include/sagen.h
-// -----------------------------------------------------------------------------------------
-// rms [n_maps][P] of the windows of a strided stream, channels 4 or 9; moments: n_maps * channels (channels + 1) / 2 doubles
-int power_map_windows_launch(const float* ambi, int channels, int stride, long long window, int n_maps, const float* sh, int P, float* rms,
-                             double* moments, hipStream_t s);
-// scratch of the blend: overlay_blend_grid_bytes() of per-node (r, g, b, v), then 4 doubles of clip bounds per frame
-size_t overlay_blend_grid_bytes(int mh, int mw, int n_frames);
-int overlay_blend_launch(const float* maps, long long map0, int mh, int mw, const double* lut, const uint8_t* frames, int n_frames,
-                         long long frame0, int h, int w, int frames_per_map, uint8_t* out, void* scratch, hipStream_t s);
-
-// -----------------------------------------------------------------------------------------
-// reprojection of 360-degree frames (project.hip): sagen_reproject of include/sagen.h; ProjArgs is project_core.h's, checked and
-// filled by proj_args_fill
-// -----------------------------------------------------------------------------------------
-struct ProjArgs;
-int reproject_launch(const uint8_t* src, uint8_t* dst, const double* rot, const ProjArgs& a, hipStream_t s);
-
-// -----------------------------------------------------------------------------------------
-// dense optical flow and its byte coding (flow.hip): sagen_optical_flow / sagen_flow_encode of include/sagen.h; FlowArgs is
-// flow_core.h's, checked and filled by flow_args_fill
-// -----------------------------------------------------------------------------------------
-struct FlowArgs;
 int flow_auto_fuse();
-int optical_flow_launch(const uint8_t* frames, const FlowArgs& a, float* flow, void* scratch, hipStream_t s);
-int flow_encode_launch(const float* flow, int n, int h, int w, uint8_t* rgb, float* limits, void* scratch, hipStream_t s);
-
-// -----------------------------------------------------------------------------------------
-// polyphase FIR resampling and windowed RMS (resample.hip): sagen_resample_fir / sagen_window_rms of include/sagen.h; ResampleArgs is
-// resample_core.h's, checked and filled by resample_args_fill
-// -----------------------------------------------------------------------------------------
-struct ResampleArgs;
-int resample_fir_launch(const float* x, const double* taps, const double* mix, float* y, const ResampleArgs& a, const char** why, hipStream_t s);
-int window_rms_launch(const float* x, int channels, int channel, long long first, long long hop, long long length, long long count,
-                      double* rms, hipStream_t s);
-
-// -----------------------------------------------------------------------------------------
-// baseline JPEG decode (jpeg.hip): sagen_jpeg_decode of include/sagen.h; JpegGeom is jpeg_core.h's, checked and filled by
-// jpeg_args_check; scratch as jpeg_scratch_layout carves it
-// -----------------------------------------------------------------------------------------
-struct JpegGeom;
-int jpeg_decode_launch(const uint8_t* bytes, long long total_bytes, const sagen_jpeg_frame* frames, const int32_t* segments, int n_segments,
-                       const uint16_t* qtabs, int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, const JpegGeom& g, uint8_t* out,
-                       int32_t* status, void* scratch, hipStream_t s);
-
-// baseline JPEG encode (jpeg_enc.hip): sagen_jpeg_encode of include/sagen.h; JpegEncGeom is jpeg_enc_core.h's, checked and filled by
-// jpeg_enc_args_check; scratch as jpeg_enc_scratch_layout carves it
-struct JpegEncGeom;
-int jpeg_encode_launch(const uint8_t* frames, const JpegEncGeom& g, const uint16_t* qtabs, uint8_t* out, int32_t* sizes, int32_t* status,
-                       void* scratch, hipStream_t s);
 
 // -----------------------------------------------------------------------------------------
 // training-step pieces (train.hip): stft loss + gradient w.r.t. the prediction, fused Adam over a flat bucket

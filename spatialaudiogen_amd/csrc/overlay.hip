@@ -256,8 +256,9 @@ __global__ __launch_bounds__(PIX_THREADS) void overlay_pixel_kernel(const double
 
 }  // namespace
 
-int power_map_windows_launch(const float* ambi, int channels, int stride, long long window, int n_maps, const float* sh, int P, float* rms,
-                             double* moments, hipStream_t s) {
+int run_power_map_windows(const float* ambi, int channels, int stride, int64_t window, int n_maps, const float* sh, int P, float* rms,
+                          double* moments, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     const int p_blocks = cdiv(P, 256);
     if (channels == 4) {
         hipLaunchKernelGGL(overlay_moments_kernel<4>, dim3(n_maps), dim3(256), 0, s, ambi, stride, window, moments);
@@ -272,10 +273,9 @@ int power_map_windows_launch(const float* ambi, int channels, int stride, long l
     return SAGEN_OK;
 }
 
-size_t overlay_blend_grid_bytes(int mh, int mw, int n_frames) { return align_up((size_t)n_frames * mh * mw * 4 * sizeof(double), 256); }
-
-int overlay_blend_launch(const float* maps, long long map0, int mh, int mw, const double* lut, const uint8_t* frames, int n_frames,
-                         long long frame0, int h, int w, int frames_per_map, uint8_t* out, void* scratch, hipStream_t s) {
+int run_overlay_blend(const float* maps, int64_t map0, int mh, int mw, const double* lut, const uint8_t* frames, int n_frames,
+                      int64_t frame0, int h, int w, int frames_per_map, uint8_t* out, void* scratch, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     BlendArgs a;
     a.map0 = map0; a.frame0 = frame0; a.mh = mh; a.mw = mw; a.h = h; a.w = w; a.fpm = frames_per_map;
     a.vec = w % 4 == 0 && ((uintptr_t)frames) % 4 == 0 && ((uintptr_t)out) % 4 == 0;

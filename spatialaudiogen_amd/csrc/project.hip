@@ -60,7 +60,8 @@ void launch_dst(const uint8_t* src, uint8_t* dst, const double* rot, const ProjA
 
 }  // namespace
 
-int reproject_launch(const uint8_t* src, uint8_t* dst, const double* rot, const ProjArgs& a, hipStream_t s) {
+int run_reproject(const uint8_t* src, uint8_t* dst, const double* rot, const ProjArgs& a, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     const dim3 grid(cdiv((long)a.dst.fh * a.dst.fw, PROJ_THREADS), a.n < PROJ_GRID_FRAMES ? a.n : PROJ_GRID_FRAMES);
     switch (a.src.kind) {
         case SAGEN_PROJ_ER: launch_dst<SAGEN_PROJ_ER>(src, dst, rot, a, grid, s); break;

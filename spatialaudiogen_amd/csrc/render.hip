@@ -175,8 +175,9 @@ size_t render_fir_lds_bytes(int channels, int ntaps) {
 
 }  // namespace
 
-int render_fir_launch(const float* x, long long n_hist, long long n, int channels, const float* taps, int outputs, int ntaps,
-                      const float* rot, int n_rot, int rot_hop, long long pos0, long long zero_before, float* y, hipStream_t s) {
+int run_render_fir(const float* x, int64_t n_hist, int64_t n, int channels, const float* taps, int outputs, int ntaps, const float* rot,
+                   int n_rot, int rot_hop, int64_t pos0, int64_t zero_before, float* y, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     RenderArgs a;
     a.n_hist = n_hist; a.n = n; a.pos0 = pos0; a.zero_before = zero_before;
     a.outputs = outputs; a.ntaps = ntaps; a.n_rot = n_rot; a.rot_hop = rot_hop;

@@ -78,7 +78,8 @@ __global__ __launch_bounds__(RS_THREADS) void window_rms_kernel(const float* __r
 
 }  // namespace
 
-int resample_fir_launch(const float* x, const double* taps, const double* mix, float* y, const ResampleArgs& a, const char** why, hipStream_t s) {
+int run_resample_fir(const float* x, const double* taps, const double* mix, float* y, const ResampleArgs& a, const char** why, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     // the widest channel group whose staged run leaves room for at least 16 outputs' worth of rows, then the longest tile that fits
     int group = a.c_out < RS_MAX_GROUP ? a.c_out : RS_MAX_GROUP;
     while (group > 1 && (long long)(a.T + 16) * group > RS_LDS_DOUBLES) group = (group + 1) / 2;
@@ -98,8 +99,9 @@ int resample_fir_launch(const float* x, const double* taps, const double* mix, f
     return SAGEN_OK;
 }
 
-int window_rms_launch(const float* x, int channels, int channel, long long first, long long hop, long long length, long long count,
-                      double* rms, hipStream_t s) {
+int run_window_rms(const float* x, int channels, int channel, int64_t first, int64_t hop, int64_t length, int64_t count, double* rms,
+                   void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     const dim3 grid(cdiv(count, RS_THREADS / 64));
     hipLaunchKernelGGL(window_rms_kernel, grid, dim3(RS_THREADS), 0, s, x, channels, channel, first, hop, length, count, rms);
     SAGEN_LAUNCH_CHECK();

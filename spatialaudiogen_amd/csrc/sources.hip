@@ -192,87 +192,34 @@ __global__ __launch_bounds__(SRC_T) void sources_hrir_kernel(const float* __rest
     }
 }
 
-int fill(const char* who, SourceSet& ss, const double* ctrl, const int32_t* pt_off, const int64_t* nframes, const double* duration,
-         int n_sources, double rate, int64_t t_first, int64_t t_last) {
-    const char* why;
-    const int rc = source_set_fill(ss, ctrl, pt_off, nframes, duration, n_sources, rate, t_first, t_last, &why);
-    return rc == SAGEN_OK ? rc : fail(rc, "%s: %s", who, why);
-}
-
-long long longest(const SourceSet& ss) {
-    long long m = 0;
-    for (int s = 0; s < ss.n_sources; ++s) m = ss.nframes[s] > m ? ss.nframes[s] : m;
-    return m;
-}
-
-constexpr int64_t SRC_MAX_N = (int64_t)1 << 31;       // samples per call (the grid is n / 256 workgroups)
-
 }  // namespace
 
-}  // namespace sagen
-
-using namespace sagen;
-
-extern "C" {
-
-int sagen_source_track(const double* ctrl, const int32_t* pt_off, const int64_t* nframes, const double* duration, int n_sources, double rate,
-                       int64_t t0, int64_t n, int64_t stride, const double* dirs, int n_dirs, double* unit, int32_t* nearest, void* stream) {
-    if (!unit && !nearest) return fail(SAGEN_ERR_NULL, "sagen_source_track: null argument (unit and nearest)");
-    if (nearest && !dirs) return fail(SAGEN_ERR_NULL, "sagen_source_track: nearest needs dirs");
-    if (n < 1 || stride < 1 || (nearest && n_dirs < 1)) return fail(SAGEN_ERR_SHAPE, "sagen_source_track: n=%ld stride=%ld n_dirs=%d", (long)n, (long)stride, n_dirs);
-    if (nearest && n_dirs > SRC_MAX_DIRS) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_source_track: n_dirs=%d (supported: <= %d)", n_dirs, SRC_MAX_DIRS);
-    if (n > SRC_MAX_N / SRC_MAX_SOURCES) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_source_track: n=%ld samples in one call", (long)n);
-    SourceSet ss;
-    const int rc = fill("sagen_source_track", ss, ctrl, pt_off, nframes, duration, n_sources, rate, t0, t0 + (n - 1) * stride);
-    if (rc != SAGEN_OK) return rc;
-    hipLaunchKernelGGL(sources_track_kernel, dim3(cdiv(n * n_sources, 256)), dim3(256), 0, (hipStream_t)stream, ctrl, ss, (long long)t0, (long long)n,
+// ---- the backends of the entry points (op_entries.h), which have checked every argument and filled the SourceSet ----
+int run_source_track(const double* ctrl, const SourceSet& ss, int64_t t0, int64_t n, int64_t stride, const double* dirs, int n_dirs,
+                     double* unit, int32_t* nearest, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(sources_track_kernel, dim3(cdiv(n * ss.n_sources, 256)), dim3(256), 0, s, ctrl, ss, (long long)t0, (long long)n,
                        (long long)stride, dirs, n_dirs, unit, (int*)nearest);
     SAGEN_LAUNCH_CHECK();
     return SAGEN_OK;
 }
 
-int sagen_encode_sources(const float* signals, int64_t ld, const double* ctrl, const int32_t* pt_off, const int64_t* nframes,
-                         const double* duration, int n_sources, double rate, int channels, int distance_model, double radius, int64_t t0,
-                         int64_t n, float* ambi, void* stream) {
-    if (!signals || !ambi) return fail(SAGEN_ERR_NULL, "sagen_encode_sources: null argument");
-    if (n < 1 || ld < 1 || channels < 1) return fail(SAGEN_ERR_SHAPE, "sagen_encode_sources: n=%ld ld=%ld channels=%d", (long)n, (long)ld, channels);
-    if (channels != 4 && channels != 9)
-        return fail(SAGEN_ERR_UNSUPPORTED, "sagen_encode_sources: channels=%d (supported: 4 and 9, ambisonic orders 1 and 2)", channels);
-    if (n > SRC_MAX_N) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_encode_sources: n=%ld samples in one call", (long)n);
-    if (distance_model != 0 && !(distance_model == 1 && radius > 0.))
-        return fail(SAGEN_ERR_SHAPE, "sagen_encode_sources: distance_model=%d radius=%g (0, or 1 with radius > 0)", distance_model, radius);
-    SourceSet ss;
-    const int rc = fill("sagen_encode_sources", ss, ctrl, pt_off, nframes, duration, n_sources, rate, t0, t0 + n - 1);
-    if (rc != SAGEN_OK) return rc;
-    if (ld < longest(ss)) return fail(SAGEN_ERR_SHAPE, "sagen_encode_sources: ld=%ld is shorter than a source's nframes", (long)ld);
-    if (channels == 4 && ((uintptr_t)ambi) % 16) return fail(SAGEN_ERR_SHAPE, "sagen_encode_sources: a 4-channel ambi must be 16-byte aligned");
+int run_encode_sources(const float* signals, int64_t ld, const double* ctrl, const SourceSet& ss, int channels, int distance_model,
+                       double radius, int64_t t0, int64_t n, float* ambi, void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
     const dim3 grid(cdiv(n, 256));
     if (channels == 4)
-        hipLaunchKernelGGL(sources_encode_kernel<4>, grid, dim3(256), 0, (hipStream_t)stream, signals, (long long)ld, ctrl, ss, distance_model, radius,
+        hipLaunchKernelGGL(sources_encode_kernel<4>, grid, dim3(256), 0, s, signals, (long long)ld, ctrl, ss, distance_model, radius,
                            (long long)t0, (long long)n, ambi);
     else
-        hipLaunchKernelGGL(sources_encode_kernel<9>, grid, dim3(256), 0, (hipStream_t)stream, signals, (long long)ld, ctrl, ss, distance_model, radius,
+        hipLaunchKernelGGL(sources_encode_kernel<9>, grid, dim3(256), 0, s, signals, (long long)ld, ctrl, ss, distance_model, radius,
                            (long long)t0, (long long)n, ambi);
     SAGEN_LAUNCH_CHECK();
     return SAGEN_OK;
 }
 
-int sagen_binauralize_sources(const float* signals, int64_t ld, const double* ctrl, const int32_t* pt_off, const int64_t* nframes,
-                              const double* duration, int n_sources, double rate, int mode, const double* dirs, const float* hrir, int n_dirs,
-                              int ntaps, int64_t zero_before, int64_t t0, int64_t n, float* y, void* stream) {
-    if (!signals || !y) return fail(SAGEN_ERR_NULL, "sagen_binauralize_sources: null argument");
-    if (mode != SAGEN_SOURCES_MIC && mode != SAGEN_SOURCES_HRIR) return fail(SAGEN_ERR_SHAPE, "sagen_binauralize_sources: mode=%d", mode);
-    if (mode == SAGEN_SOURCES_HRIR && (!dirs || !hrir)) return fail(SAGEN_ERR_NULL, "sagen_binauralize_sources: the hrir mode needs dirs and hrir");
-    if (n < 1 || ld < 1 || (mode == SAGEN_SOURCES_HRIR && (n_dirs < 1 || ntaps < 1)))
-        return fail(SAGEN_ERR_SHAPE, "sagen_binauralize_sources: n=%ld ld=%ld n_dirs=%d ntaps=%d", (long)n, (long)ld, n_dirs, ntaps);
-    if (mode == SAGEN_SOURCES_HRIR && (n_dirs > SRC_MAX_DIRS || ntaps > SRC_MAX_TAPS))
-        return fail(SAGEN_ERR_UNSUPPORTED, "sagen_binauralize_sources: n_dirs=%d ntaps=%d (supported: <= %d, <= %d)", n_dirs, ntaps, SRC_MAX_DIRS, SRC_MAX_TAPS);
-    if (n > SRC_MAX_N) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_binauralize_sources: n=%ld samples in one call", (long)n);
-    SourceSet ss;
-    const int rc = fill("sagen_binauralize_sources", ss, ctrl, pt_off, nframes, duration, n_sources, rate, t0, t0 + n - 1);
-    if (rc != SAGEN_OK) return rc;
-    if (ld < longest(ss)) return fail(SAGEN_ERR_SHAPE, "sagen_binauralize_sources: ld=%ld is shorter than a source's nframes", (long)ld);
-    if (((uintptr_t)y) % 8) return fail(SAGEN_ERR_SHAPE, "sagen_binauralize_sources: y must be 8-byte aligned");
+int run_binauralize_sources(const float* signals, int64_t ld, const double* ctrl, const SourceSet& ss, int mode, const double* dirs,
+                            const float* hrir, int n_dirs, int ntaps, int64_t zero_before, int64_t t0, int64_t n, float* y, void* stream) {
     const hipStream_t s = (hipStream_t)stream;
     if (mode == SAGEN_SOURCES_MIC) {
         hipLaunchKernelGGL(sources_mic_kernel, dim3(cdiv(n, 256)), dim3(256), 0, s, signals, (long long)ld, ctrl, ss, (long long)t0, (long long)n, y);
@@ -291,4 +238,4 @@ int sagen_binauralize_sources(const float* signals, int64_t ld, const double* ct
     return SAGEN_OK;
 }
 
-}  // extern "C"
+}  // namespace sagen

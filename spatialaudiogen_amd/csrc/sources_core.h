@@ -28,6 +28,7 @@ namespace sagen {
 constexpr int SRC_MAX_SOURCES = 64;
 constexpr int SRC_MAX_DIRS = 4096;
 constexpr int SRC_MAX_TAPS = 512;
+constexpr int64_t SRC_MAX_N = (int64_t)1 << 31;  // samples per call (the device's grid is n / 256 workgroups)
 constexpr double SRC_SPEED_OF_SOUND = 343.;      // binauralizer.py:9, encoder.py:49
 constexpr double SRC_EAR_Y = 0.1;                // VirtualStereoMic: ears at (0, +-0.1, 0) (binauralizer.py:13-16)
 constexpr double SRC_TIE = 1e-12;                // HrirSet.closest: every candidate this close to the maximum ties

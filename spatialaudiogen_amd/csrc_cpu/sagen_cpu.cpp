@@ -9,6 +9,11 @@
 // What it is NOT: a fallback.  It is never loaded unless SAGEN_LIB names it explicitly, the context / forward / training
 // entry points do not exist here (the Python binding refuses them), and it shares no code with the test checker.
 // Each function cites the reference it follows, like the header.
+//
+// Two halves.  The network's op level above is an independent restatement, entry points and checks included.  The media ops
+// (rendering, overlay, sources, reprojection, flow, resampling, JPEG, EMD) share with the device library their arithmetic
+// (csrc/*_core.h) AND their entry points (csrc/op_entries.h, included here): what is refused, with which code and message, is
+// the device library's by construction, and this file keeps only the loops, as the backends sagen::run_<op> of that header.
 #include <algorithm>
 #include <cmath>
 #include <complex>
@@ -18,25 +23,21 @@
 #include <cstring>
 #include <vector>
 
-#include "../../include/sagen.h"
-#include "../csrc/emd_core.h"
-#include "../csrc/sources_core.h"
-#include "../csrc/project_core.h"
-#include "../csrc/flow_core.h"
-#include "../csrc/resample_core.h"
-#include "../csrc/jpeg_core.h"
-#include "../csrc/jpeg_enc_core.h"
+#include "../csrc/op_entries.h"
 
 namespace {
-
 thread_local char g_err[512] = "";
-int fail(int code, const char* fmt, ...) {
+}
+
+int sagen::fail(int code, const char* fmt, ...) {
     va_list ap;
     va_start(ap, fmt);
     vsnprintf(g_err, sizeof g_err, fmt, ap);
     va_end(ap);
     return code;
 }
+
+namespace {
 
 typedef std::complex<double> cd;
 
@@ -336,16 +337,15 @@ int sagen_assemble_wyzx(const float* audio, const float* ambi_yzx, float* out_wy
     return SAGEN_OK;
 }
 
+}  // extern "C"
+
+/* ---- the media ops: the backends of csrc/op_entries.h, which has checked every argument ---- */
+namespace sagen {
+
 /* The rotated FIR matrix of the renderings (include/sagen.h: sagen_render_fir; binauralizer.py:18-36, 63-76, 124-166, decoder.py:24-28,
  * myutils.py:289): rotate every row by the matrix interpolated at its absolute position, then the direct-form sum in double */
-int sagen_render_fir(const float* x, int64_t n_hist, int64_t n, int channels, const float* taps, int outputs, int ntaps, const float* rot,
-                     int n_rot, int rot_hop, int64_t pos0, int64_t zero_before, float* y, void*) {
-    if (!x || !taps || !y) return fail(SAGEN_ERR_NULL, "sagen_render_fir: null argument");
-    if (n_hist < 0 || n <= 0 || channels <= 0 || outputs <= 0 || ntaps <= 0 || pos0 < 0 || n_hist > pos0)
-        return fail(SAGEN_ERR_SHAPE, "sagen_render_fir: bad sizes");
-    if (rot && (n_rot <= 0 || rot_hop <= 0)) return fail(SAGEN_ERR_SHAPE, "sagen_render_fir: n_rot=%d rot_hop=%d", n_rot, rot_hop);
-    if ((channels != 4 && channels != 9) || outputs > 32 || ntaps > 512)
-        return fail(SAGEN_ERR_UNSUPPORTED, "sagen_render_fir: channels=%d outputs=%d ntaps=%d", channels, outputs, ntaps);
+int run_render_fir(const float* x, int64_t n_hist, int64_t n, int channels, const float* taps, int outputs, int ntaps, const float* rot,
+                   int n_rot, int rot_hop, int64_t pos0, int64_t zero_before, float* y, void*) {
     const int C = channels;
     const int64_t rows = n_hist + n;
     std::vector<double> xr((size_t)rows * C);
@@ -380,16 +380,8 @@ int sagen_render_fir(const float* x, int64_t n_hist, int64_t n, int channels, co
 
 /* The maps of a strided stream (include/sagen.h: sagen_power_map_windows; distance.py:41-52 over myutils.py:252's ambix[::5]): the
  * definition itself, every node's projection squared and averaged in double */
-size_t sagen_power_map_windows_scratch_bytes(int n_maps, int channels) {
-    return n_maps > 0 && (channels == 4 || channels == 9) ? (size_t)n_maps * (channels * (channels + 1) / 2) * sizeof(double) : 0;
-}
-int sagen_power_map_windows(const float* ambi, int64_t n_rows, int channels, int stride, int64_t window, const float* sh, int p, float* rms,
-                            void*, size_t, void*) {
-    if (n_rows < 0 || stride <= 0 || window <= 0 || p <= 0) return fail(SAGEN_ERR_SHAPE, "sagen_power_map_windows: bad sizes");
-    if (channels != 4 && channels != 9) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_power_map_windows: channels=%d", channels);
-    const int64_t n_maps = ((n_rows + stride - 1) / stride) / window;
-    if (n_maps == 0) return SAGEN_OK;
-    if (!ambi || !sh || !rms) return fail(SAGEN_ERR_NULL, "sagen_power_map_windows: null argument");
+int run_power_map_windows(const float* ambi, int channels, int stride, int64_t window, int n_maps, const float* sh, int p, float* rms,
+                          double*, void*) {
     for (int64_t m = 0; m < n_maps; ++m)
         for (int d = 0; d < p; ++d) {
             double s = 0.0;
@@ -406,9 +398,6 @@ int sagen_power_map_windows(const float* ambi, int64_t n_rows, int channels, int
 
 /* myutils.py:255-279 for a run of frames (include/sagen.h: sagen_overlay_blend): whole arrays at a time, the way the reference's
  * numpy does it - normalise the maps, mix, colour, resize (the header's restatement of scikit-image 0.13.1), blend, truncate */
-size_t sagen_overlay_blend_scratch_bytes(int n_maps, int mh, int mw, int n_frames) {
-    return n_maps > 0 && mh > 0 && mw > 0 && n_frames > 0 ? 256 : 0;
-}
 namespace {
 // resize of one [mh][mw][nc] array to [h][w][nc]
 std::vector<double> resize_bilinear(const std::vector<double>& a, int mh, int mw, int nc, int h, int w) {
@@ -432,16 +421,11 @@ std::vector<double> resize_bilinear(const std::vector<double>& a, int mh, int mw
     return o;
 }
 }  // namespace
-int sagen_overlay_blend(const float* maps, int n_maps, int64_t map0, int mh, int mw, const double* lut, const uint8_t* frames, int n_frames,
-                        int64_t frame0, int h, int w, int frames_per_map, uint8_t* out, void*, size_t, void*) {
-    if (n_maps < 0 || map0 < 0 || mh <= 0 || mw <= 0 || n_frames < 0 || frame0 < 0 || h <= 0 || w <= 0 || frames_per_map <= 0)
-        return fail(SAGEN_ERR_SHAPE, "sagen_overlay_blend: bad sizes");
-    if (n_frames == 0) return SAGEN_OK;
-    if (!maps || !lut || !frames || !out) return fail(SAGEN_ERR_NULL, "sagen_overlay_blend: null argument");
-    if (frame0 / frames_per_map < map0 || (frame0 + n_frames - 1) / frames_per_map + 1 >= map0 + n_maps)
-        return fail(SAGEN_ERR_SHAPE, "sagen_overlay_blend: the frames need maps outside %ld..%ld", (long)map0, (long)(map0 + n_maps - 1));
+int run_overlay_blend(const float* maps, int64_t map0, int mh, int mw, const double* lut, const uint8_t* frames, int n_frames,
+                      int64_t frame0, int h, int w, int frames_per_map, uint8_t* out, void*, void*) {
     const int N = mh * mw;
-    std::vector<double> norm((size_t)std::max(n_maps, 0) * N);
+    const int n_maps = (int)((frame0 + n_frames - 1) / frames_per_map + 1 - map0) + 1;      // up to the last frame's `cur` map
+    std::vector<double> norm((size_t)n_maps * N);
     for (int m = 0; m < n_maps; ++m) {
         const float* r = maps + (size_t)m * N;
         const double lo = *std::min_element(r, r + N), hi = *std::max_element(r, r + N);
@@ -450,7 +434,6 @@ int sagen_overlay_blend(const float* maps, int n_maps, int64_t map0, int mh, int
     std::vector<double> v(N), colour((size_t)N * 3);
     for (int f = 0; f < n_frames; ++f) {
         const int64_t F = frame0 + f, prev = F / frames_per_map - map0, cur = prev + 1;
-        if (prev < 0 || cur >= n_maps) return fail(SAGEN_ERR_SHAPE, "sagen_overlay_blend: frame %ld needs a map that was not given", (long)F);
         const double beta = (double)(F % frames_per_map) / (double)frames_per_map;
         for (int n = 0; n < N; ++n) {
             double t = (1 - beta) * norm[(size_t)prev * N + n] + beta * norm[(size_t)cur * N + n];
@@ -472,10 +455,7 @@ int sagen_overlay_blend(const float* maps, int n_maps, int64_t map0, int mh, int
 }
 
 // emd/dir, emd/dir2 (distance.py:100-143): the solver core of the device kernel (csrc/emd_core.h) run by one host "lane"
-int sagen_eval_emd(const float* p, const float* q, int n_maps, int nodes, const double* cost, double* emd, uint32_t* not_converged, void*) {
-    if (!p || !q || !cost || !emd || !not_converged) return fail(SAGEN_ERR_NULL, "sagen_eval_emd: null argument");
-    if (n_maps <= 0 || nodes <= 0) return fail(SAGEN_ERR_SHAPE, "sagen_eval_emd: n_maps=%d nodes=%d", n_maps, nodes);
-    if (nodes > sagen::EMD_MAX_NODES) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_eval_emd: nodes=%d", nodes);
+int run_eval_emd(const float* p, const float* q, int n_maps, int nodes, const double* cost, double* emd, uint32_t* not_converged, void*) {
     std::vector<sagen::EmdState> st(1);
     std::vector<double> P(nodes), Q(nodes);
     const sagen::EmdSerial w;
@@ -508,23 +488,11 @@ int src_nearest(const double* dirs, int D, const double u[3]) {
     const int f = sagen::nearest_first(dirs, 0, D, u, sagen::nearest_max(dirs, D, u, -INFINITY), -1);
     return f < 0 ? 0 : f;
 }
-int src_fill(const char* who, sagen::SourceSet& ss, const double* ctrl, const int32_t* pt_off, const int64_t* nframes, const double* duration,
-             int n_sources, double rate, int64_t t_first, int64_t t_last) {
-    const char* why;
-    const int rc = sagen::source_set_fill(ss, ctrl, pt_off, nframes, duration, n_sources, rate, t_first, t_last, &why);
-    return rc == SAGEN_OK ? rc : fail(rc, "%s: %s", who, why);
-}
 }  // namespace
 
-int sagen_source_track(const double* ctrl, const int32_t* pt_off, const int64_t* nframes, const double* duration, int n_sources, double rate,
-                       int64_t t0, int64_t n, int64_t stride, const double* dirs, int n_dirs, double* unit, int32_t* nearest, void*) {
-    if (!unit && !nearest) return fail(SAGEN_ERR_NULL, "sagen_source_track: null argument (unit and nearest)");
-    if (nearest && !dirs) return fail(SAGEN_ERR_NULL, "sagen_source_track: nearest needs dirs");
-    if (n < 1 || stride < 1 || (nearest && n_dirs < 1)) return fail(SAGEN_ERR_SHAPE, "sagen_source_track: bad sizes");
-    if (nearest && n_dirs > sagen::SRC_MAX_DIRS) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_source_track: n_dirs=%d", n_dirs);
-    sagen::SourceSet ss;
-    const int rc = src_fill("sagen_source_track", ss, ctrl, pt_off, nframes, duration, n_sources, rate, t0, t0 + (n - 1) * stride);
-    if (rc != SAGEN_OK) return rc;
+int run_source_track(const double* ctrl, const SourceSet& ss, int64_t t0, int64_t n, int64_t stride, const double* dirs, int n_dirs,
+                     double* unit, int32_t* nearest, void*) {
+    const int n_sources = ss.n_sources;
     for (int64_t i = 0; i < n; ++i)
         for (int s = 0; s < n_sources; ++s) {
             const SrcPoint p = src_at(ctrl, ss, s, t0 + i * stride);
@@ -535,18 +503,11 @@ int sagen_source_track(const double* ctrl, const int32_t* pt_off, const int64_t*
     return SAGEN_OK;
 }
 
-int sagen_encode_sources(const float* signals, int64_t ld, const double* ctrl, const int32_t* pt_off, const int64_t* nframes,
-                         const double* duration, int n_sources, double rate, int channels, int distance_model, double radius, int64_t t0,
-                         int64_t n, float* ambi, void*) {
-    if (!signals || !ambi) return fail(SAGEN_ERR_NULL, "sagen_encode_sources: null argument");
-    if (n < 1 || ld < 1 || channels < 1) return fail(SAGEN_ERR_SHAPE, "sagen_encode_sources: bad sizes");
-    if (channels != 4 && channels != 9) return fail(SAGEN_ERR_UNSUPPORTED, "sagen_encode_sources: channels=%d", channels);
-    if (distance_model != 0 && !(distance_model == 1 && radius > 0.)) return fail(SAGEN_ERR_SHAPE, "sagen_encode_sources: distance_model=%d radius=%g", distance_model, radius);
-    sagen::SourceSet ss;
-    const int rc = src_fill("sagen_encode_sources", ss, ctrl, pt_off, nframes, duration, n_sources, rate, t0, t0 + n - 1);
-    if (rc != SAGEN_OK) return rc;
-    for (int s = 0; s < n_sources; ++s)
-        if (ld < nframes[s]) return fail(SAGEN_ERR_SHAPE, "sagen_encode_sources: ld=%ld is shorter than a source's nframes", (long)ld);
+int run_encode_sources(const float* signals, int64_t ld, const double* ctrl, const SourceSet& ss, int channels, int distance_model,
+                       double radius, int64_t t0, int64_t n, float* ambi, void*) {
+    const int n_sources = ss.n_sources;
+    const double rate = ss.rate;
+    const long long* nframes = ss.nframes;
     for (int64_t i = 0; i < n; ++i) {
         const int64_t t = t0 + i;
         double acc[9] = {0.};
@@ -570,21 +531,12 @@ int sagen_encode_sources(const float* signals, int64_t ld, const double* ctrl, c
     return SAGEN_OK;
 }
 
-int sagen_binauralize_sources(const float* signals, int64_t ld, const double* ctrl, const int32_t* pt_off, const int64_t* nframes,
-                              const double* duration, int n_sources, double rate, int mode, const double* dirs, const float* hrir, int n_dirs,
-                              int ntaps, int64_t zero_before, int64_t t0, int64_t n, float* y, void*) {
-    if (!signals || !y) return fail(SAGEN_ERR_NULL, "sagen_binauralize_sources: null argument");
-    if (mode != SAGEN_SOURCES_MIC && mode != SAGEN_SOURCES_HRIR) return fail(SAGEN_ERR_SHAPE, "sagen_binauralize_sources: mode=%d", mode);
+int run_binauralize_sources(const float* signals, int64_t ld, const double* ctrl, const SourceSet& ss, int mode, const double* dirs,
+                            const float* hrir, int n_dirs, int ntaps, int64_t zero_before, int64_t t0, int64_t n, float* y, void*) {
     const bool h = mode == SAGEN_SOURCES_HRIR;
-    if (h && (!dirs || !hrir)) return fail(SAGEN_ERR_NULL, "sagen_binauralize_sources: the hrir mode needs dirs and hrir");
-    if (n < 1 || ld < 1 || (h && (n_dirs < 1 || ntaps < 1))) return fail(SAGEN_ERR_SHAPE, "sagen_binauralize_sources: bad sizes");
-    if (h && (n_dirs > sagen::SRC_MAX_DIRS || ntaps > sagen::SRC_MAX_TAPS))
-        return fail(SAGEN_ERR_UNSUPPORTED, "sagen_binauralize_sources: n_dirs=%d ntaps=%d", n_dirs, ntaps);
-    sagen::SourceSet ss;
-    const int rc = src_fill("sagen_binauralize_sources", ss, ctrl, pt_off, nframes, duration, n_sources, rate, t0, t0 + n - 1);
-    if (rc != SAGEN_OK) return rc;
-    for (int s = 0; s < n_sources; ++s)
-        if (ld < nframes[s]) return fail(SAGEN_ERR_SHAPE, "sagen_binauralize_sources: ld=%ld is shorter than a source's nframes", (long)ld);
+    const int n_sources = ss.n_sources;
+    const double rate = ss.rate;
+    const long long* nframes = ss.nframes;
     for (int64_t i = 0; i < n; ++i) {
         const int64_t t = t0 + i;
         double acc[2] = {0., 0.};
@@ -615,7 +567,6 @@ int sagen_binauralize_sources(const float* signals, int64_t ld, const double* ct
 
 /* Reprojection of 360-degree frames (include/sagen.h: sagen_reproject; scraping/utils.py:91-144, preprocess.py:51-52, vrProjector's
  * CubemapProjection.py:68-121): a loop per frame and destination pixel over the fp64 core the device uses (csrc/project_core.h) */
-extern "C++" {
 namespace {
 template <int SK, int DK>
 void reproject_frames(const uint8_t* src, uint8_t* dst, const double* rot, const sagen::ProjArgs& a) {
@@ -640,19 +591,8 @@ void reproject_dst(const uint8_t* src, uint8_t* dst, const double* rot, const sa
     }
 }
 }  // namespace
-}  // extern "C++"
 
-size_t sagen_reproject_scratch_bytes(int, int, int, int) { return 0; }
-
-int sagen_reproject(const uint8_t* src, int n, int src_h, int src_w, const sagen_projection* src_proj, uint8_t* dst, int dst_h, int dst_w,
-                    const sagen_projection* dst_proj, const double* rot, int n_rot, int supersample, void*, size_t, void*) {
-    if (n < 0 || src_h <= 0 || src_w <= 0 || dst_h <= 0 || dst_w <= 0) return fail(SAGEN_ERR_SHAPE, "sagen_reproject: bad sizes");
-    if (n == 0) return SAGEN_OK;
-    if (!src || !dst || !src_proj || !dst_proj || (n_rot != 0 && !rot)) return fail(SAGEN_ERR_NULL, "sagen_reproject: null argument");
-    sagen::ProjArgs a;
-    const char* why;
-    const int rc = sagen::proj_args_fill(a, n, src_h, src_w, src_proj, dst_h, dst_w, dst_proj, n_rot, supersample, &why);
-    if (rc != SAGEN_OK) return fail(rc, "sagen_reproject: %s", why);
+int run_reproject(const uint8_t* src, uint8_t* dst, const double* rot, const ProjArgs& a, void*) {
     switch (a.src.kind) {
         case SAGEN_PROJ_ER: reproject_dst<SAGEN_PROJ_ER>(src, dst, rot, a); break;
         case SAGEN_PROJ_CUBE: reproject_dst<SAGEN_PROJ_CUBE>(src, dst, rot, a); break;
@@ -664,7 +604,6 @@ int sagen_reproject(const uint8_t* src, int n, int src_h, int src_w, const sagen
 /* Dense optical flow and its byte coding (include/sagen.h: sagen_optical_flow, sagen_flow_encode): plain loops per pair over the fp64
  * core the device uses (csrc/flow_core.h).  Every Jacobi sweep covers the whole level: `fuse` is checked and otherwise ignored, which
  * is what "the result does not depend on it" means on this side. */
-extern "C++" {
 namespace {
 void flow_pair(const double* p1, const double* p2, const sagen::FlowArgs& a, float* out, double* s1, double* s2, sagen::FlowUV* cur,
                sagen::FlowUV* oth, sagen::FlowUV* f0, sagen::FlowCoef* coef) {
@@ -712,26 +651,9 @@ void flow_pair(const double* p1, const double* p2, const sagen::FlowArgs& a, flo
     }
 }
 }  // namespace
-}  // extern "C++"
 
-size_t sagen_optical_flow_scratch_bytes(int n_frames, int h, int w, int levels) {
-    const char* why;
-    if (n_frames <= 1 || sagen::flow_check_sizes(n_frames, h, w, levels, &why) != SAGEN_OK) return 0;
-    return sagen::flow_scratch_doubles(n_frames, h, w, levels) * sizeof(double);
-}
-
-int sagen_optical_flow(const uint8_t* frames, int n_frames, int h, int w, const sagen_flow_params* p, float* flow, void* scratch,
-                       size_t scratch_bytes, void*) {
-    using namespace sagen;
-    if (n_frames < 0) return fail(SAGEN_ERR_SHAPE, "sagen_optical_flow: n_frames=%d", n_frames);
-    if (n_frames <= 1) return SAGEN_OK;
-    if (!frames || !p || !flow || !scratch) return fail(SAGEN_ERR_NULL, "sagen_optical_flow: null argument");
-    FlowArgs a;
-    const char* why;
-    const int rc = flow_args_fill(a, n_frames, h, w, p, &why);
-    if (rc != SAGEN_OK) return fail(rc, "sagen_optical_flow: %s", why);
-    if (scratch_bytes < flow_scratch_doubles(n_frames, h, w, a.levels) * sizeof(double)) return fail(SAGEN_ERR_SHAPE, "sagen_optical_flow: scratch_bytes too small");
-    if (((uintptr_t)scratch) % 8) return fail(SAGEN_ERR_SHAPE, "sagen_optical_flow: scratch must be 8-byte aligned");
+int run_optical_flow(const uint8_t* frames, const FlowArgs& a, float* flow, void* scratch, void*) {
+    const int n_frames = a.n_frames, h = a.h, w = a.w;
     // the device's layout: three (u, v) fields and the coefficients per pair, the pyramids, the smoothed level (two frames used here)
     const size_t hw = (size_t)h * w, pyr = flow_level_pixels(h, w, a.levels);
     FlowUV* cur = (FlowUV*)scratch;
@@ -757,17 +679,7 @@ int sagen_optical_flow(const uint8_t* frames, int n_frames, int h, int w, const 
     return SAGEN_OK;
 }
 
-size_t sagen_flow_encode_scratch_bytes(int n, int, int) { return n > 0 ? (size_t)n * sagen::FLOW_ENC_PARTS * 2 * sizeof(float) : 0; }
-
-int sagen_flow_encode(const float* flow, int n, int h, int w, uint8_t* rgb, float* limits, void* scratch, size_t scratch_bytes, void*) {
-    using namespace sagen;
-    if (n < 0) return fail(SAGEN_ERR_SHAPE, "sagen_flow_encode: n is negative");
-    if (n == 0) return SAGEN_OK;
-    const char* why;
-    const int rc = flow_encode_check(n, h, w, &why);
-    if (rc != SAGEN_OK) return fail(rc, "sagen_flow_encode: %s", why);
-    if (!flow || !rgb || !limits || !scratch) return fail(SAGEN_ERR_NULL, "sagen_flow_encode: null argument");
-    if (scratch_bytes < sagen_flow_encode_scratch_bytes(n, h, w)) return fail(SAGEN_ERR_SHAPE, "sagen_flow_encode: scratch_bytes too small");
+int run_flow_encode(const float* flow, int n, int h, int w, uint8_t* rgb, float* limits, void*, void*) {
     const size_t hw = (size_t)h * w;
     for (int f = 0; f < n; ++f) {
         const float* p = flow + (size_t)f * hw * 2;
@@ -787,16 +699,8 @@ int sagen_flow_encode(const float* flow, int n, int h, int w, uint8_t* rgb, floa
 /* Polyphase FIR resampling and windowed RMS (include/sagen.h: sagen_resample_fir, sagen_window_rms; pyutils/iolib/audio.py:23,
  * scraping/preprocess.py:14-34 and :146-153, pyutils/ambisonics/common.py:34-59): plain loops per output over the fp64 core the
  * device uses (csrc/resample_core.h).  The rows an output reaches are mixed into a small buffer, zeros where the x buffer has none. */
-int sagen_resample_fir(const float* x, int64_t x0, int64_t n_in, int c_in, const double* taps, int L, int M, int H, int T, const double* mix,
-                       int c_out, int64_t n0, int64_t n, float* y, void*) {
-    using namespace sagen;
-    if (n < 0) return fail(SAGEN_ERR_SHAPE, "sagen_resample_fir: n is negative");
-    if (n == 0) return SAGEN_OK;
-    if (!taps || !y || (!x && n_in != 0)) return fail(SAGEN_ERR_NULL, "sagen_resample_fir: null argument");
-    ResampleArgs a;
-    const char* why;
-    const int rc = resample_args_fill(a, x0, n_in, c_in, L, M, H, T, mix != nullptr, c_out, n0, n, &why);
-    if (rc != SAGEN_OK) return fail(rc, "sagen_resample_fir: %s", why);
+int run_resample_fir(const float* x, const double* taps, const double* mix, float* y, const ResampleArgs& a, const char**, void*) {
+    const int c_in = a.c_in, c_out = a.c_out, L = a.L, M = a.M, H = a.H, T = a.T;
     std::vector<double> z((size_t)T * c_out);
     for (long long j = 0; j < a.n; ++j) {
         const long long nn = a.n0 + j, m0 = rs_first_row(nn, L, M, H);
@@ -810,15 +714,8 @@ int sagen_resample_fir(const float* x, int64_t x0, int64_t n_in, int c_in, const
     return SAGEN_OK;
 }
 
-int sagen_window_rms(const float* x, int64_t n, int channels, int channel, int64_t first, int64_t hop, int64_t length, int64_t count,
-                     double* rms, void*) {
-    using namespace sagen;
-    if (count < 0) return fail(SAGEN_ERR_SHAPE, "sagen_window_rms: count is negative");
-    if (count == 0) return SAGEN_OK;
-    if (!x || !rms) return fail(SAGEN_ERR_NULL, "sagen_window_rms: null argument");
-    const char* why;
-    const int rc = window_rms_check(n, channels, channel, first, hop, length, count, &why);
-    if (rc != SAGEN_OK) return fail(rc, "sagen_window_rms: %s", why);
+int run_window_rms(const float* x, int channels, int channel, int64_t first, int64_t hop, int64_t length, int64_t count, double* rms,
+                   void*) {
     for (long long i = 0; i < count; ++i) {
         double p[RMS_LANES];
         for (int l = 0; l < RMS_LANES; ++l) p[l] = rms_partial(x, first + i * hop, channels, channel, length, l);
@@ -829,52 +726,20 @@ int sagen_window_rms(const float* x, int64_t n, int channels, int channel, int64
 
 /* Baseline JPEG decode (include/sagen.h: sagen_jpeg_decode; PIL / libjpeg behind feeder.py:18-23 in the reference): the five stages
  * of csrc/jpeg.hip as plain loops over the integer core the device uses (csrc/jpeg_core.h: jpeg_decode_host) */
-size_t sagen_jpeg_decode_scratch_bytes(int n, int w, int h, int components, int hs, int vs, int n_hufftabs) {
-    sagen::JpegGeom g;
-    const char* why;
-    if (n <= 0 || n_hufftabs < 1 || n_hufftabs > 65536 || sagen::jpeg_geom_fill(g, n, w, h, components, hs, vs, &why) != SAGEN_OK) return 0;
-    return sagen::jpeg_scratch_layout(g, n_hufftabs).total;
-}
-
-int sagen_jpeg_decode(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_frame* frames, int n, const int32_t* segments,
-                      int n_segments, const uint16_t* qtabs, int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, int w, int h,
-                      int components, int hs, int vs, uint8_t* out, int32_t* status, void* scratch, size_t scratch_bytes, void*) {
-    if (n == 0) return SAGEN_OK;
-    sagen::JpegGeom g;
-    const char* why;
-    const int rc = sagen::jpeg_args_check(g, bytes, total_bytes, frames, n, segments, n_segments, qtabs, n_qtabs, hufftabs, n_hufftabs, w, h,
-                                          components, hs, vs, out, status, scratch, scratch_bytes, &why);
-    if (rc != SAGEN_OK) return fail(rc, "sagen_jpeg_decode: %s", why);
-    sagen::jpeg_decode_host(bytes, total_bytes, frames, segments, n_segments, qtabs, n_qtabs, hufftabs, n_hufftabs, g, out, status, scratch);
+int run_jpeg_decode(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_frame* frames, const int32_t* segments, int n_segments,
+                    const uint16_t* qtabs, int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, const JpegGeom& g, uint8_t* out,
+                    int32_t* status, void* scratch, void*) {
+    jpeg_decode_host(bytes, total_bytes, frames, segments, n_segments, qtabs, n_qtabs, hufftabs, n_hufftabs, g, out, status, scratch);
     return SAGEN_OK;
 }
 
 /* Baseline JPEG encode (include/sagen.h: sagen_jpeg_encode; ffmpeg's "%06d.jpg" behind scraping/preprocess.py:183-196 in the
  * reference, PIL / libjpeg behind the frame writers here): frame by frame, block by block, bit by bit over the integer core the device
- * uses (csrc/jpeg_enc_core.h: jpeg_encode_host).  The scratch is checked as the device library checks it, and not used. */
-size_t sagen_jpeg_encode_scratch_bytes(int n, int w, int h, int components, int hs, int vs, int64_t stride) {
-    sagen::JpegEncGeom g;
-    const char* why;
-    if (n <= 0 || sagen::jpeg_enc_geom_fill(g, n, w, h, components, hs, vs, stride, &why) != SAGEN_OK) return 0;
-    return sagen::jpeg_enc_scratch_layout(g).total;
-}
-
-int64_t sagen_jpeg_encode_max_bytes(int w, int h, int components, int hs, int vs) {
-    sagen::JpegEncGeom g;
-    const char* why;
-    if (sagen::jpeg_enc_geom_fill(g, 1, w, h, components, hs, vs, 4, &why) != SAGEN_OK) return 0;
-    return sagen::jpeg_enc_max_bytes(g.blocks);
-}
-
-int sagen_jpeg_encode(const uint8_t* frames, int n, int w, int h, int components, int hs, int vs, const uint16_t* qtabs, uint8_t* out,
-                      int64_t stride, int32_t* sizes, int32_t* status, void* scratch, size_t scratch_bytes, void*) {
-    if (n == 0) return SAGEN_OK;
-    sagen::JpegEncGeom g;
-    const char* why;
-    const int rc = sagen::jpeg_enc_args_check(g, frames, n, w, h, components, hs, vs, qtabs, out, stride, sizes, status, scratch, scratch_bytes, &why);
-    if (rc != SAGEN_OK) return fail(rc, "sagen_jpeg_encode: %s", why);
-    sagen::jpeg_encode_host(frames, g, qtabs, out, sizes, status);
+ * uses (csrc/jpeg_enc_core.h: jpeg_encode_host).  The scratch is not used. */
+int run_jpeg_encode(const uint8_t* frames, const JpegEncGeom& g, const uint16_t* qtabs, uint8_t* out, int32_t* sizes, int32_t* status, void*,
+                    void*) {
+    jpeg_encode_host(frames, g, qtabs, out, sizes, status);
     return SAGEN_OK;
 }
 
-}  // extern "C"
+}  // namespace sagen

@@ -39,20 +39,29 @@ def test_the_twin_exports_the_overlay_entries(twin):
     x = (C.c_float * 32)(*([3., 0, 0, 0, 9, 9, 9, 9] * 2 + [4., 0, 0, 0, 9, 9, 9, 9] * 2))
     sh = (C.c_float * 8)(1., 0, 0, 0, 0.5, 0, 0, 0)
     rms = (C.c_float * 4)()
-    assert l.sagen_power_map_windows(x, 8, 4, 2, 2, sh, 2, rms, None, 0, None) == 0
-    assert list(rms) == [3., 1.5, 4., 2.]
-    assert l.sagen_power_map_windows(None, 8, 4, 2, 2, sh, 2, rms, None, 0, None) == -1
-    assert l.sagen_power_map_windows(x, 8, 5, 2, 2, sh, 2, rms, None, 0, None) == -3
-    assert l.sagen_power_map_windows(x, 8, 4, 0, 2, sh, 2, rms, None, 0, None) == -2
-    assert l.sagen_power_map_windows(None, 2, 4, 2, 2, None, 2, None, None, 0, None) == 0          # no map fits: nothing is looked at
+    # the twin checks the scratch as the device library does (the entry points are shared: csrc/op_entries.h) and does not use it
     assert l.sagen_power_map_windows_scratch_bytes(2, 4) == 2 * 10 * 8
+    scratch = (C.c_double * 20)()
+    assert l.sagen_power_map_windows(x, 8, 4, 2, 2, sh, 2, rms, scratch, 160, None) == 0
+    assert list(rms) == [3., 1.5, 4., 2.]
+    assert l.sagen_power_map_windows(x, 8, 4, 2, 2, sh, 2, rms, scratch, 159, None) == -5
+    assert l.sagen_power_map_windows(None, 8, 4, 2, 2, sh, 2, rms, scratch, 160, None) == -1
+    assert l.sagen_power_map_windows(x, 8, 5, 2, 2, sh, 2, rms, scratch, 160, None) == -3
+    assert l.sagen_power_map_windows(x, 8, 4, 0, 2, sh, 2, rms, scratch, 160, None) == -2
+    assert l.sagen_power_map_windows(None, 2, 4, 2, 2, None, 2, None, None, 0, None) == 0          # no map fits: nothing is looked at
     # two flat maps: v = 0, alpha = 0 - the frames come back; a frame without its `cur` map is refused
     maps = (C.c_float * 4)(1., 1., 2., 2.)
     lut = (C.c_double * 768)(*([0.5] * 768))
     frames = (C.c_uint8 * 18)(*range(10, 28))
     out = (C.c_uint8 * 18)()
-    assert l.sagen_overlay_blend(maps, 2, 0, 1, 2, lut, frames, 3, 0, 1, 2, 5, out, None, 0, None) == 0
+    # the device library's number (csrc/host_sizes.h): the grid of per-node (r, g, b, v) doubles rounded up to 256 bytes, then 4 doubles of clip bounds per frame
+    need = (3 * 1 * 2 * 4 * 8 + 255) // 256 * 256 + 3 * 4 * 8
+    assert l.sagen_overlay_blend_scratch_bytes(2, 1, 2, 3) == need
+    blend_scratch = (C.c_double * (need // 8 + 2))()
+    sp = (C.addressof(blend_scratch) + 15) // 16 * 16
+    assert l.sagen_overlay_blend(maps, 2, 0, 1, 2, lut, frames, 3, 0, 1, 2, 5, out, sp, need, None) == 0
     assert list(out) == list(frames)
-    assert l.sagen_overlay_blend(maps, 2, 0, 1, 2, lut, frames, 3, 3, 1, 2, 5, out, None, 0, None) == -2
-    assert l.sagen_overlay_blend(maps, 2, 0, 1, 2, None, frames, 3, 0, 1, 2, 5, out, None, 0, None) == -1
+    assert l.sagen_overlay_blend(maps, 2, 0, 1, 2, lut, frames, 3, 0, 1, 2, 5, out, sp, need - 1, None) == -5
+    assert l.sagen_overlay_blend(maps, 2, 0, 1, 2, lut, frames, 3, 3, 1, 2, 5, out, sp, need, None) == -2
+    assert l.sagen_overlay_blend(maps, 2, 0, 1, 2, None, frames, 3, 0, 1, 2, 5, out, sp, need, None) == -1
     assert l.sagen_overlay_blend(maps, 2, 0, 1, 2, lut, frames, 0, 99, 1, 2, 5, out, None, 0, None) == 0
