@@ -614,6 +614,31 @@ int64_t sagen_jpeg_encode_max_bytes(int w, int h, int components, int hs, int vs
 int sagen_jpeg_encode(const uint8_t* frames, int n, int w, int h, int components, int hs, int vs, const uint16_t* qtabs, uint8_t* out,
                       int64_t stride, int32_t* sizes, int32_t* status, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- frame batches from a resident clip -------------------------------------------------------------------------------------
+ * The reference's reader threads pick the frame of every window, roll it by the yaw rotation, un-code the flow bytes and stack the
+ * batch on the host (feeder.py:106-161), and the batch crosses the bus.  sagen_assemble_frames is that step over frames that already
+ * lie on the device (what sagen_jpeg_decode wrote): one launch builds the frames of n_out batch items.
+ *   frames   [n_frames][h][w][3] uint8 DEVICE; may be null when n_frames == 0
+ *   index    [n_out] int32 DEVICE: the frame of item i.  A value outside [0, n_frames) makes item i PADDING: every element of it is
+ *            written as zero (bytes in mode 0, 0.0f otherwise) and no frame is read
+ *   shift    [n_out] int32 DEVICE: output column x of item i is source column (x - shift[i]) mod w, the mathematical modulo, any
+ *            int32: numpy's roll(frame, shift[i], axis=1)
+ *   out      [n_out][h][w][3] DEVICE, by mode:
+ *     0  uint8: the bytes
+ *     1  fp32: table[byte], table [256] fp32 DEVICE (e.g. byte / 255 - 0.5 as the host computes it)
+ *     2  fp32, the flow folder's un-coding (feeder.py:147-160): table [512] fp32 = cos[256] then sin[256] of the angle a byte
+ *        stands for, scale_lo [n_frames][2] fp64 DEVICE = ((hi - lo) / 255, lo) of each frame's row of flow_limits.npy.  For the
+ *        source bytes (b0, b1, b2) of frame f:  m = (float)((double)b2 * scale_lo[f][0]);  m = (float)((double)m + scale_lo[f][1]);
+ *        out = (m * cos[b0], m * sin[b0], m), the products in fp32.  b1 is not used.
+ * The kernel is a total function of its arrays - no content of index or shift moves an address out of bounds -, so there is no
+ * status word, and the entry point reads no device memory.
+ * Returns: n_out == 0 SAGEN_OK, nothing touched; SAGEN_ERR_SHAPE for n_out or n_frames < 0, h or w < 1, a mode outside 0..2, a float
+ * out or table not 4-byte aligned, scale_lo not 8-byte aligned, index or shift not 4-byte aligned; SAGEN_ERR_UNSUPPORTED for h or w
+ * above 16384; SAGEN_ERR_NULL for a null index, shift or out, null frames with n_frames > 0, a null table in modes 1 and 2, a null
+ * scale_lo in mode 2 with n_frames > 0.  A refused call writes nothing. */
+int sagen_assemble_frames(const uint8_t* frames, int n_frames, int h, int w, const int32_t* index, const int32_t* shift, int n_out, int mode,
+                          const float* table, const double* scale_lo, void* out, void* stream);
+
 /* ---- moving point sources: encode to ambisonics, binauralise, track ------------------------------------------------------
  * The front end of the reference's ambisonics toolbox: AmbiEncoder.encode / encode_frame / encode_v2 (pyutils/ambisonics/
  * encoder.py:10-55), SourceBinauralizer over VirtualStereoMic and Convolvotron, static and per frame (binauralizer.py:12-121), and

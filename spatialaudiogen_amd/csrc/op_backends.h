@@ -43,5 +43,7 @@ int run_jpeg_decode(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_
                     int32_t* status, void* scratch, void* stream);
 int run_jpeg_encode(const uint8_t* frames, const JpegEncGeom& g, const uint16_t* qtabs, uint8_t* out, int32_t* sizes, int32_t* status,
                     void* scratch, void* stream);
+int run_assemble_frames(const uint8_t* frames, int n_frames, int h, int w, const int32_t* index, const int32_t* shift, int n_out, int mode,
+                        const float* table, const double* scale_lo, void* out, void* stream);
 
 }  // namespace sagen

@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../csrc/op_entries.h"
+#include "../csrc/op_entries_feed.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -739,6 +740,37 @@ int run_jpeg_decode(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_
 int run_jpeg_encode(const uint8_t* frames, const JpegEncGeom& g, const uint16_t* qtabs, uint8_t* out, int32_t* sizes, int32_t* status, void*,
                     void*) {
     jpeg_encode_host(frames, g, qtabs, out, sizes, status);
+    return SAGEN_OK;
+}
+
+/* Frame batches from a resident clip (include/sagen.h: sagen_assemble_frames; the stacking, rolling and flow un-coding of
+ * feeder.py:106-161 in the reference): item by item, pixel by pixel over the core the device uses (csrc/feed_core.h). */
+int run_assemble_frames(const uint8_t* frames, int n_frames, int h, int w, const int32_t* index, const int32_t* shift, int n_out, int mode,
+                        const float* table, const double* scale_lo, void* out, void*) {
+    const size_t hw = (size_t)h * w;
+    for (int i = 0; i < n_out; ++i) {
+        uint8_t* ob = (uint8_t*)out + (size_t)i * hw * 3;
+        float* of = (float*)out + (size_t)i * hw * 3;
+        const int f = index[i];
+        if (f < 0 || f >= n_frames) {
+            if (mode == FEED_BYTES) memset(ob, 0, hw * 3);
+            else for (size_t k = 0; k < hw * 3; ++k) of[k] = 0.f;
+            continue;
+        }
+        const int s = feed_roll(shift[i], w);
+        for (int y = 0; y < h; ++y)
+            for (int x = 0; x < w; ++x) {
+                const uint8_t* p = frames + ((size_t)f * hw + (size_t)y * w + feed_src_x(x, s, w)) * 3;
+                const size_t o = ((size_t)y * w + x) * 3;
+                if (mode == FEED_BYTES) {
+                    ob[o] = p[0]; ob[o + 1] = p[1]; ob[o + 2] = p[2];
+                } else if (mode == FEED_TABLE) {
+                    of[o] = table[p[0]]; of[o + 1] = table[p[1]]; of[o + 2] = table[p[2]];
+                } else {
+                    feed_flow_pixel(p[0], p[2], table, table + 256, scale_lo[2 * (size_t)f], scale_lo[2 * (size_t)f + 1], of + o);
+                }
+            }
+    }
     return SAGEN_OK;
 }
 

@@ -6,7 +6,9 @@
 Host-side only: window arithmetic, batching in groups of 10 with zero-padded last group
 (deploy.py:112-139 — the padding is part of the result because batch-norm runs on batch statistics),
 H2D staging and the final [mono | prediction] assembly.  All tensor arithmetic runs in
-libsagen_hip.so through SptAudioGen.inference_ops.
+libsagen_hip.so through SptAudioGen.inference_ops.  With decode='device' (--decode device) the frames
+do not pass through the host either: feeder.DeviceFrames decodes the files on the device and builds
+every batch there; only the files' bytes and the audio are staged.
 """
 import os
 import numpy as np
@@ -146,7 +148,15 @@ class W2XYZ(object):
     # per sess.run); batches that do not fill a group (the clip's tail, a zero-padded partial batch) run one at a time
     groups = 1
 
-    def __init__(self, model_dir=None, params=None, variables=None, device=None):
+    # where the frames of a clip FOLDER are decoded and batched: 'host' (PIL in the reader, numpy batches, one H2D copy per batch) or
+    # 'device' (feeder.DeviceFrames: the files' bytes go up once, jpeg.py decodes, sagen_assemble_frames builds every batch there).
+    # The model sees the same bits either way; a ClipArrays source holds decoded arrays already and ignores this
+    decode = 'host'
+
+    def __init__(self, model_dir=None, params=None, variables=None, device=None, decode='host'):
+        if decode not in ('host', 'device'):
+            raise ValueError("decode must be 'host' or 'device', not %r" % (decode,))
+        self.decode = decode
         if params is None:
             params = load_params(model_dir)
         self.params = params
@@ -178,7 +188,8 @@ class W2XYZ(object):
             raise IOError('no checkpoint (or variables.npz) found in %s' % model_dir)
         return load_checkpoint(prefix)
 
-    def _reader(self, source, deploy_start, deploy_duration):
+    def _reader(self, source, deploy_start, deploy_duration, frames=True):
+        """frames=False: the reader serves the audio only (the frames come from feeder.DeviceFrames)."""
         p = self.params
         if isinstance(source, ClipArrays):
             return source.windowed(deploy_start, deploy_duration)
@@ -186,8 +197,8 @@ class W2XYZ(object):
         # img_prep=None: frames stay the uint8 the JPEG decoder produced; x/255 - 0.5 (myutils.py:88-89) runs on the device
         # (sagen_forward_u8), bit-identical to img_prep_fcn() + float32 cast, at a quarter of the H2D bytes
         return SampleReader(source, ambi_order=p.ambi_order, audio_rate=p.audio_rate, video_rate=p.video_rate,
-                            context=p.context, duration=self.duration, return_video=VIDEO in p.encoders,
-                            img_prep=None, return_flow=FLOW in p.encoders, start_time=deploy_start,
+                            context=p.context, duration=self.duration, return_video=frames and VIDEO in p.encoders,
+                            img_prep=None, return_flow=frames and FLOW in p.encoders, start_time=deploy_start,
                             sample_duration=deploy_duration, skip_silence_thr=None, shuffle=False,
                             random_rotations=False, skip_rate=None)                   # deploy.py:91-105
 
@@ -241,14 +252,27 @@ class W2XYZ(object):
         from . import ops
         from .feeder import BatchPrefetcher, frames_to_float
         p, m = self.params, self.model
-        reader = self._reader(input_folder, deploy_start, deploy_duration)
+        on_device = self.decode == 'device' and not isinstance(input_folder, ClipArrays)
+        reader = self._reader(input_folder, deploy_start, deploy_duration, frames=not on_device)
         if not reader.chunks_t:
             empty = np.zeros((0, 4), np.float32), np.zeros((0, renderer.outputs if renderer else 0), np.float32)
             return empty if overlay is None else empty + (np.zeros((0, 0, 0, 3), np.uint8),)
         dt = reader.chunks_t[0] - deploy_start                           # deploy.py:106-107
         reader.chunks_t = [t - dt for t in reader.chunks_t]
         use_v, use_f = VIDEO in p.encoders, FLOW in p.encoders
-        frame_of = self._overlay_frames(input_folder, reader) if overlay is not None else None
+        frame_of = self._overlay_frames(input_folder, reader) if overlay is not None and not on_device else None
+        vdev = fdev = None
+        if on_device:       # the frames the window table references, and only those, decoded once and kept on the device
+            from .feeder import DeviceFrames
+            if self.video_size != 1:
+                raise ValueError("decode='device' needs one frame per window (duration %g s x video_rate %g != 1)" % (self.duration, p.video_rate))
+            wanted = [frame_index(t, p.video_rate) for t in reader.chunks_t]
+            if use_v or overlay is not None:
+                vdev = DeviceFrames(os.path.join(input_folder, 'video'), 'video', device=m.device, rate=p.video_rate)
+                vdev.ensure(min(wanted), max(wanted) + 1)
+            if use_f:
+                fdev = DeviceFrames(os.path.join(input_folder, 'flow'), 'flow', device=m.device, rate=p.video_rate)
+                fdev.ensure(min(wanted), max(wanted) + 1)
 
         def batches():                                                   # deploy.py:112-139
             while True:
@@ -257,6 +281,8 @@ class W2XYZ(object):
                     chunk = reader.get()
                     if chunk is None:
                         break
+                    if on_device:                                        # the frame SampleReader.sample_at would decode
+                        chunk['index'] = frame_index(reader.chunks_t[reader.head], p.video_rate)
                     if frame_of is not None:
                         chunk['frame'] = frame_of(reader.chunks_t[reader.head])
                     batch.append(chunk)
@@ -269,8 +295,10 @@ class W2XYZ(object):
                 out['audio'] = audio
                 if frame_of is not None:
                     out['frames'] = np.stack([b['frame'] for b in batch], 0)
+                if on_device:
+                    out['index'] = [b['index'] for b in batch]               # (a list: indices instead of arrays, nothing to pin)
                 for key, on in (('video', use_v), ('flow', use_f)):
-                    if on:
+                    if on and not on_device:
                         clip = np.stack([b[key] for b in batch], 0)
                         if clip.dtype == np.uint8 and n == self.batch_size:
                             out[key] = clip                                   # decoded frames as they are (sagen_forward_u8)
@@ -288,8 +316,18 @@ class W2XYZ(object):
         def run(net, bs):               # one forward call over the batches `bs` (len(bs) == net.groups), results appended in order
             cat = lambda k: torch.cat([torch.as_tensor(b[k]) for b in bs], 0).to(m.device, non_blocking=True) if k in bs[0] else None
             a_dev = cat('audio')
+            if on_device:               # the rules of batches(): full batches give uint8 video, a partial one float frames padded with 0.0
+                idx = [i for b in bs for i in b['index']]
+                full = all(b['n'] == self.batch_size for b in bs)
+                if not full and len(bs) != 1:
+                    raise RuntimeError('a partial batch in a group of %d' % len(bs))
+                pad = None if full else self.batch_size
+                v_dev = vdev.batch(idx, pad_to=pad, as_float=not full) if use_v else None
+                f_dev = fdev.batch(idx, pad_to=pad) if use_f else None
+            else:
+                v_dev, f_dev = cat('video'), cat('flow')
             # deploy.py:141 - with the fp16x2 guard: a batch whose trunk planes clamped anything is re-run on bf16 planes
-            pred = net.inference_ops_checked(a_dev, cat('video'), cat('flow'), on_saturation=self.on_saturation)
+            pred = net.inference_ops_checked(a_dev, v_dev, f_dev, on_saturation=self.on_saturation)
             wyzx = ops.assemble_wyzx(a_dev[:, :, 0].contiguous(), pred, m.snd_contx)   # deploy.py:143-152
             rows = [wyzx[i * self.batch_size:i * self.batch_size + b['n']].reshape(b['n'] * m.snd_dur, 4) for i, b in enumerate(bs)]
             if renderer is not None:    # one call for everything this forward produced, in stream order, only the valid windows of a partial batch
@@ -297,7 +335,10 @@ class W2XYZ(object):
                 rendered.append(renderer.process(valid).cpu().numpy())
             if overlay is not None:     # the same rows, and the frames of exactly these windows
                 valid = rows[0] if len(rows) == 1 else torch.cat(rows, 0)
-                frames = torch.cat([torch.as_tensor(b['frames']) for b in bs], 0).to(m.device, non_blocking=True)
+                if on_device:
+                    frames = vdev.batch(idx)[:, 0]
+                else:
+                    frames = torch.cat([torch.as_tensor(b['frames']) for b in bs], 0).to(m.device, non_blocking=True)
                 painted.append(overlay.process(valid, frames).cpu().numpy())
             for r in rows:
                 outs.append(r.cpu().numpy())
@@ -338,7 +379,7 @@ def parse_arguments(argv=None):
     """deploy.py:14-38 (the ffmpeg muxing of the 360 video is outside this path; the ambisonic wav is written, and --render adds the
     audio the reference's --save_video path ends in, rendered on the device: render.py)."""
     import argparse
-    parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter, conflict_handler='resolve')
     parser.add_argument('model_dir', help='Directory containing model snapshot.')
     parser.add_argument('input_folder', default='', help='Folder with input sample.')
     parser.add_argument('--deploy_start', default=0., type=float)
@@ -350,6 +391,18 @@ def parse_arguments(argv=None):
                              'its own batch-norm statistics; output bit-identical to 1)')
     from .render import add_render_arguments
     add_render_arguments(parser)
+
+    class Decode(argparse.Action):
+        """This command decodes two things, and --decode names both, as it does in render (the ambisonic decoder) and in project / flow /
+        overlay (where the frames are decoded): the value says which one is meant, and the flag may be given once for each."""
+
+        def __call__(self, parser, namespace, value, option_string=None):
+            setattr(namespace, 'frame_decode' if value in ('host', 'device') else 'decode', value)
+    parser.add_argument('--decode', action=Decode, choices=('host', 'device', 'projection', 'pseudoinv'), default=None,
+                        help="host | device: where the clip's frames are decoded and batched (default host: PIL in the reader threads; device: "
+                             "the files' bytes go to the device, jpeg.py decodes and every batch is assembled there; same output, bit for bit).  "
+                             'projection | pseudoinv: the decoder of --render ears (default pseudoinv) / speakers (default projection)')
+    parser.set_defaults(frame_decode='host')
     parser.add_argument('--render_fn', default=None, help='Output wav of --render.')
     parser.add_argument('--overlay_dir', default=None, metavar='DIR',
                         help='paint the sound-direction heat map over the frames of <input_folder>/video and write them here as %%06d.png (overlay.py)')
@@ -380,7 +433,7 @@ def main(argv=None):
         overlay.prepare_output_dir(args.overlay_dir, args.overwrite, 'deploy')
     torch.cuda.set_device(args.gpu)
     renderer = render.Renderer(*rendering) if rendering else None
-    model = W2XYZ(args.model_dir)
+    model = W2XYZ(args.model_dir, decode=args.frame_decode)
     model.groups = max(1, args.groups)
     painted = None
     if args.overlay_dir:

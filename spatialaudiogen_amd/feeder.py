@@ -20,7 +20,8 @@ gets -
     frame index                         max(int(t * video_rate), 0)                    feeder.py:121
     time filters on audio_pow.lst       skip_rate, silence, start, duration, threads   feeder.py:222-238
 - the truncations differ by one sample for about a fifth of the windows, and the network sees that.
-Nothing here touches the GPU, except load_wav(..., resample=...) when it is asked to resample a file (resample.py).
+Nothing here touches the GPU, except load_wav(..., resample=...) when it is asked to resample a file (resample.py) and
+`DeviceFrames`, the device-resident counterpart of `JpgFrames` / `FlowFrames` (jpeg.py decodes, sagen_assemble_frames batches).
 """
 import collections
 import os
@@ -302,6 +303,141 @@ class FlowFrames(object):
 
 
 FlowReader = FlowFrames
+
+
+class DeviceFrames(object):
+    """The %06d.jpg frames of a folder RESIDENT ON THE DEVICE, and batches assembled from them there (include/sagen.h:
+    sagen_assemble_frames): what JpgFrames.frames (kind='video') and FlowFrames.frames (kind='flow', with the folder's
+    flow_limits.npy) return, bit for bit, without a decoded frame crossing the bus.
+
+        ensure(first, stop)     decodes the frames [first, stop) that are not resident yet (jpeg.JpegDecoder, `block` files per call)
+        batch(indices, ...)     [n, 1, H, W, 3] on the device: uint8 video as decoded, or float32 (normalised video / un-coded flow)
+
+    The resident frames are one uint8 tensor over one contiguous range of frame numbers.  Host preprocessing callables (prep,
+    flow_prep) are refused: the values are made on the device.  With SAGEN_LIB naming the CPU twin everything runs on device='cpu'."""
+
+    RAW_RATE = JpgFrames.RAW_RATE
+
+    def __init__(self, folder, kind='video', device=None, decoder=None, block=256, rate=None, prep=None, flow_prep=None):
+        import torch
+        from . import _lib
+        if kind not in ('video', 'flow'):
+            raise ValueError("kind must be 'video' or 'flow', not %r" % (kind,))
+        if prep is not None or flow_prep is not None:
+            raise ValueError('DeviceFrames makes its values on the device: a prep / flow_prep callable is a host function (use JpgFrames / FlowFrames)')
+        if int(block) < 1:
+            raise ValueError('block must be at least 1')
+        self.folder, self.kind, self.block = str(folder), kind, int(block)
+        self.rate = self.RAW_RATE if rate is None else rate
+        names = sorted(f for f in os.listdir(folder) if f.endswith('.jpg'))
+        if not names:
+            raise IOError('no jpg frames in %s' % folder)
+        self.num_frames = len(names)
+        self.duration = self.num_frames / self.RAW_RATE
+        from PIL import Image
+        with Image.open(os.path.join(self.folder, names[0])) as im:       # (the header only: nothing is decoded here)
+            self.frame_shape = (im.size[1], im.size[0], 3)
+        _lib.lib()
+        self.device = torch.device(device if device is not None else (decoder.device if decoder is not None else
+                                                                       ('cpu' if _lib.IS_CPU_TWIN else 'cuda')))
+        if decoder is None:
+            from .jpeg import JpegDecoder
+            decoder = JpegDecoder(self.device)
+        self.decoder = decoder
+        self.first = self.stop = 0                                      # the resident range
+        self._frames = torch.empty((0,) + self.frame_shape, dtype=torch.uint8, device=self.device)
+        self._scale_lo = None
+        if kind == 'flow':
+            limits = np.load(os.path.join(self.folder, 'flow_limits.npy'))
+            if limits.ndim != 2 or limits.shape[1] != 2:
+                raise ValueError('flow_limits.npy must be [frames, 2], not %s' % (limits.shape,))
+            # the operands of FlowFrames.frames, by its own expressions and in the file's dtype, then widened (exact)
+            lo, hi = limits[:, 0], limits[:, 1]
+            self.limits = limits
+            self._scale_lo = torch.as_tensor(np.stack([(hi - lo) / 255., lo], 1).astype(np.float64)).contiguous().to(self.device)
+            angle = np.arange(256).astype(np.float32)
+            angle *= (2 * np.pi) / 255.
+            table = np.concatenate([np.cos(angle), np.sin(angle)])
+        else:
+            table = frames_to_float(np.arange(256).astype(np.uint8))
+        self._table = torch.as_tensor(np.ascontiguousarray(table, dtype=np.float32)).to(self.device)
+
+    def ensure(self, first, stop):
+        """Make the frames [first, stop) resident.  The resident range stays one range: it grows to cover the request (and what lies
+        between the two, if they do not touch); frames already resident are not decoded again."""
+        import torch
+        first, stop = int(first), int(stop)
+        if not 0 <= first <= stop <= self.num_frames:
+            raise IndexError('frames %d..%d of the %d in %s' % (first, stop - 1, self.num_frames, self.folder))
+        if self.kind == 'flow' and stop > self.limits.shape[0]:
+            raise IndexError('frames %d..%d: flow_limits.npy of %s has %d rows' % (first, stop - 1, self.folder, self.limits.shape[0]))
+        if first == stop:
+            return
+        if self.first == self.stop:
+            parts, self.first, self.stop = [self._decode(first, stop)], first, stop
+        else:
+            parts = [self._frames]
+            if first < self.first:
+                parts.insert(0, self._decode(first, self.first))
+                self.first = first
+            if stop > self.stop:
+                parts.append(self._decode(self.stop, stop))
+                self.stop = stop
+        if len(parts) > 1 or parts[0] is not self._frames:
+            parts = [p for p in parts if p.shape[0]]
+            self._frames = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+
+    def _decode(self, first, stop):
+        import torch
+        names = [os.path.join(self.folder, '%06d.jpg' % i) for i in range(first, stop)]
+        parts = [self.decoder.decode(names[k:k + self.block]) for k in range(0, len(names), self.block)]
+        for p in parts:
+            if tuple(p.shape[1:]) != self.frame_shape:
+                raise ValueError('%s: a frame of %dx%d, the first one is %dx%d' % ((self.folder, p.shape[2], p.shape[1]) + self.frame_shape[1::-1]))
+        return parts[0] if len(parts) == 1 else torch.cat(parts, 0)
+
+    def shift_of(self, rotation):
+        """The roll of JpgFrames.frames, by its expression: a yaw rotation of an equirectangular frame is a horizontal roll."""
+        return -int(rotation / (2. * np.pi) * self.frame_shape[1]) if rotation else 0
+
+    def batch(self, indices, rotations=None, pad_to=None, as_float=False):
+        """The frames `indices` (resident frame numbers, any order, repeats allowed), item i rolled by rotations[i] (a sequence, one
+        number for all, or None), as [n, 1, H, W, 3] on the device.  video: uint8 as decoded, or with as_float=True the float32 of
+        frames_to_float; flow: always the float32 of FlowFrames.frames.  pad_to: the float32 forms are filled up to pad_to items
+        with items of 0.0 (a zero-padded partial batch; no uint8 value stands for 0.0 after normalisation, so uint8 has no padding).
+        One launch; an index that is not resident raises before it."""
+        import torch
+        from . import _lib
+        from .ops import _ptr, _stream
+        idx =[int(i) for i in indices]
+        n = len(idx)
+        for i in idx:
+            if not self.first <= i < self.stop:
+                raise IndexError('frame %d of %s is not resident (resident: %d..%d; ensure() decodes)' % (i, self.folder, self.first, self.stop - 1))
+        if rotations is None or isinstance(rotations, (int, float)):
+            rotations = [rotations] * n
+        if len(rotations) != n:
+            raise ValueError('%d rotations for %d frames' % (len(rotations), n))
+        as_float = bool(as_float) or self.kind == 'flow'
+        total = n if pad_to is None else int(pad_to)
+        if total < n:
+            raise ValueError('pad_to=%d is less than the %d frames asked for' % (total, n))
+        if total > n and not as_float:
+            raise ValueError('uint8 frames cannot be padded (0.0 after normalisation is no uint8 value): as_float=True')
+        h, w = self.frame_shape[:2]
+        out = torch.empty((total, 1, h, w, 3), dtype=torch.float32 if as_float else torch.uint8, device=self.device)
+        if total == 0:
+            return out
+        args = np.zeros((2, total), np.int32)
+        args[0] = -1                                                   # padding
+        args[0, :n] = np.asarray(idx, np.int64) - self.first
+        args[1, :n] = [self.shift_of(r) for r in rotations]
+        dev = torch.as_tensor(args).to(self.device)
+        mode = 2 if self.kind == 'flow' else (1 if as_float else 0)
+        _lib.check(_lib.lib().sagen_assemble_frames(_ptr(self._frames), int(self._frames.shape[0]), h, w, _ptr(dev[0]), _ptr(dev[1]), total, mode,
+                                                    _ptr(self._table), _ptr(self._scale_lo[self.first:]) if mode == 2 else None, _ptr(out),
+                                                    _stream()))
+        return out
 
 
 # ------------------------------------------------------------------------------------------------
