@@ -519,8 +519,10 @@ int bn_bwd_apply_h2_launch(const float* ga, const float* gb, const float* act, c
 // max-pool 3x3/2 SAME backward through relu(bn(y0)).  tf.nn.max_pool's gradient routes each window's gradient to its maximum;
 // here as a gather: input pixel (i, j) collects from the (at most 2x2) windows that contain it and whose pooled value equals
 // its own activation (recomputed with the forward's exact fmaf / fmaxf sequence, so the comparison is exact).  A window whose
-// maximum is 0 (all inputs <= 0) routes nowhere that survives the ReLU mask, in TF as here.  Exact float ties between two
-// positive activations of one window would be credited twice (TF: first in scan order); not observed, measure-zero.
+// maximum is 0 (all inputs <= 0) routes nowhere that survives the ReLU mask, in TF as here.  Exact float ties between
+// positive activations of one window go to the first of them in scan order, as in TF: a pixel that equals the pooled value
+// looks at the window's earlier elements before it takes the gradient.  (Ties are the rule, not the exception, on constant
+// frames: crediting every tied element gave the stem up to nine times its gradient on a black frame.)
 // -----------------------------------------------------------------------------------------
 // MODE 0 writes the gradient at z0 = bn(y0) (after the ReLU mask); MODES 1 and 2 are the two passes of the batch-norm backward of
 // the stem with that gradient RECOMPUTED on the fly (1: per-channel sums of dz and dz*xhat; 2: dy0), so dz0 - 205 MB at batch 32 -
@@ -575,8 +577,22 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float4* __restri
                 const float4 pv = pooled[q];
                 float4 gv = ga[q];
                 if (gb) gv = add4(gv, gb[q]);
-                g.x += (a.x == pv.x) ? gv.x : 0.f; g.y += (a.y == pv.y) ? gv.y : 0.f;
-                g.z += (a.z == pv.z) ? gv.z : 0.f; g.w += (a.w == pv.w) ? gv.w : 0.f;
+                // (a window whose maximum is 0 gives nothing that survives the ReLU mask below: such lanes neither match nor scan)
+                bool mx = a.x == pv.x && pv.x > 0.f, my = a.y == pv.y && pv.y > 0.f, mz = a.z == pv.z && pv.z > 0.f, mw = a.w == pv.w && pv.w > 0.f;
+                if (mx | my | mz | mw) {
+                    // the FIRST maximum of the window in scan order takes its gradient: an element of the window before (i, j) with the
+                    // same activation wins (constant frames make every interior window a nine-fold tie)
+                    const int c0 = max(2 * oj - pl, 0), c1 = min(2 * oj - pl + 2, W - 1);
+                    for (int ii = max(2 * oi - pt, 0); ii <= i; ++ii) {
+                        const int jend = ii < i ? c1 : j - 1;
+                        for (int jj = c0; jj <= jend; ++jj) {
+                            const float4 u = y0[(((long)b * H + ii) * W + jj) * C4 + c4];
+                            mx = mx && !(fmaxf(fmaf(u.x, sc.x, sh.x), 0.f) == pv.x); my = my && !(fmaxf(fmaf(u.y, sc.y, sh.y), 0.f) == pv.y);
+                            mz = mz && !(fmaxf(fmaf(u.z, sc.z, sh.z), 0.f) == pv.z); mw = mw && !(fmaxf(fmaf(u.w, sc.w, sh.w), 0.f) == pv.w);
+                        }
+                    }
+                    g.x += mx ? gv.x : 0.f; g.y += my ? gv.y : 0.f; g.z += mz ? gv.z : 0.f; g.w += mw ? gv.w : 0.f;
+                }
             }
         g.x = a.x > 0.f ? g.x : 0.f; g.y = a.y > 0.f ? g.y : 0.f; g.z = a.z > 0.f ? g.z : 0.f; g.w = a.w > 0.f ? g.w : 0.f;
         if (MODE == 0) out[idx] = g;
@@ -599,8 +615,8 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float4* __restri
 // The first pass of maxpool_bn_bwd on the POOLED grid (round 5): every window routes its gradient to its extremum, whose raw value the
 // training forward now keeps (stem8pool_kernel<raw+pool>: `praw` = max, or min where gamma < 0, of the raw stem output over the
 // window; relu(bn(praw)) IS the pooled activation) - so sum dz and sum dz * xhat are sums over the windows: 4 x 51 MB read instead of the
-// 205 MB raw tensor plus its 2x2 gathers.  (An exact float tie inside a window is credited once here and twice by the gather of the second
-// pass - both measure-zero deviations from TF's first-in-scan-order rule, ~1e-6 of the sums.)
+// 205 MB raw tensor plus its 2x2 gathers.  (An exact float tie inside a window is credited once here, and once - to its first element -
+// by the gather of the second pass.)
 __global__ __launch_bounds__(256) void pool_bn_reduce_kernel(const float4* __restrict__ praw, const BnRef bn, const float4* __restrict__ ga,
                                                              const float4* __restrict__ gb, long total, int C4, float* __restrict__ part) {
     const int C = 4 * C4;
