@@ -639,6 +639,37 @@ int sagen_jpeg_encode(const uint8_t* frames, int n, int w, int h, int components
 int sagen_assemble_frames(const uint8_t* frames, int n_frames, int h, int w, const int32_t* index, const int32_t* shift, int n_out, int mode,
                           const float* table, const double* scale_lo, void* out, void* stream);
 
+/* ---- audio windows from a resident clip -------------------------------------------------------------------------------------
+ * The reference's reader threads cut every 52799-sample window out of the 1-second wav pieces, pad it with zeros where the clip
+ * ends, rotate it about the vertical axis (feeder.py:50-103), and the batch crosses the bus; train.py:107-111 then slices the
+ * network's mono input and its target out of it.  sagen_assemble_audio is those steps over samples that already lie on the device,
+ * as the files store them: one launch builds the windows of n_out batch items and writes up to three views of them.
+ *   samples    [n_samples][channels] DEVICE, row-major, by sample_type: 0 int16, value (double)s / 32768.0; 1 fp32, widened;
+ *              2 fp64 - the values feeder.load_wav returns for PCM16 and float wavs.  May be null when n_samples == 0
+ *   lead, read_from, count   [n_out] int32 / int64 / int32 DEVICE, columns of feeder.window_table.  Window i has `size` rows; row j
+ *              is a SOURCE ROW iff 0 <= k < count[i] with k = (int64)j - lead[i], and 0 <= read_from[i] + k < n_samples - evaluated
+ *              without int64 overflow, as read_from >= -k and read_from < n_samples - k.  A source row holds source row
+ *              read_from[i] + k; every channel of any other row is 0.0f
+ *   rot        [n_out][2] fp64 (cos, sin) DEVICE, or null for no rotation; needs channels == 4 (W, Y, Z, X).  Per source row, in fp64,
+ *              not contracted, in exactly this order:  Y' = c*Y + s*X;  X' = c*X - s*Y;  W and Z unchanged - the product with
+ *              feeder.rotation_matrix_z (feeder.py:92-101).  Padding rows stay 0.  The host computes cos and sin: the device calls no
+ *              trig.  (c, s) = (1, 0) is NOT null: it turns a sample of -0.0 in Y or X into +0.0
+ *   outputs    every value is narrowed once, fp64 -> fp32, round to nearest.  Any of the three may be null, not all:
+ *     full     [n_out][size][channels]
+ *     mono     [n_out][size]: channel 0, the network's input
+ *     target   [n_out][t_len][channels - 1]: the channels 1.. of the rows [t_off, t_off + t_len) of every window; needs
+ *              channels >= 2, t_off >= 0, t_len >= 1 and t_off + t_len <= size (t_off and t_len are not looked at without it)
+ * The kernel is a total function of its arrays - any int32 / int64 content of lead, read_from and count is legal and moves no
+ * address out of bounds -, so there is no status word, and the entry point reads no device memory.
+ * Returns: n_out == 0 SAGEN_OK, nothing touched, before any pointer is examined; SAGEN_ERR_SHAPE for n_out or n_samples < 0,
+ * size < 1, channels < 1, a sample_type outside 0..2, a target with channels == 1 or with t_off / t_len outside the rule above, a
+ * pointer not aligned to its element (samples 2 / 4 / 8 bytes by type, lead and count 4, read_from and rot 8, full, mono and target
+ * 4); SAGEN_ERR_UNSUPPORTED for channels > 16, size > 1 << 24, rot with channels != 4; SAGEN_ERR_NULL for a null lead, read_from or
+ * count, all three outputs null, null samples with n_samples > 0.  A refused call writes nothing. */
+int sagen_assemble_audio(const void* samples, int sample_type, int64_t n_samples, int channels, const int32_t* lead, const int64_t* read_from,
+                         const int32_t* count, const double* rot, int n_out, int size, int t_off, int t_len, float* full, float* mono,
+                         float* target, void* stream);
+
 /* ---- moving point sources: encode to ambisonics, binauralise, track ------------------------------------------------------
  * The front end of the reference's ambisonics toolbox: AmbiEncoder.encode / encode_frame / encode_v2 (pyutils/ambisonics/
  * encoder.py:10-55), SourceBinauralizer over VirtualStereoMic and Convolvotron, static and per frame (binauralizer.py:12-121), and

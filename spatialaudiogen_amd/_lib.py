@@ -128,6 +128,7 @@ SIGNATURES = {
     'sagen_jpeg_encode_max_bytes': (_I64, [_I] * 5),
     'sagen_jpeg_encode': (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I64, _P, _P, _P, _SZ, _P]),
     'sagen_assemble_frames': (C.c_int, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
+    'sagen_assemble_audio': (C.c_int, [_P, _I, _I64, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     'sagen_window_rms': (C.c_int, [_P, _I64, _I, _I, _I64, _I64, _I64, _I64, _P, _P]),
     'sagen_source_track': (C.c_int, [_P, _P, _P, _P, _I, C.c_double, _I64, _I64, _I64, _P, _I, _P, _P, _P]),
     'sagen_encode_sources': (C.c_int, [_P, _I64, _P, _P, _P, _P, _I, C.c_double, _I, _I, C.c_double, _I64, _I64, _P, _P]),

@@ -3,6 +3,7 @@
 #include "kernels.h"
 #include "op_entries.h"        // the media ops' entry points, shared with the CPU twin; their backends are the launchers of the ops' .hip files
 #include "op_entries_feed.h"   // sagen_assemble_frames, likewise (a header of its own: see its first lines)
+#include "op_entries_audio.h"  // sagen_assemble_audio, likewise
 #include <new>
 #include <cstdlib>
 #include <algorithm>

@@ -45,5 +45,8 @@ int run_jpeg_encode(const uint8_t* frames, const JpegEncGeom& g, const uint16_t*
                     void* scratch, void* stream);
 int run_assemble_frames(const uint8_t* frames, int n_frames, int h, int w, const int32_t* index, const int32_t* shift, int n_out, int mode,
                         const float* table, const double* scale_lo, void* out, void* stream);
+int run_assemble_audio(const void* samples, int sample_type, int64_t n_samples, int channels, const int32_t* lead, const int64_t* read_from,
+                       const int32_t* count, const double* rot, int n_out, int size, int t_off, int t_len, float* full, float* mono,
+                       float* target, void* stream);
 
 }  // namespace sagen

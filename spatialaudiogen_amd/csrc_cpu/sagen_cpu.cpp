@@ -25,6 +25,7 @@
 
 #include "../csrc/op_entries.h"
 #include "../csrc/op_entries_feed.h"
+#include "../csrc/op_entries_audio.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -771,6 +772,39 @@ int run_assemble_frames(const uint8_t* frames, int n_frames, int h, int w, const
                 }
             }
     }
+    return SAGEN_OK;
+}
+
+/* Audio windows from a resident clip (include/sagen.h: sagen_assemble_audio; the cutting, padding and rotating of feeder.py:50-103 in
+ * the reference and the slicing of train.py:107-111): item by item, row by row over the core the device uses (csrc/audio_feed_core.h). */
+namespace {
+template <typename T>
+void assemble_audio_rows(const T* samples, int64_t n_samples, int channels, const int32_t* lead, const int64_t* read_from, const int32_t* count,
+                         const double* rot, int n_out, int size, int t_off, int t_len, float* full, float* mono, float* target) {
+    for (int i = 0; i < n_out; ++i)
+        for (int j = 0; j < size; ++j) {
+            double v[AUDIO_FEED_MAX_CHANNELS];
+            float o[AUDIO_FEED_MAX_CHANNELS];
+            int64_t src = 0;
+            const bool live = audio_feed_src_row(j, lead[i], read_from[i], count[i], n_samples, &src);
+            for (int c = 0; c < channels; ++c) v[c] = live ? audio_feed_value(samples[src * channels + c]) : 0.0;
+            if (live && rot) audio_feed_rotate(v, rot[2 * (size_t)i], rot[2 * (size_t)i + 1]);
+            for (int c = 0; c < channels; ++c) o[c] = live ? (float)v[c] : 0.f;
+            const size_t row = (size_t)i * size + j;
+            if (full) for (int c = 0; c < channels; ++c) full[row * channels + c] = o[c];
+            if (mono) mono[row] = o[0];
+            if (target && j >= t_off && j - t_off < t_len)
+                for (int c = 1; c < channels; ++c) target[((size_t)i * t_len + (j - t_off)) * (channels - 1) + (c - 1)] = o[c];
+        }
+}
+}  // namespace
+
+int run_assemble_audio(const void* samples, int sample_type, int64_t n_samples, int channels, const int32_t* lead, const int64_t* read_from,
+                       const int32_t* count, const double* rot, int n_out, int size, int t_off, int t_len, float* full, float* mono,
+                       float* target, void*) {
+    if (sample_type == AUDIO_I16) assemble_audio_rows((const int16_t*)samples, n_samples, channels, lead, read_from, count, rot, n_out, size, t_off, t_len, full, mono, target);
+    else if (sample_type == AUDIO_F32) assemble_audio_rows((const float*)samples, n_samples, channels, lead, read_from, count, rot, n_out, size, t_off, t_len, full, mono, target);
+    else assemble_audio_rows((const double*)samples, n_samples, channels, lead, read_from, count, rot, n_out, size, t_off, t_len, full, mono, target);
     return SAGEN_OK;
 }
 

@@ -6,9 +6,10 @@
 Host-side only: window arithmetic, batching in groups of 10 with zero-padded last group
 (deploy.py:112-139 — the padding is part of the result because batch-norm runs on batch statistics),
 H2D staging and the final [mono | prediction] assembly.  All tensor arithmetic runs in
-libsagen_hip.so through SptAudioGen.inference_ops.  With decode='device' (--decode device) the frames
-do not pass through the host either: feeder.DeviceFrames decodes the files on the device and builds
-every batch there; only the files' bytes and the audio are staged.
+libsagen_hip.so through SptAudioGen.inference_ops.  With decode='device' (--decode device) neither the
+frames nor the audio windows pass through the host: feeder.DeviceFrames decodes the jpg files on the
+device, feeder.DeviceAudio keeps the wav pieces there as stored, and every batch is assembled there;
+only the files' bytes are staged.
 """
 import os
 import numpy as np
@@ -149,7 +150,8 @@ class W2XYZ(object):
     groups = 1
 
     # where the frames of a clip FOLDER are decoded and batched: 'host' (PIL in the reader, numpy batches, one H2D copy per batch) or
-    # 'device' (feeder.DeviceFrames: the files' bytes go up once, jpeg.py decodes, sagen_assemble_frames builds every batch there).
+    # 'device' (feeder.DeviceFrames: the files' bytes go up once, jpeg.py decodes, sagen_assemble_frames builds every batch there; the
+    # audio windows likewise, feeder.DeviceAudio / sagen_assemble_audio over the wav pieces as stored).
     # The model sees the same bits either way; a ClipArrays source holds decoded arrays already and ignores this
     decode = 'host'
 
@@ -189,7 +191,8 @@ class W2XYZ(object):
         return load_checkpoint(prefix)
 
     def _reader(self, source, deploy_start, deploy_duration, frames=True):
-        """frames=False: the reader serves the audio only (the frames come from feeder.DeviceFrames)."""
+        """frames=False: the reader decodes no frames (decode='device' takes only its window times: the frames come from
+        feeder.DeviceFrames, the audio windows from feeder.DeviceAudio)."""
         p = self.params
         if isinstance(source, ClipArrays):
             return source.windowed(deploy_start, deploy_duration)
@@ -261,11 +264,12 @@ class W2XYZ(object):
         reader.chunks_t = [t - dt for t in reader.chunks_t]
         use_v, use_f = VIDEO in p.encoders, FLOW in p.encoders
         frame_of = self._overlay_frames(input_folder, reader) if overlay is not None and not on_device else None
-        vdev = fdev = None
-        if on_device:       # the frames the window table references, and only those, decoded once and kept on the device
-            from .feeder import DeviceFrames
+        vdev = fdev = adev = None
+        if on_device:       # the frames the window table references, and only those, decoded once and kept on the device; the wav pieces as stored
+            from .feeder import DeviceFrames, DeviceAudio
             if self.video_size != 1:
                 raise ValueError("decode='device' needs one frame per window (duration %g s x video_rate %g != 1)" % (self.duration, p.video_rate))
+            adev = DeviceAudio(os.path.join(input_folder, 'ambix'), p.audio_rate, p.ambi_order, device=m.device)
             wanted = [frame_index(t, p.video_rate) for t in reader.chunks_t]
             if use_v or overlay is not None:
                 vdev = DeviceFrames(os.path.join(input_folder, 'video'), 'video', device=m.device, rate=p.video_rate)
@@ -274,11 +278,19 @@ class W2XYZ(object):
                 fdev = DeviceFrames(os.path.join(input_folder, 'flow'), 'flow', device=m.device, rate=p.video_rate)
                 fdev.ensure(min(wanted), max(wanted) + 1)
 
+        def next_chunk():
+            if not on_device:
+                return reader.get()
+            reader.head += 1                                             # the reader's walk over chunks_t, without cutting a window
+            if reader.head >= len(reader.chunks_t):
+                return None
+            return {'t': reader.chunks_t[reader.head]}
+
         def batches():                                                   # deploy.py:112-139
             while True:
                 batch = []
                 for _ in range(self.batch_size):
-                    chunk = reader.get()
+                    chunk = next_chunk()
                     if chunk is None:
                         break
                     if on_device:                                        # the frame SampleReader.sample_at would decode
@@ -290,13 +302,15 @@ class W2XYZ(object):
                     return
                 n = len(batch)
                 out = {'n': n}
-                audio = np.zeros((self.batch_size, self.audio_size, 1), np.float32)   # zero rows = deploy.py:125-127
-                audio[:n] = np.stack([b['ambix'] for b in batch], 0)[:, :, :1]
-                out['audio'] = audio
+                if not on_device:
+                    audio = np.zeros((self.batch_size, self.audio_size, 1), np.float32)   # zero rows = deploy.py:125-127
+                    audio[:n] = np.stack([b['ambix'] for b in batch], 0)[:, :, :1]
+                    out['audio'] = audio
                 if frame_of is not None:
                     out['frames'] = np.stack([b['frame'] for b in batch], 0)
                 if on_device:
-                    out['index'] = [b['index'] for b in batch]               # (a list: indices instead of arrays, nothing to pin)
+                    out['index'] = [b['index'] for b in batch]               # (lists: times and indices instead of arrays, nothing to pin)
+                    out['times'] = [b['t'] for b in batch]
                 for key, on in (('video', use_v), ('flow', use_f)):
                     if on and not on_device:
                         clip = np.stack([b[key] for b in batch], 0)
@@ -315,17 +329,18 @@ class W2XYZ(object):
 
         def run(net, bs):               # one forward call over the batches `bs` (len(bs) == net.groups), results appended in order
             cat = lambda k: torch.cat([torch.as_tensor(b[k]) for b in bs], 0).to(m.device, non_blocking=True) if k in bs[0] else None
-            a_dev = cat('audio')
             if on_device:               # the rules of batches(): full batches give uint8 video, a partial one float frames padded with 0.0
                 idx = [i for b in bs for i in b['index']]
                 full = all(b['n'] == self.batch_size for b in bs)
                 if not full and len(bs) != 1:
                     raise RuntimeError('a partial batch in a group of %d' % len(bs))
                 pad = None if full else self.batch_size
+                # the mono windows [B, 52799, 1], zero windows behind a partial batch included: one launch over the resident clip
+                a_dev = adev.batch([t for b in bs for t in b['times']], p.context, self.audio_size, pad_to=pad)[0]
                 v_dev = vdev.batch(idx, pad_to=pad, as_float=not full) if use_v else None
                 f_dev = fdev.batch(idx, pad_to=pad) if use_f else None
             else:
-                v_dev, f_dev = cat('video'), cat('flow')
+                a_dev, v_dev, f_dev = cat('audio'), cat('video'), cat('flow')
             # deploy.py:141 - with the fp16x2 guard: a batch whose trunk planes clamped anything is re-run on bf16 planes
             pred = net.inference_ops_checked(a_dev, v_dev, f_dev, on_saturation=self.on_saturation)
             wyzx = ops.assemble_wyzx(a_dev[:, :, 0].contiguous(), pred, m.snd_contx)   # deploy.py:143-152

@@ -112,10 +112,28 @@ class Evaluator(object):
         m = torch.as_tensor(pad(masks.astype(np.float32))).to(dev)
         self._finish(ids, a, pred, m, n)
 
+    def run_views(self, ids, mono, target, video, flow, masks, net=None, full=None):
+        """The device feed's forward call: the windows come as the views the op wrote (mono [N,52799,1], target [N,4800,3], both on the
+        device; N = 16 x the net's groups, a partial batch already padded with zero windows), masks [n <= N, 4] of the real windows.
+        net: the grouped facade for more than one batch (run_batches' rules), None for one batch (run_batch's)."""
+        import torch
+        n, N = masks.shape[0], mono.shape[0]
+        m = np.zeros((N, 4), np.float32)
+        m[:n] = masks
+        if net is None:
+            pred = self.net.inference_ops_checked(mono, video, flow)
+        else:
+            pred = net.inference_ops_checked(mono, video, flow, on_saturation='raise')
+        self._finish_views(ids, mono, target, pred, torch.as_tensor(m).to(self.net.device), n, full)
+
     def _finish(self, ids, a, pred, m, n):
         """metrics + rows of the first n windows of a forward's worth of windows (a [N,52799,4] on the device, pred [N,4800,3], m [N,4])"""
+        self._finish_views(ids, a[:, :, :1], a[:, self.ss:self.ss + self.t, 1:].contiguous(), pred, m, n, a)
+
+    def _finish_views(self, ids, mono, target, pred, m, n, full=None):
+        """_finish on the views themselves: mono [N,52799,1] (or full [N,52799,4], whose channel 0 it is), target [N,4800,3] contiguous"""
         import torch
-        target = a[:, self.ss:self.ss + self.t, 1:].contiguous()
+        a = full if full is not None else mono
         _, stft_ps, lsd_ps, mse_ps, snr_ps = self.net.evaluation_ops(pred, target, None, m[:, 1:])
         amp_p = pred.abs().amax(dim=(1, 2)); amp_g = target.abs().amax(dim=(1, 2))
         per = torch.stack([amp_p, amp_g], 1).cpu().numpy()
@@ -193,17 +211,88 @@ class _ReaderCache(object):
         return self.items[yid]
 
 
+class DeviceFeed(object):
+    """evaluate --decode device: the inputs of one forward call made on the device from the clip folders.
+
+    Audio: the clips' wav pieces stay resident as stored (feeder.DeviceAudio, the most recently used clips), and the mono input and
+    the target rows of a call are written by sagen_assemble_audio - one launch per run of consecutive windows of one clip, into slices
+    of the call's two tensors; the padding windows of a partial batch ride on the last launch.  The whole windows are never built:
+    the metrics and the power maps read channel 0 and the centre rows of the others only.
+    Frames: evaluate takes every 10th window, so a resident range of frames (feeder.DeviceFrames.ensure) would decode ten times too
+    many; exactly the files the call's windows name, of whatever clips, go through ONE JpegDecoder.decode per folder kind.  Video
+    goes in as decoded (uint8); flow through sagen_assemble_frames mode 2 with the scale_lo rows of those frames; a zero-padded
+    partial batch through modes 1 / 2 with padding indices (0.0 after normalisation)."""
+
+    def __init__(self, db_dir, params, device, keep=2):
+        import torch
+        from .feeder import DeviceAudio, flow_table, video_table
+        from .jpeg import JpegDecoder
+        self.db_dir, self.params, self.device = db_dir, params, device
+        self.use_v, self.use_f = VIDEO in params.encoders, FLOW in params.encoders
+        self.size = int(0.1 * params.audio_rate) + int(params.context * params.audio_rate) - 1      # SampleReader.audio_size
+        self.ss, self.t = int(params.audio_rate * params.context) // 2, int(params.audio_rate * 0.1)
+        self.audio = _ReaderCache(lambda yid: DeviceAudio(os.path.join(db_dir, yid, 'ambix'), params.audio_rate, params.ambi_order,
+                                                          device=device), keep)
+        self.decoder = JpegDecoder(device) if self.use_v or self.use_f else None
+        self._tables = {k: torch.as_tensor(np.ascontiguousarray(f(), dtype=np.float32)).to(device)
+                        for k, f in (('video', video_table), ('flow', flow_table)) if (self.use_v if k == 'video' else self.use_f)}
+        self._scale_lo = _ReaderCache(self._load_scale_lo, keep)
+
+    def _load_scale_lo(self, yid):
+        from .feeder import flow_scale_lo
+        return flow_scale_lo(np.load(os.path.join(self.db_dir, yid, 'flow', 'flow_limits.npy')))
+
+    def call(self, wins, total):
+        """wins [(clip id, t)] in order, total >= len(wins) windows in the call -> (ids, mono [total,52799,1], target [total,4800,3],
+        video, flow): what SampleReader.sample_at + the stacking of evaluate() + Evaluator.run_batch's padding make on the host."""
+        import torch
+        from .deploy import frame_index
+        from .feeder import frames_batch
+        p, n = self.params, len(wins)
+        mono = torch.empty((total, self.size, 1), dtype=torch.float32, device=self.device)
+        target = torch.empty((total, self.t, 3), dtype=torch.float32, device=self.device)
+        a = 0
+        while a < n:                                                    # runs of consecutive windows of one clip
+            b = a + 1
+            while b < n and wins[b][0] == wins[a][0]:
+                b += 1
+            stop = total if b == n else b                               # the padding windows ride on the last launch
+            self.audio.get(wins[a][0]).batch([t for _, t in wins[a:b]], p.context, self.size, pad_to=stop - a, want=('mono', 'target'),
+                                             t_off=self.ss, t_len=self.t, out={'mono': mono[a:stop], 'target': target[a:stop]})
+            a = b
+        frames = {}
+        for kind, on in (('video', self.use_v), ('flow', self.use_f)):
+            if not on:
+                frames[kind] = None
+                continue
+            index = [frame_index(t, p.video_rate) for _, t in wins]
+            decoded = self.decoder.decode([os.path.join(self.db_dir, yid, kind, '%06d.jpg' % i) for (yid, _), i in zip(wins, index)])
+            if kind == 'video' and total == n:
+                frames[kind] = decoded[:, None]                         # [n, 1, H, W, 3] uint8 as decoded (sagen_forward_u8)
+                continue
+            scale_lo = None
+            if kind == 'flow':
+                scale_lo = torch.as_tensor(np.ascontiguousarray(np.stack([self._scale_lo.get(yid)[i] for (yid, _), i in zip(wins, index)], 0))).to(self.device)
+            frames[kind] = frames_batch(decoded, self._tables[kind], 2 if kind == 'flow' else 1, pad_to=total, scale_lo=scale_lo)
+        return ['%s %s' % (yid, t) for yid, t in wins], mono, target, frames['video'], frames['flow']
+
+
 def evaluate(model_dir, db_dir, subset_fn=None, layouts_fn=None, variables=None, params=None, overwrite=True,
-             partial_batch='drop', power_maps=False, groups=1, all_metrics=False):
+             partial_batch='drop', power_maps=False, groups=1, all_metrics=False, decode='host'):
+    """decode: 'host' (SampleReader: numpy windows, PIL frames, one upload per batch) or 'device' (DeviceFeed); the rows written are the
+    same, line for line."""
     import torch
     from .deploy import load_params, W2XYZ
     from .feeder import SampleReader
+    if decode not in ('host', 'device'):
+        raise ValueError("decode must be 'host' or 'device', not %r" % (decode,))
     rank, world = init_process_group()
     if torch.cuda.is_available():
         torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', 0)) % torch.cuda.device_count())
     params = params or load_params(model_dir)
     w2 = W2XYZ(model_dir, params=params, variables=variables)
     net = w2.model
+    feed = DeviceFeed(db_dir, params, net.device) if decode == 'device' else None
     ids = [l.strip() for l in open(subset_fn)] if subset_fn else sorted(os.listdir(db_dir))
     ids = [i for i in ids if i and os.path.isdir(os.path.join(db_dir, i))]
     layouts = read_layouts(layouts_fn)
@@ -221,28 +310,44 @@ def evaluate(model_dir, db_dir, subset_fn=None, layouts_fn=None, variables=None,
     w2.groups = max(1, int(groups))
     gnet = w2._grouped_model(w2.groups) if w2.groups > 1 else None
     pending = []
+    masks_of = lambda wins: np.stack([layouts.get(yid, np.ones(4)) for yid, _ in wins], 0)
 
-    def flush(force_single=False):
-        if pending and (force_single or len(pending) < w2.groups):
-            for q in pending:
-                ev.run_batch(*q)
-        elif pending:
-            ev.run_batches(pending, gnet)
-        del pending[:]
-    for b in range(lo, hi):
-        wins = plan[b * BATCH_SIZE:(b + 1) * BATCH_SIZE]
+    def host_item(wins):
         samples = [readers.get(yid).sample_at(t) for yid, t in wins]
         def stack(k):
             if k not in samples[0]:
                 return None
             x = np.stack([smp[k] for smp in samples], 0)
             return x if (k == 'video' and x.dtype == np.uint8) else x.astype(np.float32)
-        item = ([smp['id'] for smp in samples], stack('ambix'), stack('video'), stack('flow'),
-                np.stack([layouts.get(yid, np.ones(4)) for yid, _ in wins], 0))
-        full = len(samples) == BATCH_SIZE and (item[2] is None or item[2].dtype == np.uint8)
+        return ([smp['id'] for smp in samples], stack('ambix'), stack('video'), stack('flow'), masks_of(wins))
+
+    def run_single(item):
+        if feed is None:
+            return ev.run_batch(*item)
+        ids_, mono, target, video, flow = feed.call(item, BATCH_SIZE)             # (an item of the device feed is its windows)
+        ev.run_views(ids_, mono, target, video, flow, masks_of(item))
+
+    def run_group(items):
+        if feed is None:
+            return ev.run_batches(items, gnet)
+        wins = [w for q in items for w in q]
+        ids_, mono, target, video, flow = feed.call(wins, len(wins))
+        ev.run_views(ids_, mono, target, video, flow, masks_of(wins), net=gnet)
+
+    def flush(force_single=False):
+        if pending and (force_single or len(pending) < w2.groups):
+            for q in pending:
+                run_single(q)
+        elif pending:
+            run_group(pending)
+        del pending[:]
+    for b in range(lo, hi):
+        wins = plan[b * BATCH_SIZE:(b + 1) * BATCH_SIZE]
+        item = host_item(wins) if feed is None else wins
+        full = len(wins) == BATCH_SIZE and (feed is not None or item[2] is None or item[2].dtype == np.uint8)
         if gnet is None or not full:
             flush(force_single=True)
-            ev.run_batch(*item)
+            run_single(item)
             continue
         pending.append(item)
         if len(pending) == w2.groups:
@@ -303,6 +408,11 @@ def arg_parser():
     ap.add_argument('--all_metrics', action='store_true',
                     help="write all 28 columns of the reference's eval.py (ALL_METRIC_KEYS): adds mel_lsd, env_mse and emd/dir, emd/dir2, "
                          'computed on the device')
+    ap.add_argument('--decode', choices=['host', 'device'], default='host',
+                    help="where the windows and frames of a batch are made: 'host' (numpy windows, PIL frames, one upload per batch) or 'device' "
+                         "(the clips' wav pieces stay on the device and sagen_assemble_audio cuts input and target there; the frame files' bytes go "
+                         'up and jpeg.py decodes them); the same rows, line for line.  A decode call costs the same whatever it holds: measured, device is slower than '
+                         'host below --groups 4 and faster from there on (README)')
     return ap
 
 
@@ -312,7 +422,7 @@ def main(argv=None):
     require_first_order(load_params(args.model_dir).ambi_order, 'evaluate')
     means, count = evaluate(args.model_dir, args.db_dir, args.subset_fn, args.layouts_fn, overwrite=args.overwrite,
                             partial_batch=args.partial_batch, power_maps=args.power_maps, groups=args.groups,
-                            all_metrics=args.all_metrics)
+                            all_metrics=args.all_metrics, decode=args.decode)
     if args.power_maps and evaluate.last_maps:
         maps = evaluate.last_maps                      # [pred, gt, pred, gt, ...] per batch, each [n, 7, 12]
         np.savez(os.path.join(args.model_dir, 'eval-powermaps-rank%d.npz' % int(os.environ.get('RANK', 0))),

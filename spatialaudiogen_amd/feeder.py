@@ -20,8 +20,9 @@ gets -
     frame index                         max(int(t * video_rate), 0)                    feeder.py:121
     time filters on audio_pow.lst       skip_rate, silence, start, duration, threads   feeder.py:222-238
 - the truncations differ by one sample for about a fifth of the windows, and the network sees that.
-Nothing here touches the GPU, except load_wav(..., resample=...) when it is asked to resample a file (resample.py) and
-`DeviceFrames`, the device-resident counterpart of `JpgFrames` / `FlowFrames` (jpeg.py decodes, sagen_assemble_frames batches).
+Nothing here touches the GPU, except load_wav(..., resample=...) when it is asked to resample a file (resample.py),
+`DeviceFrames`, the device-resident counterpart of `JpgFrames` / `FlowFrames` (jpeg.py decodes, sagen_assemble_frames batches), and
+`DeviceAudio`, that of `WavPieces` (the pieces go up as stored, sagen_assemble_audio cuts the windows).
 """
 import collections
 import os
@@ -305,6 +306,50 @@ class FlowFrames(object):
 FlowReader = FlowFrames
 
 
+def video_table():
+    """table[byte] of sagen_assemble_frames mode 1: frames_to_float of every byte value"""
+    return frames_to_float(np.arange(256).astype(np.uint8))
+
+
+def flow_table():
+    """cos[256] then sin[256] of the angle a byte stands for (sagen_assemble_frames mode 2), by the expressions of FlowFrames.frames"""
+    angle = np.arange(256).astype(np.float32)
+    angle *= (2 * np.pi) / 255.
+    return np.concatenate([np.cos(angle), np.sin(angle)])
+
+
+def flow_scale_lo(limits):
+    """flow_limits.npy [frames, 2] -> the operands ((hi - lo) / 255., lo) of FlowFrames.frames per frame, by its own expressions and in
+    the file's dtype, then widened (exact): float64 [frames, 2]"""
+    lo, hi = limits[:, 0], limits[:, 1]
+    return np.stack([(hi - lo) / 255., lo], 1).astype(np.float64)
+
+
+def frames_batch(frames, table, mode, pad_to=None, scale_lo=None):
+    """Decoded frames uint8 [n, H, W, 3] on the device, in batch order -> float32 [pad_to or n, 1, H, W, 3] there by one launch of
+    sagen_assemble_frames: mode 1 table[byte] (video_table: frames_to_float), mode 2 the flow un-coding (flow_table, scale_lo float64
+    [n, 2] on the device, row i for frame i); the items behind n are 0.0.  For frames that are decoded per batch, not resident
+    (evaluate --decode device); a resident clip batches through DeviceFrames.batch."""
+    import torch
+    from . import _lib
+    from .ops import _ptr, _stream
+    n, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    total = n if pad_to is None else int(pad_to)
+    if total < n:
+        raise ValueError('pad_to=%d is less than the %d frames given' % (total, n))
+    out = torch.empty((total, 1, h, w, 3), dtype=torch.float32, device=frames.device)
+    if total == 0:
+        return out
+    args = np.zeros((2, total), np.int32)
+    args[0] = -1                                                       # padding
+    args[0, :n] = np.arange(n)
+    dev = torch.as_tensor(args).to(frames.device)
+    frames = frames.contiguous()
+    _lib.check(_lib.lib().sagen_assemble_frames(_ptr(frames), n, h, w, _ptr(dev[0]), _ptr(dev[1]), total, int(mode), _ptr(table),
+                                                _ptr(scale_lo) if mode == 2 else None, _ptr(out), _stream()))
+    return out
+
+
 class DeviceFrames(object):
     """The %06d.jpg frames of a folder RESIDENT ON THE DEVICE, and batches assembled from them there (include/sagen.h:
     sagen_assemble_frames): what JpgFrames.frames (kind='video') and FlowFrames.frames (kind='flow', with the folder's
@@ -351,15 +396,11 @@ class DeviceFrames(object):
             limits = np.load(os.path.join(self.folder, 'flow_limits.npy'))
             if limits.ndim != 2 or limits.shape[1] != 2:
                 raise ValueError('flow_limits.npy must be [frames, 2], not %s' % (limits.shape,))
-            # the operands of FlowFrames.frames, by its own expressions and in the file's dtype, then widened (exact)
-            lo, hi = limits[:, 0], limits[:, 1]
             self.limits = limits
-            self._scale_lo = torch.as_tensor(np.stack([(hi - lo) / 255., lo], 1).astype(np.float64)).contiguous().to(self.device)
-            angle = np.arange(256).astype(np.float32)
-            angle *= (2 * np.pi) / 255.
-            table = np.concatenate([np.cos(angle), np.sin(angle)])
+            self._scale_lo = torch.as_tensor(flow_scale_lo(limits)).contiguous().to(self.device)
+            table = flow_table()
         else:
-            table = frames_to_float(np.arange(256).astype(np.uint8))
+            table = video_table()
         self._table = torch.as_tensor(np.ascontiguousarray(table, dtype=np.float32)).to(self.device)
 
     def ensure(self, first, stop):
@@ -438,6 +479,142 @@ class DeviceFrames(object):
                                                     _ptr(self._table), _ptr(self._scale_lo[self.first:]) if mode == 2 else None, _ptr(out),
                                                     _stream()))
         return out
+
+
+class DeviceAudio(object):
+    """The %06d.wav pieces of an ambix folder RESIDENT ON THE DEVICE, and batches of windows assembled from them there (include/sagen.h:
+    sagen_assemble_audio): what WavPieces.assemble(...).astype(float32) returns for every window, without a window crossing the bus -
+    and, in the same launch, the two views the network is fed from (the mono input, the target rows of the other channels).
+
+        batch(times, context, size, ...)     the windows at `times`, as the outputs named by `want`, on the device
+
+    The samples are kept as the files store them when that is int16 or float32 (the op widens them as load_wav does), float64 of
+    load_wav's values otherwise (other PCM widths, pieces of mixed types).  Piece i lies at row i * rate; num_frames = n_files * rate as
+    WavPieces has it; a short LAST piece is zero-filled, any other piece that is not `rate` rows long raises ValueError (WavPieces would
+    read zeros or the wrong rows there).  A file at another rate raises, as load_wav does by default: nothing is resampled here.
+    With SAGEN_LIB naming the CPU twin everything runs on device='cpu'."""
+
+    OUTPUTS = ('full', 'mono', 'target')
+
+    def __init__(self, folder, rate=None, ambi_order=1, device=None):
+        import torch
+        from scipy.io import wavfile
+        from . import _lib
+        self.folder = str(folder)
+        self.num_files = sum(1 for f in os.listdir(folder) if f.endswith('.wav'))
+        if self.num_files == 0:
+            raise IOError('no wav pieces in %s' % folder)
+        pieces = []
+        for i in range(self.num_files):
+            fname = os.path.join(self.folder, '%06d.wav' % i)
+            file_rate, pcm = wavfile.read(fname)
+            if i == 0:
+                self.rate = float(file_rate) if rate is None else rate
+                self.num_channels = min(1 if pcm.ndim == 1 else pcm.shape[1], (ambi_order + 1) ** 2)
+            if int(self.rate) != int(file_rate):
+                raise ValueError('%s is sampled at %d Hz, expected %d (DeviceAudio does not resample)' % (fname, file_rate, self.rate))
+            pcm = pcm[:, None] if pcm.ndim == 1 else pcm
+            if pcm.shape[1] < self.num_channels:
+                raise ValueError('%s has %d channels, the first piece has %d' % (fname, pcm.shape[1], self.num_channels))
+            pieces.append(pcm[:, :self.num_channels])
+        per = int(self.rate)
+        self.duration = self.num_files
+        self.num_frames = int(self.duration * self.rate)
+        for i, pcm in enumerate(pieces):
+            if pcm.shape[0] > per or (pcm.shape[0] < per and i != self.num_files - 1):
+                raise ValueError('%s holds %d samples, not the %d of one second (only the last piece may be short)'
+                                 % (os.path.join(self.folder, '%06d.wav' % i), pcm.shape[0], per))
+        kinds = set(p.dtype for p in pieces)
+        if kinds == {np.dtype(np.int16)} or kinds == {np.dtype(np.float32)}:
+            dtype = kinds.pop()
+        else:                                                          # load_wav's values
+            dtype = np.dtype(np.float64)
+            for i, pcm in enumerate(pieces):
+                offset, scale = _PCM_SCALE.get(pcm.dtype, (0.0, 1.0))
+                pieces[i] = (pcm.astype(np.float64) - offset) / scale
+        self.sample_type = {np.dtype(np.int16): 0, np.dtype(np.float32): 1, np.dtype(np.float64): 2}[dtype]
+        host = np.zeros((self.num_frames, self.num_channels), dtype)
+        for i, pcm in enumerate(pieces):
+            host[i * per:i * per + pcm.shape[0]] = pcm
+        _lib.lib()
+        self.device = torch.device(device if device is not None else ('cpu' if _lib.IS_CPU_TWIN else 'cuda'))
+        self._samples = torch.as_tensor(host).to(self.device)
+
+    def table(self, times, context, size):
+        """The window table of `times` over this clip (see window_table)."""
+        return window_table(times, context, size, self.rate, self.num_frames)
+
+    def batch(self, times, context, size, rotations=None, pad_to=None, want=('mono',), t_off=None, t_len=None, out=None):
+        """The `size`-sample windows at `times` (window_table's arithmetic with `context`), window i rotated about the vertical axis by
+        rotations[i] (a sequence, one number for all, or None; each angle in [-pi, pi) as WavPieces.assemble demands; needs the 4
+        first-order channels).  Returns a tuple of float32 device tensors in the order of `want`:
+            'full'    [n, size, channels]
+            'mono'    [n, size, 1]: channel 0, the network's input
+            'target'  [n, t_len, channels - 1]: the other channels of the rows [t_off, t_off + t_len)
+        pad_to: the outputs are filled up to pad_to windows with windows of zeros (read_count = 0; a zero-padded partial batch).
+        out: {name: tensor} to write into (contiguous, of exactly these shapes - slices along the first axis of a larger batch, say),
+        instead of new tensors.  The three columns of the table and the (cos, sin) pairs go up in one small tensor; one launch.
+        When `rotations` mixes None with angles, None becomes (cos, sin) = (1, 0), which is the identity on every value but one: a
+        sample of -0.0 in Y or X comes out as +0.0 (1 * -0.0 + 0 * x).  All None passes no rotation at all and keeps it."""
+        import ctypes as C
+        import torch
+        from . import _lib
+        from .ops import _ptr, _stream
+        want = (want,) if isinstance(want, str) else tuple(want)
+        if not want or any(w not in self.OUTPUTS for w in want) or len(set(want)) != len(want):
+            raise ValueError('want must name one or more of %s, once each; not %r' % (self.OUTPUTS, want))
+        times = [float(t) for t in times]
+        n, size = len(times), int(size)
+        if rotations is None or isinstance(rotations, (int, float)):
+            rotations = [rotations] * n
+        if len(rotations) != n:
+            raise ValueError('%d rotations for %d windows' % (len(rotations), n))
+        rotated = any(r is not None for r in rotations)
+        for r in rotations:
+            if r is not None and not -np.pi <= r < np.pi:
+                raise ValueError('rotation must lie in [-pi, pi)')
+        if rotated and self.num_channels != 4:
+            raise ValueError('a rotation needs the 4 first-order channels (W,Y,Z,X), this clip has %d' % self.num_channels)
+        total = n if pad_to is None else int(pad_to)
+        if total < n:
+            raise ValueError('pad_to=%d is less than the %d windows asked for' % (total, n))
+        if 'target' in want:
+            if t_off is None or t_len is None:
+                raise ValueError("want='target' needs t_off and t_len")
+            if self.num_channels < 2 or not (0 <= int(t_off) and 1 <= int(t_len) and int(t_off) + int(t_len) <= size):
+                raise ValueError('target rows t_off=%s t_len=%s of %d-sample windows of %d channels' % (t_off, t_len, size, self.num_channels))
+        t_off, t_len = (int(t_off), int(t_len)) if 'target' in want else (0, 0)
+        shapes = {'full': (total, size, self.num_channels), 'mono': (total, size, 1), 'target': (total, t_len, self.num_channels - 1)}
+        outs = {}
+        for w in want:
+            if out is not None and w in out:
+                o = out[w]
+                if tuple(o.shape) != shapes[w] or o.dtype != torch.float32 or o.device != self._samples.device or not o.is_contiguous():
+                    raise ValueError('out[%r] must be a contiguous float32 %s on %s' % (w, shapes[w], self.device))
+                outs[w] = o
+            else:
+                outs[w] = torch.empty(shapes[w], dtype=torch.float32, device=self.device)
+        if total == 0:
+            return tuple(outs[w] for w in want)
+        # one int64 buffer: read_from [total] | (cos, sin) [total][2] as fp64 | lead [total] int32 | read_count [total] int32
+        buf = np.zeros(4 * total, np.int64)
+        i32 = buf[3 * total:].view(np.int32)
+        if n:
+            tab = window_table(times, context, size, self.rate, self.num_frames)
+            buf[:n] = tab.read_from
+            i32[:n] = tab.lead
+            i32[total:total + n] = tab.read_count
+        if rotated:
+            cs = buf[total:3 * total].view(np.float64).reshape(total, 2)
+            cs[:, 0] = 1.0
+            cs[:n] = [(1.0, 0.0) if r is None else (np.cos(r), np.sin(r)) for r in rotations]
+        dev = torch.as_tensor(buf).to(self.device)
+        base = dev.data_ptr()
+        _lib.check(_lib.lib().sagen_assemble_audio(
+            _ptr(self._samples), self.sample_type, int(self._samples.shape[0]), self.num_channels, C.c_void_p(base + 24 * total),
+            C.c_void_p(base), C.c_void_p(base + 28 * total), C.c_void_p(base + 8 * total) if rotated else None, total, size, t_off, t_len,
+            _ptr(outs.get('full')), _ptr(outs.get('mono')), _ptr(outs.get('target')), _stream()))
+        return tuple(outs[w] for w in want)
 
 
 # ------------------------------------------------------------------------------------------------
