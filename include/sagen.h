@@ -189,7 +189,12 @@ int    sagen_profile_report(sagen_ctx* ctx, char* buf, size_t buflen);
 /* myutils.stft (myutils.py:119-147) fused with the crop + tf.abs of audio_encoder_ops
  * (model.py:166-178): hop = wind/4, periodic Hann, 1024-pt FFT.
  * mag [B, f1-f0, 1024] magnitudes of frames [f0,f1); spec [B, c1-c0, 513, 2] (re,im) of frames
- * [c0,c1) (bins 0..512; the rest is the Hermitian mirror).  Either output may be NULL. */
+ * [c0,c1) (bins 0..512; the rest is the Hermitian mirror).  Either output may be NULL, not both.
+ * Legal frames are the reference's: frame t covers samples [256 t, 256 t + 1024), and n_samples has
+ * 4 * (n_samples / 1024 - 1) of them (integer division; 200 at 52799 samples, none below 2048) - frames that merely fit behind
+ * those are not produced by myutils.stft and are refused.  SAGEN_ERR_SHAPE, before anything is launched, for batch <= 0,
+ * f0 < 0, f1 <= f0, f1 > 4 * (n_samples / 1024 - 1) and, where spec is given, c0 < f0, c1 > f1 or c1 <= c0 (c0, c1 are ignored
+ * where spec is NULL).  Both libraries share the rule (csrc/stft_frames.h). */
 int sagen_stft_mag(const float* audio, int batch, int n_samples, int f0, int f1, float* mag,
                    int c0, int c1, float* spec, void* stream);
 

@@ -14,6 +14,7 @@
 //    step) — two of them packed per complex transform — instead of 32 complex iFFTs per frame.
 //    (Changes rounding order only; bounded far below the 1e-4 parity budget, tests/test_gpu_*.)
 #include "kernels.h"
+#include "stft_frames.h"
 #include <mutex>
 
 namespace sagen {
@@ -135,10 +136,9 @@ __global__ __launch_bounds__(256) void stft_kernel(const float* __restrict__ aud
 
 int stft_launch(const float* audio, int B, int n_samples, int f0, int f1, float* mag, int c0, int c1, float* spec,
                 const GroupInfo& gi, hipStream_t s, float* zero_ptr, int zero_n) {
-    if (f1 <= f0 || 256L * (f1 - 1) + 1024 > n_samples)
-        return fail(SAGEN_ERR_SHAPE, "stft: frames [%d,%d) do not fit %d samples", f0, f1, n_samples);
-    if (spec && (c0 < f0 || c1 > f1 || c1 <= c0)) return fail(SAGEN_ERR_SHAPE, "stft: spec frames must lie in [f0,f1)");
-    int rc = fft_tables_ensure(s);
+    int rc = stft_frames_check(n_samples, f0, f1, spec != nullptr, c0, c1);      // (stft_frames.h: f0 >= 0 and the reference's frame count)
+    if (rc) return rc;
+    rc = fft_tables_ensure(s);
     if (rc) return rc;
     hipLaunchKernelGGL(stft_kernel, dim3(cdiv(f1 - f0, 2), B, gi.G), dim3(256), 0, s, audio, n_samples, f0, f1, mag, c0, c1,
                        (float2*)spec, zero_ptr, zero_ptr ? zero_n : 0, gi);
@@ -307,9 +307,11 @@ size_t mask_istft_scratch_bytes(int B) { return (size_t)B * MASK_NF * 3 * 1024 *
 
 int mask_istft_mix_launch(const float* dmask, long dmask_bstride, int dmask_f0, const float* spec, const float* coeffs,
                           int B, int ntracks, float* out, float* scratch, const GroupInfo& gi, hipStream_t s, const float* ebuf) {
+    if (dmask_f0 > MASK_F_LO) return fail(SAGEN_ERR_SHAPE, "mask_istft: dmask must start at frame <= %d", MASK_F_LO);
+    if (ntracks != 16 && ntracks != 32 && ntracks != 64)      // (before the tables' launch: a refused call launches nothing)
+        return fail(SAGEN_ERR_UNSUPPORTED, "mask_istft: num_sep_tracks=%d (supported: 16, 32, 64)", ntracks);
     int rc = fft_tables_ensure(s);
     if (rc) return rc;
-    if (dmask_f0 > MASK_F_LO) return fail(SAGEN_ERR_SHAPE, "mask_istft: dmask must start at frame <= %d", MASK_F_LO);
     dim3 grid(MASK_NF, B, gi.G);
     if (ntracks == 32)
         hipLaunchKernelGGL(mask_istft_kernel<32>, grid, dim3(256), 0, s, dmask, dmask_bstride, dmask_f0, (const float2*)spec, coeffs, scratch, ebuf, gi);
@@ -382,10 +384,9 @@ __global__ __launch_bounds__(256) void stft_multi_kernel(const float* __restrict
 int stft_multi_launch(const float* audio, int B, int n_samples, int nin, int f0, int f1, float* mag, int c0, int c1, float* spec,
                       const GroupInfo& gi, hipStream_t s, float* zero_ptr, int zero_n) {
     if (nin < 1 || nin > 16) return fail(SAGEN_ERR_SHAPE, "stft: %d input channels", nin);
-    if (f1 <= f0 || 256L * (f1 - 1) + 1024 > n_samples)
-        return fail(SAGEN_ERR_SHAPE, "stft: frames [%d,%d) do not fit %d samples", f0, f1, n_samples);
-    if (spec && (c0 < f0 || c1 > f1 || c1 <= c0)) return fail(SAGEN_ERR_SHAPE, "stft: spec frames must lie in [f0,f1)");
-    int rc = fft_tables_ensure(s);
+    int rc = stft_frames_check(n_samples, f0, f1, spec != nullptr, c0, c1);      // (stft_frames.h: f0 >= 0 and the reference's frame count)
+    if (rc) return rc;
+    rc = fft_tables_ensure(s);
     if (rc) return rc;
     hipLaunchKernelGGL(stft_multi_kernel, dim3(cdiv(f1 - f0, 2) * nin, B, gi.G), dim3(256), 0, s, audio, n_samples, nin, f0, f1, mag, c0, c1,
                        (float2*)spec, zero_ptr, zero_ptr ? zero_n : 0, gi);
@@ -521,10 +522,12 @@ size_t mask_istft_hoa_scratch_bytes(int B, int nout) { return (size_t)B * MASK_N
 
 int mask_istft_hoa_launch(const float* dmask, long dmask_bstride, int dmask_f0, const float* spec, const float* coeffs, int B,
                           int ntracks, int nin, int nout, float* out, float* scratch, const GroupInfo& gi, hipStream_t s) {
-    int rc = fft_tables_ensure(s);
-    if (rc) return rc;
     if (dmask_f0 > MASK_F_LO || dmask_f0 < 0) return fail(SAGEN_ERR_SHAPE, "mask_istft_hoa: dmask must start at frame 0..%d", MASK_F_LO);
     if (nin != 4 || nout != 5) return fail(SAGEN_ERR_UNSUPPORTED, "mask_istft_hoa: (nin, nout) = (%d, %d) (supported: (4, 5), ambi_order 2)", nin, nout);
+    if (ntracks != 16 && ntracks != 32 && ntracks != 64)
+        return fail(SAGEN_ERR_UNSUPPORTED, "mask_istft_hoa: num_sep_tracks=%d (supported: 16, 32, 64)", ntracks);
+    int rc = fft_tables_ensure(s);
+    if (rc) return rc;
     dim3 grid(MASK_NF, B, gi.G);
     if (ntracks == 32)
         hipLaunchKernelGGL((mask_istft_hoa_kernel<32, 4, 5>), grid, dim3(256), 0, s, dmask, dmask_bstride, dmask_f0, (const float2*)spec, coeffs, scratch, gi);

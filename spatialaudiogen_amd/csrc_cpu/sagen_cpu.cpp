@@ -26,6 +26,7 @@
 #include "../csrc/op_entries.h"
 #include "../csrc/op_entries_feed.h"
 #include "../csrc/op_entries_audio.h"
+#include "../csrc/stft_frames.h"
 
 namespace {
 thread_local char g_err[512] = "";
@@ -85,15 +86,15 @@ const char* sagen_last_error(void) { return g_err; }
 
 /* myutils.stft (myutils.py:119-147) + crop + tf.abs (model.py:166-178): frame t = samples [256 t, 256 t + 1024) x periodic Hann */
 int sagen_stft_mag(const float* audio, int batch, int n_samples, int f0, int f1, float* mag, int c0, int c1, float* spec, void*) {
-    if (!audio) return fail(SAGEN_ERR_NULL, "sagen_stft_mag: null audio");
-    const int nframes = (n_samples / 1024 - 1) * 4;
-    if (f0 < 0 || f1 > nframes || (spec && (c0 < 0 || c1 > nframes))) return fail(SAGEN_ERR_SHAPE, "sagen_stft_mag: frames out of range (%d available)", nframes);
+    if (!audio || (!mag && !spec)) return fail(SAGEN_ERR_NULL, "sagen_stft_mag: null argument");
+    if (batch <= 0) return fail(SAGEN_ERR_SHAPE, "sagen_stft_mag: batch=%d", batch);
+    const int rc = sagen::stft_frames_check(n_samples, f0, f1, spec != nullptr, c0, c1);      // the device library's rule (csrc/stft_frames.h)
+    if (rc) return rc;
     std::vector<double> hann(1024);
     for (int n = 0; n < 1024; ++n) hann[n] = (double)(float)(0.5 - 0.5 * std::cos(2.0 * M_PI / 1024 * n));     // (the reference rounds the window to float32, myutils.py:134)
     std::vector<cd> buf(1024);
     for (int b = 0; b < batch; ++b) {
-        const int lo = std::min(mag ? f0 : c0, spec ? c0 : f0), hi = std::max(mag ? f1 : c1, spec ? c1 : f1);
-        for (int t = lo; t < hi; ++t) {
+        for (int t = f0; t < f1; ++t) {                  // (the spec window lies inside [f0, f1))
             const bool want_m = mag && t >= f0 && t < f1, want_s = spec && t >= c0 && t < c1;
             if (!want_m && !want_s) continue;
             for (int n = 0; n < 1024; ++n) buf[n] = cd((double)audio[(size_t)b * n_samples + 256 * t + n] * hann[n], 0.0);
@@ -261,11 +262,16 @@ int sagen_deconv2d(const float* x, int batch, int h, int w, int cin, const float
     return SAGEN_OK;
 }
 
-size_t sagen_mask_istft_mix_scratch_bytes(int) { return 256; }
+size_t sagen_mask_istft_mix_scratch_bytes(int) { return 256; }      /* not used here; asked for as the device library asks for its own */
 /* model.py:326-347 (sigmoid mask x STFT), myutils.istft (myutils.py:181-211: plain average of the four overlaps, no synthesis
  * window), crop [448, 5248), decoder sum (model.py:421-434): out[b, n, o] = sum_k w[b, n / 1600, o, k] s_k[n] + bias */
-int sagen_mask_istft_mix(const float* dmask, const float* spec, const float* coeffs, int batch, int ntracks, float* ambi_yzx, void*, size_t, void*) {
-    if (!dmask || !spec || !coeffs || !ambi_yzx) return fail(SAGEN_ERR_NULL, "sagen_mask_istft_mix: null argument");
+int sagen_mask_istft_mix(const float* dmask, const float* spec, const float* coeffs, int batch, int ntracks, float* ambi_yzx, void* scratch,
+                         size_t scratch_bytes, void*) {
+    if (!dmask || !spec || !coeffs || !ambi_yzx || !scratch) return fail(SAGEN_ERR_NULL, "sagen_mask_istft_mix: null argument");
+    if (batch <= 0) return fail(SAGEN_ERR_SHAPE, "sagen_mask_istft_mix: batch=%d", batch);
+    if (scratch_bytes < sagen_mask_istft_mix_scratch_bytes(batch)) return fail(SAGEN_ERR_WORKSPACE, "sagen_mask_istft_mix: scratch too small");
+    if (ntracks != 16 && ntracks != 32 && ntracks != 64)
+        return fail(SAGEN_ERR_UNSUPPORTED, "mask_istft: num_sep_tracks=%d (supported: 16, 32, 64)", ntracks);
     const int NF = 28;
     std::vector<cd> buf(1024);
     std::vector<double> frames((size_t)NF * 1024), sep(4800);

@@ -39,6 +39,19 @@ def test_forward_sweeps_pass_on_the_cpu_twin(twin):
     assert ' passed' in r.stdout and 'failed' not in r.stdout and 'skipped' not in r.stdout, r.stdout[-500:]
 
 
+def test_spectral_sweeps_pass_on_the_cpu_twin(twin):
+    """The STFT, the mask-iSTFT-mix tail and the BN / pool passes (test_gpu_spectral_ops.py) against the twin: the references, the
+    derived bounds (with the twin's count of roundings), the NaN poisoning of everything a call must not read and the guards are
+    right before a kernel is involved.  The twin has no second-order tail: those cases are deselected by name, and so are the
+    tests of the tail inside the network, which the twin does not have."""
+    env = dict(os.environ, SAGEN_LIB=twin)
+    r = subprocess.run([sys.executable, '-m', 'pytest', os.path.join(ROOT, 'tests', 'test_gpu_spectral_ops.py'), '-m', 'gpu', '-q', '-x',
+                        '-k', 'not hoa and not second_order and not network', '-p', 'no:cacheprovider'], env=env, cwd=ROOT, capture_output=True, text=True,
+                       timeout=1500)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
+    assert ' passed' in r.stdout and 'failed' not in r.stdout and 'skipped' not in r.stdout, r.stdout[-500:]
+
+
 def test_the_twin_is_op_level_only_and_never_a_fallback(twin):
     code = ("import os, sys; sys.path.insert(0, %r)\n"
             "from spatialaudiogen_amd import _lib\n"
