@@ -619,6 +619,51 @@ int64_t sagen_jpeg_encode_max_bytes(int w, int h, int components, int hs, int vs
 int sagen_jpeg_encode(const uint8_t* frames, int n, int w, int h, int components, int hs, int vs, const uint16_t* qtabs, uint8_t* out,
                       int64_t stride, int32_t* sizes, int32_t* status, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- PNG frames: the row filters and a zlib stream -------------------------------------------------------------------------
+ * The reference muxes lossless frames (myutils.py:246-279) and leaves their compression to the host; the overlay writers here
+ * called PIL's save per frame.  These two ops are that step over frames that lie on the device: sagen_png_filter turns frames into
+ * PNG's filtered rows, sagen_deflate turns each frame's rows (any byte strings of one length) into one complete zlib stream.  The
+ * file around it (signature, IHDR, IDAT, IEND and the chunk CRCs) is the caller's (spatialaudiogen_amd/png.py).  8 bit, colour type
+ * 2 or 0, no interlace.  Integer arithmetic end to end: the CPU twin writes the same bytes.
+ *
+ * sagen_png_filter
+ *   frames   [n][h][w][3] uint8 RGB DEVICE for components == 3, [n][h][w] grey for components == 1
+ *   rows     [n][h][1 + w components] uint8 DEVICE: the filter's number, then the filtered row
+ * Each row takes, of None / Sub / Up / Average / Paeth (0..4), the filter whose sum of min(v, 256 - v) over the filtered bytes is
+ * smallest, the lowest number among equals; the row above row 0 is zeros.
+ * Returns: n == 0 SAGEN_OK, nothing touched; SAGEN_ERR_SHAPE for n < 0, w or h < 1; SAGEN_ERR_UNSUPPORTED for components other
+ * than 1 or 3, w or h above 16384, n > 65535; SAGEN_ERR_NULL for a null argument.  A refused call writes nothing.
+ *
+ * sagen_deflate
+ *   data     [n][length] uint8 DEVICE, any alignment; may be null when length == 0
+ *   out      [n][stride] uint8 DEVICE: frame f's stream - 78 01, the deflate blocks, Adler-32 of the input big-endian
+ *   sizes    [n] int32 DEVICE: the bytes frame f's stream needs, filled even when that exceeds stride: then nothing beyond
+ *            out[f][stride - 1] is written, the status is CAPACITY and the frame's bytes are unspecified.  Otherwise nothing
+ *            beyond out[f][sizes[f] - 1] is written
+ *   status   [n] int32 DEVICE: 0 or SAGEN_DEFLATE_ST_CAPACITY; a frame with a non-zero status leaves every other exact
+ * The input is cut into blocks of 16384 bytes (length 0: one empty block).  Inside a block a maximal run of m equal bytes is a
+ * literal followed by matches of distance 1 that cover the other m - 1 bytes in chunks of 258; a last chunk shorter than 3 is
+ * literals; a block's first byte is always a literal.  Each block is the cheapest of stored / fixed / dynamic by bit count, a stored
+ * block counted at its worst padding (42 bits + its bytes), ties to stored, then fixed.  A dynamic block carries a Huffman code
+ * over the 286 literal / length symbols of at most 15 bits, built from the block's histogram (minimum redundancy over symbols
+ * ordered by (count, symbol); lengths above 15 cut and the Kraft sum restored one code at a time), the single distance code 0 of
+ * 1 bit, and sends all 287 lengths plainly through a code-length code of sixteen 4-bit codes: a header of 1222 bits.  No matches at
+ * other distances: general LZ77 is out of scope.
+ * sagen_deflate_max_bytes: the stride that can never be too small, length + 6 + ceil(5.25 blocks) with blocks =
+ * max(1, ceil(length / 16384)) - at most length + 6 blocks + 7; 0 for a length the call would refuse.  sizes[f] never exceeds it.
+ * Returns: n == 0 SAGEN_OK, nothing touched; SAGEN_ERR_SHAPE for n < 0, length < 0, stride < 4 or not a multiple of 4, out / sizes
+ * / status / scratch misaligned (4, 4, 4, 16 bytes); SAGEN_ERR_UNSUPPORTED for n > 65535, length or stride above 2^28;
+ * SAGEN_ERR_NULL for a null argument (data with length > 0); SAGEN_ERR_WORKSPACE for scratch smaller than
+ * sagen_deflate_scratch_bytes(...), which is 0 for arguments the call would refuse.  A refused call writes nothing. */
+enum {
+    SAGEN_DEFLATE_ST_CAPACITY = 1 /* the stream needs more than `stride` bytes; sizes[f] holds what it needs */
+};
+int sagen_png_filter(const uint8_t* frames, int n, int w, int h, int components, uint8_t* rows, void* stream);
+int64_t sagen_deflate_max_bytes(int64_t length);
+size_t sagen_deflate_scratch_bytes(int n, int64_t length, int64_t stride);
+int sagen_deflate(const uint8_t* data, int n, int64_t length, uint8_t* out, int64_t stride, int32_t* sizes, int32_t* status, void* scratch,
+                  size_t scratch_bytes, void* stream);
+
 /* ---- frame batches from a resident clip -------------------------------------------------------------------------------------
  * The reference's reader threads pick the frame of every window, roll it by the yaw rotation, un-code the flow bytes and stack the
  * batch on the host (feeder.py:106-161), and the batch crosses the bus.  sagen_assemble_frames is that step over frames that already

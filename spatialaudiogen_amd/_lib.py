@@ -11,6 +11,7 @@ SAGEN_SEP_NONE, SAGEN_SEP_FREQ_MASK = 0, 1
 SAGEN_SOURCES_MIC, SAGEN_SOURCES_HRIR = 0, 1
 SAGEN_PROJ_ER, SAGEN_PROJ_CUBE, SAGEN_PROJ_EAC, SAGEN_PROJ_VIEW = 0, 1, 2, 3
 SAGEN_JPEG_ENC_ST_CAPACITY, SAGEN_JPEG_ENC_ST_RANGE = 1, 2
+SAGEN_DEFLATE_ST_CAPACITY = 1
 SAGEN_JPEG_STATUS = {1: 'overrun', 2: 'code', 4: 'index', 8: 'marker', 16: 'descriptor', 32: 'table', 64: 'range', 128: 'trailing'}
 
 
@@ -127,6 +128,10 @@ SIGNATURES = {
     'sagen_jpeg_encode_scratch_bytes': (_SZ, [_I] * 6 + [_I64]),
     'sagen_jpeg_encode_max_bytes': (_I64, [_I] * 5),
     'sagen_jpeg_encode': (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I64, _P, _P, _P, _SZ, _P]),
+    'sagen_png_filter': (C.c_int, [_P, _I, _I, _I, _I, _P, _P]),
+    'sagen_deflate_max_bytes': (_I64, [_I64]),
+    'sagen_deflate_scratch_bytes': (_SZ, [_I, _I64, _I64]),
+    'sagen_deflate': (C.c_int, [_P, _I, _I64, _P, _I64, _P, _P, _P, _SZ, _P]),
     'sagen_assemble_frames': (C.c_int, [_P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     'sagen_assemble_audio': (C.c_int, [_P, _I, _I64, _I, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P]),
     'sagen_window_rms': (C.c_int, [_P, _I64, _I, _I, _I64, _I64, _I64, _I64, _P, _P]),

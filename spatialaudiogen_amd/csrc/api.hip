@@ -4,6 +4,7 @@
 #include "op_entries.h"        // the media ops' entry points, shared with the CPU twin; their backends are the launchers of the ops' .hip files
 #include "op_entries_feed.h"   // sagen_assemble_frames, likewise (a header of its own: see its first lines)
 #include "op_entries_audio.h"  // sagen_assemble_audio, likewise
+#include "op_entries_png.h"    // sagen_png_filter, sagen_deflate, likewise
 #include <new>
 #include <cstdlib>
 #include <algorithm>

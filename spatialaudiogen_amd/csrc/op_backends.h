@@ -15,6 +15,7 @@ struct FlowArgs;        // flow_core.h, filled by flow_args_fill
 struct ResampleArgs;    // resample_core.h, filled by resample_args_fill
 struct JpegGeom;        // jpeg_core.h, filled by jpeg_args_check; scratch as jpeg_scratch_layout carves it
 struct JpegEncGeom;     // jpeg_enc_core.h, filled by jpeg_enc_args_check; scratch as jpeg_enc_scratch_layout carves it
+struct DeflateGeom;     // png_core.h, filled by deflate_args_check; scratch as deflate_scratch_layout carves it
 
 int fail(int code, const char* fmt, ...);      // writes the message sagen_last_error() returns, returns code
 
@@ -48,5 +49,7 @@ int run_assemble_frames(const uint8_t* frames, int n_frames, int h, int w, const
 int run_assemble_audio(const void* samples, int sample_type, int64_t n_samples, int channels, const int32_t* lead, const int64_t* read_from,
                        const int32_t* count, const double* rot, int n_out, int size, int t_off, int t_len, float* full, float* mono,
                        float* target, void* stream);
+int run_png_filter(const uint8_t* frames, int n, int w, int h, int components, uint8_t* rows, void* stream);
+int run_deflate(const uint8_t* data, const DeflateGeom& g, uint8_t* out, int32_t* sizes, int32_t* status, void* scratch, void* stream);
 
 }  // namespace sagen

@@ -26,6 +26,7 @@
 #include "../csrc/op_entries.h"
 #include "../csrc/op_entries_feed.h"
 #include "../csrc/op_entries_audio.h"
+#include "../csrc/op_entries_png.h"
 #include "../csrc/stft_frames.h"
 
 namespace {
@@ -811,6 +812,19 @@ int run_assemble_audio(const void* samples, int sample_type, int64_t n_samples, 
     if (sample_type == AUDIO_I16) assemble_audio_rows((const int16_t*)samples, n_samples, channels, lead, read_from, count, rot, n_out, size, t_off, t_len, full, mono, target);
     else if (sample_type == AUDIO_F32) assemble_audio_rows((const float*)samples, n_samples, channels, lead, read_from, count, rot, n_out, size, t_off, t_len, full, mono, target);
     else assemble_audio_rows((const double*)samples, n_samples, channels, lead, read_from, count, rot, n_out, size, t_off, t_len, full, mono, target);
+    return SAGEN_OK;
+}
+
+/* PNG frames (include/sagen.h: sagen_png_filter, sagen_deflate; the host's zlib behind the lossless frames of myutils.py:246-279 in
+ * the reference, PIL's save behind the overlay writers here): row by row, and frame by frame, block by block, chunk by chunk over the
+ * integer core the device uses (csrc/png_core.h: png_filter_host, deflate_host).  The scratch is used as the device uses it. */
+int run_png_filter(const uint8_t* frames, int n, int w, int h, int components, uint8_t* rows, void*) {
+    png_filter_host(frames, n, w, h, components, rows);
+    return SAGEN_OK;
+}
+
+int run_deflate(const uint8_t* data, const DeflateGeom& g, uint8_t* out, int32_t* sizes, int32_t* status, void* scratch, void*) {
+    deflate_host(data, g, out, sizes, status, scratch);
     return SAGEN_OK;
 }
 

@@ -219,13 +219,15 @@ class W2XYZ(object):
         renderer.reset()
         return self._deploy(input_folder, deploy_start, deploy_duration, prefetch, renderer)
 
-    def deploy_and_overlay(self, input_folder, deploy_start=0., deploy_duration=10., overlay=None, renderer=None, prefetch=True):
+    def deploy_and_overlay(self, input_folder, deploy_start=0., deploy_duration=10., overlay=None, renderer=None, prefetch=True, encoder=None):
         """deploy() plus the picture the reference's --save_video --overlay_map path ends in (myutils.py:246-279): every forward
         call's W,Y,Z,X rows and the frames of its windows go through overlay.process (overlay.Overlay) on the device, before the
         copy to the host.  Frame F of the overlay is the frame the feeder selects for output window F (frame_index(t_F,
         video_rate), one per 0.1 s window), read as decoded from <input_folder>/video - also for a model that has no video
         encoder - or from ClipArrays.frames.  Returns (ambi [N, 4] - the bits deploy() returns -, frames [5 (n_maps - 1), H, W, 3]
-        uint8) and, with a renderer, its rendering as a third item."""
+        uint8) and, with a renderer, its rendering as a third item.  With an encoder (png.PngEncoder on the model's device) every forward
+        call's painted frames are encoded before they leave the device, and the frames item is the list of the files' bytes, one
+        complete PNG per frame, in order."""
         if overlay is None or overlay.channels != 4:
             raise ValueError('deploy_and_overlay needs an overlay.Overlay over 4 channels (W,Y,Z,X)')
         if renderer is not None and renderer.channels != 4:
@@ -236,7 +238,7 @@ class W2XYZ(object):
         overlay.reset()
         if renderer is not None:
             renderer.reset()
-        ambi, rendered, painted = self._deploy(input_folder, deploy_start, deploy_duration, prefetch, renderer, overlay)
+        ambi, rendered, painted = self._deploy(input_folder, deploy_start, deploy_duration, prefetch, renderer, overlay, encoder)
         return (ambi, painted) if renderer is None else (ambi, painted, rendered)
 
     def _overlay_frames(self, source, reader):
@@ -250,7 +252,7 @@ class W2XYZ(object):
         jpgs = JpgFrames(os.path.join(source, 'video'), rate)
         return lambda t: jpgs.frame(frame_index(t, rate))
 
-    def _deploy(self, input_folder, deploy_start, deploy_duration, prefetch, renderer, overlay=None):
+    def _deploy(self, input_folder, deploy_start, deploy_duration, prefetch, renderer, overlay=None, encoder=None):
         import torch
         from . import ops
         from .feeder import BatchPrefetcher, frames_to_float
@@ -259,7 +261,7 @@ class W2XYZ(object):
         reader = self._reader(input_folder, deploy_start, deploy_duration, frames=not on_device)
         if not reader.chunks_t:
             empty = np.zeros((0, 4), np.float32), np.zeros((0, renderer.outputs if renderer else 0), np.float32)
-            return empty if overlay is None else empty + (np.zeros((0, 0, 0, 3), np.uint8),)
+            return empty if overlay is None else empty + ([] if encoder is not None else np.zeros((0, 0, 0, 3), np.uint8),)
         dt = reader.chunks_t[0] - deploy_start                           # deploy.py:106-107
         reader.chunks_t = [t - dt for t in reader.chunks_t]
         use_v, use_f = VIDEO in p.encoders, FLOW in p.encoders
@@ -354,7 +356,11 @@ class W2XYZ(object):
                     frames = vdev.batch(idx)[:, 0]
                 else:
                     frames = torch.cat([torch.as_tensor(b['frames']) for b in bs], 0).to(m.device, non_blocking=True)
-                painted.append(overlay.process(valid, frames).cpu().numpy())
+                done = overlay.process(valid, frames)
+                if encoder is not None:     # the files instead of the pixels: compressed before they cross the bus
+                    painted.extend(encoder.encode(done, first=len(painted)) if done.shape[0] else [])
+                else:
+                    painted.append(done.cpu().numpy())
             for r in rows:
                 outs.append(r.cpu().numpy())
 
@@ -376,6 +382,8 @@ class W2XYZ(object):
         result = np.concatenate(outs, 0), (np.concatenate(rendered, 0) if renderer is not None else None)
         if overlay is None:
             return result
+        if encoder is not None:
+            return result + (painted,)
         painted = [f for f in painted if f.shape[0]]
         return result + (np.concatenate(painted, 0) if painted else np.zeros((0, 0, 0, 3), np.uint8),)
 
@@ -423,6 +431,9 @@ def parse_arguments(argv=None):
                         help='paint the sound-direction heat map over the frames of <input_folder>/video and write them here as %%06d.png (overlay.py)')
     parser.add_argument('--save_maps', default=None, metavar='FILE.npz', help='with --overlay_dir: also write the raw power maps')
     parser.add_argument('--overwrite', action='store_true', help='replace frames already in --overlay_dir')
+    parser.add_argument('--encode', default='host', choices=['host', 'device'],
+                        help='with --overlay_dir: where the frames are compressed: host (PIL, one thread) or device (png.py: the files\' bytes come '
+                             'back instead of the pixels; other bytes, the same pixels)')
     args = parser.parse_args(argv)
     if args.deploy_duration <= 0:
         args.deploy_duration = None
@@ -430,6 +441,8 @@ def parse_arguments(argv=None):
         parser.error('--render and --render_fn come together')
     if args.save_maps and not args.overlay_dir:
         parser.error('--save_maps needs --overlay_dir')
+    if args.encode == 'device' and not args.overlay_dir:
+        parser.error('--encode device needs --overlay_dir')
     return args
 
 
@@ -453,7 +466,11 @@ def main(argv=None):
     painted = None
     if args.overlay_dir:
         ov = overlay.Overlay(4, audio_rate=params.audio_rate, video_rate=params.video_rate)
-        res = model.deploy_and_overlay(args.input_folder, args.deploy_start, args.deploy_duration, ov, renderer)
+        encoder = None
+        if args.encode == 'device':
+            from .png import PngEncoder
+            encoder = PngEncoder(ov.device)
+        res = model.deploy_and_overlay(args.input_folder, args.deploy_start, args.deploy_duration, ov, renderer, encoder=encoder)
         ambi_pred, painted = res[0], res[1]
         rendered = res[2] if renderer is not None else None
     elif renderer is None:
@@ -468,10 +485,17 @@ def main(argv=None):
         save_wav(args.render_fn, rendered, model.params.audio_rate)
         print('wrote %s: %d samples x %d channels (%s)' % (args.render_fn, rendered.shape[0], rendered.shape[1], args.render))
     if painted is not None:
-        overlay.save_frames(args.overlay_dir, painted)
+        if args.encode == 'device':
+            for i, data in enumerate(painted):
+                with open(os.path.join(args.overlay_dir, '%06d.png' % i), 'wb') as f:
+                    f.write(data)
+            count = len(painted)
+        else:
+            overlay.save_frames(args.overlay_dir, painted)
+            count = painted.shape[0]
         if args.save_maps:
             np.savez(args.save_maps, maps=ov.maps().cpu().numpy())
-        print('wrote %d frames to %s (%d maps of %dx%d)' % (painted.shape[0], args.overlay_dir, ov.maps().shape[0], ov.map_shape[0], ov.map_shape[1]))
+        print('wrote %d frames to %s (%d maps of %dx%d)' % (count, args.overlay_dir, ov.maps().shape[0], ov.map_shape[0], ov.map_shape[1]))
 
 
 if __name__ == '__main__':

@@ -2,7 +2,7 @@
 (myutils.gen_360video(overlay_map=True), myutils.py:246-279, over SphericalAmbisonicsVisualizer, pyutils/ambisonics/
 distance.py:16-59).
 
-    python -m spatialaudiogen_amd.overlay IN_AMBIX.wav FRAMES_DIR OUT_DIR [--angular_res 5] [--save_maps FILE.npz] [--overwrite]
+    python -m spatialaudiogen_amd.overlay IN_AMBIX.wav FRAMES_DIR OUT_DIR [--angular_res 5] [--save_maps FILE.npz] [--overwrite] [--encode {host,device}]
 
 IN_AMBIX.wav holds 4 or 9 channels (ACN / SN3D, orders 1 and 2), FRAMES_DIR the frames %06d.jpg at 10 per second; OUT_DIR receives
 %06d.png.  What is computed (include/sagen.h: sagen_power_map_windows, sagen_overlay_blend; csrc/overlay.hip):
@@ -201,6 +201,7 @@ def parse_arguments(argv=None):
     parser.add_argument('--gpu', type=int, default=0, help='GPU id')
     parser.add_argument('--block', type=int, default=50, help='frames per device call')
     parser.add_argument('--decode', default='host', choices=['host', 'device'], help="where the input frames are decoded: host (PIL, one thread) or device (jpeg.py: the files' bytes go to the device; same pixels)")
+    parser.add_argument('--encode', default='host', choices=['host', 'device'], help="where the output frames are compressed: host (PIL, one thread) or device (png.py: the files' bytes come back instead of the pixels; other bytes, the same pixels)")
     return parser.parse_args(argv)
 
 
@@ -230,11 +231,17 @@ def main(argv=None):
     if args.decode == 'device':
         from .jpeg import JpegDecoder
         decoder = JpegDecoder(ov.device)
+    if args.encode == 'device':
+        from .png import PngEncoder, save_frames_device
+        encoder = PngEncoder(ov.device)
     for i in range(0, len(names), args.block):
         block = names[i:i + args.block]
         frames = decoder.decode(block) if args.decode == 'device' else torch.as_tensor(load_frames(block)).to(ov.device)
-        out = ov.process(None, frames).cpu().numpy()
-        save_frames(args.output_dir, out, written)
+        out = ov.process(None, frames)
+        if args.encode == 'device':
+            save_frames_device(args.output_dir, out, written, encoder)
+        else:
+            save_frames(args.output_dir, out.cpu().numpy(), written)
         written += out.shape[0]
     if args.save_maps:
         np.savez(args.save_maps, maps=ov.maps().cpu().numpy())
