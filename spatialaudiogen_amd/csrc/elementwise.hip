@@ -288,28 +288,35 @@ int nosep_mix_multi_launch(const float* audio, const float* coeffs, float* out, 
 // rms[p] = sqrt(mean_t (sum_c ambi[t,c] * sh[p,c])^2).  Expanded as the 4x4 second-moment matrix
 // S = sum_t ambi^T ambi (one wavefront-reduced pass over the audio, DPP/shuffle tree), then
 // rms[p] = sqrt(sh[p] S sh[p]^T / T) — the audio is read exactly once whatever the mesh size.
-__global__ __launch_bounds__(256) void power_moments_kernel(const float4* __restrict__ ambi, long T, double* __restrict__ S) {
-    float m[10];
-#pragma unroll
-    for (int k = 0; k < 10; ++k) m[k] = 0.f;
-    for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < T; t += (long)gridDim.x * 256) {
-        const float4 a = ambi[t];
-        m[0] += a.x * a.x; m[1] += a.x * a.y; m[2] += a.x * a.z; m[3] += a.x * a.w;
-        m[4] += a.y * a.y; m[5] += a.y * a.z; m[6] += a.y * a.w;
-        m[7] += a.z * a.z; m[8] += a.z * a.w; m[9] += a.w * a.w;
-    }
-    __shared__ float red[4][10];
+// The ten moments are summed in fp64 from the first addition on (products of float32 values are exact there): the quadratic form
+// cancels to zero opposite a plane wave, and float32 sums left 1e-4 of the map's maximum at that null
+// ("The evaluation side op by op"; overlay_moments_kernel sums the same way).
+__device__ __forceinline__ void moments_add(double (&m)[10], const float4 a4) {
+    const double a[4] = {a4.x, a4.y, a4.z, a4.w};
+    m[0] += a[0] * a[0]; m[1] += a[0] * a[1]; m[2] += a[0] * a[2]; m[3] += a[0] * a[3];
+    m[4] += a[1] * a[1]; m[5] += a[1] * a[2]; m[6] += a[1] * a[3];
+    m[7] += a[2] * a[2]; m[8] += a[2] * a[3]; m[9] += a[3] * a[3];
+}
+
+// sum of the 256 threads' moments, in one fixed order (wave butterflies, then the four waves): moment threadIdx.x in threads 0..9
+__device__ __forceinline__ double moments_block_sum(const double (&m)[10]) {
+    __shared__ double red[4][10];
 #pragma unroll
     for (int k = 0; k < 10; ++k) {
-        float v = m[k];
-        v = wave_sum(v);
+        const double v = wave_sum_f64(m[k]);
         if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
     }
     __syncthreads();
-    if (threadIdx.x < 10) {
-        const double v = (double)red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
-        atomicAdd(&S[threadIdx.x], v);
-    }
+    return threadIdx.x < 10 ? red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x] : 0.0;
+}
+
+__global__ __launch_bounds__(256) void power_moments_kernel(const float4* __restrict__ ambi, long T, double* __restrict__ S) {
+    double m[10];
+#pragma unroll
+    for (int k = 0; k < 10; ++k) m[k] = 0.0;
+    for (long t = (long)blockIdx.x * 256 + threadIdx.x; t < T; t += (long)gridDim.x * 256) moments_add(m, ambi[t]);
+    const double v = moments_block_sum(m);
+    if (threadIdx.x < 10) atomicAdd(&S[threadIdx.x], v);
 }
 
 __global__ __launch_bounds__(256) void power_map_kernel(const double* __restrict__ S, double inv_T, const float4* __restrict__ sh,
@@ -329,25 +336,12 @@ __global__ __launch_bounds__(256) void power_map_kernel(const double* __restrict
 // distance.py:41-59: one RMS map per 0.1 s window): block b reduces the second moments of chunk b (no atomics).
 __global__ __launch_bounds__(256) void power_moments_batched_kernel(const float4* __restrict__ ambi, long T, double* __restrict__ S) {
     const float4* a4 = ambi + (long)blockIdx.x * T;
-    float m[10];
+    double m[10];
 #pragma unroll
-    for (int k = 0; k < 10; ++k) m[k] = 0.f;
-    for (long t = threadIdx.x; t < T; t += 256) {
-        const float4 a = a4[t];
-        m[0] += a.x * a.x; m[1] += a.x * a.y; m[2] += a.x * a.z; m[3] += a.x * a.w;
-        m[4] += a.y * a.y; m[5] += a.y * a.z; m[6] += a.y * a.w;
-        m[7] += a.z * a.z; m[8] += a.z * a.w; m[9] += a.w * a.w;
-    }
-    __shared__ float red[4][10];
-#pragma unroll
-    for (int k = 0; k < 10; ++k) {
-        float v = m[k];
-        v = wave_sum(v);
-        if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
-    }
-    __syncthreads();
-    if (threadIdx.x < 10)
-        S[(long)blockIdx.x * 10 + threadIdx.x] = (double)red[0][threadIdx.x] + red[1][threadIdx.x] + red[2][threadIdx.x] + red[3][threadIdx.x];
+    for (int k = 0; k < 10; ++k) m[k] = 0.0;
+    for (long t = threadIdx.x; t < T; t += 256) moments_add(m, a4[t]);
+    const double v = moments_block_sum(m);
+    if (threadIdx.x < 10) S[(long)blockIdx.x * 10 + threadIdx.x] = v;
 }
 
 __global__ __launch_bounds__(256) void power_map_batched_kernel(const double* __restrict__ Sall, double inv_T, const float4* __restrict__ sh,

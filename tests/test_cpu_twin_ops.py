@@ -52,6 +52,18 @@ def test_spectral_sweeps_pass_on_the_cpu_twin(twin):
     assert ' passed' in r.stdout and 'failed' not in r.stdout and 'skipped' not in r.stdout, r.stdout[-500:]
 
 
+def test_eval_sweeps_pass_on_the_cpu_twin(twin):
+    """The power-map and EMD cases of test_gpu_eval_ops.py against the twin: its power maps evaluate the definition in double and its
+    EMD is the serial core itself, so the references, the case lists, the bounds and the guards are right before a kernel is involved.
+    The twin has no sagen_eval_metrics and no sagen_eval_mel_env: those tests are deselected by name."""
+    env = dict(os.environ, SAGEN_LIB=twin)
+    r = subprocess.run([sys.executable, '-m', 'pytest', os.path.join(ROOT, 'tests', 'test_gpu_eval_ops.py'), '-m', 'gpu', '-q', '-x',
+                        '-k', 'not eval_metrics and not eval_mel_env', '-p', 'no:cacheprovider'], env=env, cwd=ROOT, capture_output=True, text=True,
+                       timeout=1500)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-1000:]
+    assert ' passed' in r.stdout and 'failed' not in r.stdout and 'skipped' not in r.stdout, r.stdout[-500:]
+
+
 def test_the_twin_is_op_level_only_and_never_a_fallback(twin):
     code = ("import os, sys; sys.path.insert(0, %r)\n"
             "from spatialaudiogen_amd import _lib\n"
