@@ -619,6 +619,58 @@ int64_t sagen_jpeg_encode_max_bytes(int w, int h, int components, int hs, int vs
 int sagen_jpeg_encode(const uint8_t* frames, int n, int w, int h, int components, int hs, int vs, const uint16_t* qtabs, uint8_t* out,
                       int64_t stride, int32_t* sizes, int32_t* status, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- baseline JPEG encode with restart intervals ----------------------------------------------------------------------------
+ * sagen_jpeg_decode runs one lane per restart segment, so a file without restart interval is decoded by one lane.
+ * sagen_jpeg_encode_rst is sagen_jpeg_encode with a restart interval: every argument, status bit and return code as there, plus
+ *   restart_interval  MCUs per segment, as the DRI segment of the header names it (the caller's, FF DD 00 04 RRRR directly in
+ *                     front of SOS); 0: none, and then the call writes exactly what sagen_jpeg_encode writes; 1..65535 are
+ *                     accepted, anything else is SAGEN_ERR_UNSUPPORTED.  An interval of at least the frame's MCU count writes
+ *                     no marker
+ * The stream is the one libjpeg writes for the same interval (PIL's save with restart_marker_blocks=R, optimize=False).  In front
+ * of MCU number k R for k >= 1, never behind the last MCU: the bit buffer is filled with ones to a byte boundary (nothing where it
+ * stands on one); that byte is followed by 00 if it comes out as FF, like any other; FF D0+((k-1) & 7) follows and is NOT stuffed;
+ * every component's DC prediction goes back to 0, so the DC difference of a segment's first blocks is against 0 (a luma block
+ * wholly outside the image still repeats the DC in front of it: an MCU's first block is never one).  The end of the scan is
+ * unchanged.  No stage walks a frame: the bit positions come from a segmented prefix sum, each segment starting on a byte, and
+ * the markers are placed by the pass that stuffs the bytes.
+ * sagen_jpeg_encode_rst_max_bytes: the stride that can never be too small.  With S = ceil(MCUs / R) segments (1 for R = 0 or
+ * R >= MCUs) it is sagen_jpeg_encode_max_bytes + 4 (S - 1): each fill moves the unstuffed bytes up by less than one per segment
+ * (ceil(a / 8) + ceil(b / 8) <= ceil((a + b) / 8) + 1), so by at most S - 1 in all, a fill byte that is FF included; stuffing can
+ * double those; the S - 1 markers of two bytes are not stuffed.  sizes[f] never exceeds it.  0 for a geometry or an interval
+ * outside the scope.  sagen_jpeg_encode_rst_scratch_bytes likewise; for restart_interval 0 it is
+ * sagen_jpeg_encode_scratch_bytes. */
+size_t sagen_jpeg_encode_rst_scratch_bytes(int n, int w, int h, int components, int hs, int vs, int restart_interval, int64_t stride);
+int64_t sagen_jpeg_encode_rst_max_bytes(int w, int h, int components, int hs, int vs, int restart_interval);
+int sagen_jpeg_encode_rst(const uint8_t* frames, int n, int w, int h, int components, int hs, int vs, int restart_interval,
+                          const uint16_t* qtabs, uint8_t* out, int64_t stride, int32_t* sizes, int32_t* status, void* scratch,
+                          size_t scratch_bytes, void* stream);
+
+/* ---- re-segmenting existing JPEG files: a lossless transcode ------------------------------------------------------------------
+ * sagen_jpeg_transcode gives files that exist (ffmpeg's extraction, PIL's saves) a restart interval without computing a pixel.
+ * Inputs as sagen_jpeg_decode takes them - bytes, frames, segments, hufftabs and the geometry; no qtabs (the descriptors' qtab
+ * indices only have to be non-negative), no pixels - plus restart_interval as sagen_jpeg_encode_rst takes it.  The decoder's table,
+ * check and entropy stages fill int16 coefficients, a kernel puts them from natural into zigzag order, and the entropy half of
+ * sagen_jpeg_encode_rst codes THOSE coefficients with the standard tables (Annex K.3 - K.6) and the new interval.  Every block the
+ * source scan holds is coded as it stands, the luma blocks of an MCU that lie wholly outside the image included: the pixel
+ * encoder's rule for such blocks does not apply, the DC prediction is the component's previous block in the segment.  The
+ * coefficients of the written scan equal those of the source; header and FF D9 are the caller's (spatialaudiogen_amd/jpeg.py).
+ *   out, sizes  as sagen_jpeg_encode: [n][stride] and the bytes each stream needs, filled even where that exceeds stride
+ *   status      [n] int32 DEVICE: the decoder's SAGEN_JPEG_ST_* bits in bits 0..7, the encoder's SAGEN_JPEG_ENC_ST_* bits shifted
+ *               left by 8 (a DC difference that the new segmentation pushes above category 11 is RANGE << 8).  A frame with a
+ *               non-zero status has unspecified bytes and leaves every other frame exact
+ * sagen_jpeg_transcode_max_bytes: 2 ceil(blocks 1660 / 8) + 2 + 4 (S - 1) for S segments - a file's block can hold what the
+ * tables allow (11 + 11 bits of DC, 63 x (16 + 10) of AC), not only what 8-bit samples reach; the terms for the segments as above.
+ * Returns: as sagen_jpeg_decode and sagen_jpeg_encode_rst for the arguments each shares (n == 0 SAGEN_OK, nothing touched; a null
+ * argument SAGEN_ERR_NULL; shapes, alignments and the scope as there); SAGEN_ERR_WORKSPACE for scratch smaller than
+ * sagen_jpeg_transcode_scratch_bytes(...), which is 0 for a call that would be refused.  A refused call writes nothing. */
+size_t sagen_jpeg_transcode_scratch_bytes(int n, int w, int h, int components, int hs, int vs, int n_hufftabs, int restart_interval,
+                                          int64_t stride);
+int64_t sagen_jpeg_transcode_max_bytes(int w, int h, int components, int hs, int vs, int restart_interval);
+int sagen_jpeg_transcode(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_frame* frames, int n, const int32_t* segments,
+                         int n_segments, const uint8_t* hufftabs, int n_hufftabs, int w, int h, int components, int hs, int vs,
+                         int restart_interval, uint8_t* out, int64_t stride, int32_t* sizes, int32_t* status, void* scratch,
+                         size_t scratch_bytes, void* stream);
+
 /* ---- PNG frames: the row filters and a zlib stream -------------------------------------------------------------------------
  * The reference muxes lossless frames (myutils.py:246-279) and leaves their compression to the host; the overlay writers here
  * called PIL's save per frame.  These two ops are that step over frames that lie on the device: sagen_png_filter turns frames into

@@ -128,6 +128,12 @@ SIGNATURES = {
     'sagen_jpeg_encode_scratch_bytes': (_SZ, [_I] * 6 + [_I64]),
     'sagen_jpeg_encode_max_bytes': (_I64, [_I] * 5),
     'sagen_jpeg_encode': (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I64, _P, _P, _P, _SZ, _P]),
+    'sagen_jpeg_encode_rst_scratch_bytes': (_SZ, [_I] * 7 + [_I64]),
+    'sagen_jpeg_encode_rst_max_bytes': (_I64, [_I] * 6),
+    'sagen_jpeg_encode_rst': (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I64, _P, _P, _P, _SZ, _P]),
+    'sagen_jpeg_transcode_scratch_bytes': (_SZ, [_I] * 8 + [_I64]),
+    'sagen_jpeg_transcode_max_bytes': (_I64, [_I] * 6),
+    'sagen_jpeg_transcode': (C.c_int, [_P, _I64, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I64, _P, _P, _P, _SZ, _P]),
     'sagen_png_filter': (C.c_int, [_P, _I, _I, _I, _I, _P, _P]),
     'sagen_deflate_max_bytes': (_I64, [_I64]),
     'sagen_deflate_scratch_bytes': (_SZ, [_I, _I64, _I64]),

@@ -5,6 +5,7 @@
 #include "op_entries_feed.h"   // sagen_assemble_frames, likewise (a header of its own: see its first lines)
 #include "op_entries_audio.h"  // sagen_assemble_audio, likewise
 #include "op_entries_png.h"    // sagen_png_filter, sagen_deflate, likewise
+#include "op_entries_jpeg_rst.h"   // sagen_jpeg_encode_rst, likewise
 #include <new>
 #include <cstdlib>
 #include <algorithm>

@@ -97,6 +97,23 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_pixel_kernel(const uint8_t*
 
 }  // namespace
 
+// The first three stages: the tables, the check and the entropy decode into the natural-order coefficients (zeroed here).
+// sagen_jpeg_transcode (jpeg_enc.hip) stops behind them; n_qtabs bounds the descriptors' table indices and nothing else.
+int jpeg_coefficients_launch(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_frame* frames, const int32_t* segments, int n_segments,
+                             int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, const JpegGeom& g, JpegHuff* huff, int16_t* coef, int32_t* status,
+                             void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
+    SAGEN_HIP_CHECK(hipMemsetAsync(coef, 0, (size_t)g.n * g.blocks * 64 * sizeof(int16_t), s));
+    hipLaunchKernelGGL(jpeg_tables_kernel, dim3(cdiv(n_hufftabs, 64)), dim3(64), 0, s, hufftabs, huff, n_hufftabs);
+    hipLaunchKernelGGL(jpeg_check_kernel, dim3(cdiv(g.n, 64)), dim3(64), 0, s, frames, segments, n_segments, total_bytes, n_qtabs, n_hufftabs, g,
+                       huff, status);
+    int lanes = cdiv(n_segments, JPEG_ENTROPY_WAVES);
+    lanes = lanes > 64 ? 64 : lanes;
+    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(cdiv(n_segments, lanes)), dim3(64), 0, s, bytes, frames, segments, n_segments, lanes, g, huff,
+                       coef, status);
+    return SAGEN_OK;
+}
+
 int run_jpeg_decode(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_frame* frames, const int32_t* segments, int n_segments,
                     const uint16_t* qtabs, int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, const JpegGeom& g, uint8_t* out,
                     int32_t* status, void* scratch, void* stream) {
@@ -105,14 +122,8 @@ int run_jpeg_decode(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_
     JpegHuff* huff = (JpegHuff*)((char*)scratch + lay.huff);
     int16_t* coef = (int16_t*)((char*)scratch + lay.coef);
     uint8_t* planes = (uint8_t*)scratch + lay.planes;
-    SAGEN_HIP_CHECK(hipMemsetAsync(coef, 0, lay.planes - lay.coef, s));
-    hipLaunchKernelGGL(jpeg_tables_kernel, dim3(cdiv(n_hufftabs, 64)), dim3(64), 0, s, hufftabs, huff, n_hufftabs);
-    hipLaunchKernelGGL(jpeg_check_kernel, dim3(cdiv(g.n, 64)), dim3(64), 0, s, frames, segments, n_segments, total_bytes, n_qtabs, n_hufftabs, g,
-                       huff, status);
-    int lanes = cdiv(n_segments, JPEG_ENTROPY_WAVES);
-    lanes = lanes > 64 ? 64 : lanes;
-    hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(cdiv(n_segments, lanes)), dim3(64), 0, s, bytes, frames, segments, n_segments, lanes, g, huff,
-                       coef, status);
+    const int rc = jpeg_coefficients_launch(bytes, total_bytes, frames, segments, n_segments, n_qtabs, hufftabs, n_hufftabs, g, huff, coef, status, stream);
+    if (rc != SAGEN_OK) return rc;
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3(cdiv((long)g.n * g.blocks, JPEG_THREADS)), dim3(JPEG_THREADS), 0, s, coef, frames, qtabs, g, status,
                        planes);
     hipLaunchKernelGGL(jpeg_pixel_kernel, dim3(cdiv((long)g.w * g.h, JPEG_THREADS), g.n < JPEG_GRID_FRAMES ? g.n : JPEG_GRID_FRAMES),

@@ -27,6 +27,8 @@ struct JpegEncGeom {
     int blocks;                                    // per frame, dummies included
     long long stride;                              // bytes per row of out
     long long cap;                                 // bytes per frame of the unstuffed stream in scratch: its bound, a multiple of 16
+    int seg_blocks, nseg;                          // blocks per restart segment and segments per frame; without markers: blocks, 1
+    int all_real;                                  // sagen_jpeg_transcode: the coefficients are a file's, every block is coded as it stands
 };
 
 // the four standard tables (Annex K.3 - K.6) as an encoder wants them: symbol -> (code << 8) | length, 0: no such symbol
@@ -86,6 +88,7 @@ constexpr JpegEncHuff jpeg_enc_huff_make() {
 
 struct JpegEncScratch {
     size_t coef, counts, tiles, tile_at, frame_bits, qok, ff_tiles, ff_at, stream, total;   // byte offsets of the regions
+    size_t seg_pad, seg_at;                        // behind the stream, only where nseg > 1
     int scan_tiles;                                // tiles of JPEG_ENC_SCAN_TILE blocks per frame
     long long ff_tiles_n;                          // tiles of JPEG_ENC_FF_TILE unstuffed bytes per frame
 };
@@ -93,6 +96,11 @@ constexpr int JPEG_ENC_SCAN_TILE = 256;            // blocks per workgroup of th
 constexpr int JPEG_ENC_FF_TILE = 4096;             // unstuffed bytes per workgroup of the stuffing scan (256 threads x 16 bytes)
 
 inline long long jpeg_enc_max_bytes(long long blocks) { return 2 * ((blocks * JPEG_ENC_BLOCK_BITS + 7) / 8) + 2; }
+
+// With nseg restart segments: each segment is filled to a byte of its own, and ceil(a / 8) + ceil(b / 8) <= ceil((a + b) / 8) + 1, so
+// the unstuffed bytes grow by at most nseg - 1; stuffing can double them (a fill byte that comes out as FF included); the nseg - 1
+// markers of two bytes are not stuffed.
+inline long long jpeg_enc_rst_max_bytes(long long blocks, long long nseg) { return jpeg_enc_max_bytes(blocks) + 4 * (nseg - 1); }
 
 inline int jpeg_enc_geom_fill(JpegEncGeom& g, int n, int w, int h, int ncomp, int hs, int vs, long long stride, const char** why) {
     JpegGeom d;
@@ -105,6 +113,18 @@ inline int jpeg_enc_geom_fill(JpegEncGeom& g, int n, int w, int h, int ncomp, in
     g.wb = (w + 7) / 8, g.hb = (h + 7) / 8;
     g.stride = stride;
     g.cap = (((long long)g.blocks * JPEG_ENC_CODE_BITS + 7) / 8 + 15) / 16 * 16;
+    g.seg_blocks = g.blocks, g.nseg = 1, g.all_real = 0;
+    return SAGEN_OK;
+}
+
+// the restart interval of sagen_jpeg_encode_rst on a filled g: an interval that reaches over the whole frame writes no marker
+inline int jpeg_enc_geom_rst(JpegEncGeom& g, int restart_interval, const char** why) {
+    if (restart_interval < 0 || restart_interval > 65535) return *why = "restart_interval outside 0..65535", SAGEN_ERR_UNSUPPORTED;
+    const long long mcus = (long long)g.mcus_x * g.mcus_y;
+    if (restart_interval == 0 || restart_interval >= mcus) return SAGEN_OK;
+    g.seg_blocks = restart_interval * g.bpm;
+    g.nseg = (int)((mcus + restart_interval - 1) / restart_interval);
+    g.cap = (((long long)g.blocks * JPEG_ENC_CODE_BITS + 7) / 8 + (g.nseg - 1) + 15) / 16 * 16;     // a fill of up to 7 bits per segment
     return SAGEN_OK;
 }
 
@@ -125,13 +145,21 @@ inline JpegEncScratch jpeg_enc_scratch_layout(const JpegEncGeom& g) {
     s.ff_at = up(s.ff_tiles + (size_t)g.n * s.ff_tiles_n * sizeof(int32_t));       // int64 [n][ff_tiles_n]: FF bytes before the tile
     s.stream = up(s.ff_at + (size_t)g.n * s.ff_tiles_n * sizeof(int64_t));         // uint8 [n][cap]
     s.total = s.stream + (size_t)g.n * g.cap;
+    s.seg_pad = s.seg_at = s.total;
+    if (g.nseg > 1) {
+        s.seg_at = s.seg_pad + (size_t)g.n * g.nseg * sizeof(int64_t);             // int64 [n][nseg]: fill bits in front of the segment
+        s.total = s.seg_at + (size_t)g.n * g.nseg * sizeof(int64_t);               // int64 [n][nseg]: its first unstuffed byte
+    }
     return s;
 }
 
 // the checks of sagen_jpeg_encode that need no look at device memory; g is filled when SAGEN_OK comes back
 inline int jpeg_enc_args_check(JpegEncGeom& g, const void* frames, int n, int w, int h, int ncomp, int hs, int vs, const void* qtabs, const void* out,
-                               long long stride, const void* sizes, const void* status, const void* scratch, size_t scratch_bytes, const char** why) {
-    const int rc = jpeg_enc_geom_fill(g, n, w, h, ncomp, hs, vs, stride, why);
+                               long long stride, const void* sizes, const void* status, const void* scratch, size_t scratch_bytes, const char** why,
+                               int restart_interval = 0) {
+    int rc = jpeg_enc_geom_fill(g, n, w, h, ncomp, hs, vs, stride, why);
+    if (rc != SAGEN_OK) return rc;
+    rc = jpeg_enc_geom_rst(g, restart_interval, why);
     if (rc != SAGEN_OK) return rc;
     if (!frames || !qtabs || !out || !sizes || !status || !scratch) return *why = "null argument", SAGEN_ERR_NULL;
     if ((uintptr_t)out % 4 || (uintptr_t)sizes % 4 || (uintptr_t)status % 4 || (uintptr_t)qtabs % 2 || (uintptr_t)scratch % 16)
@@ -146,7 +174,7 @@ JPEG_FN void jpeg_enc_block_place(const JpegEncGeom& g, int b, int& comp, int& b
     const int mcu = b / g.bpm, j = b % g.bpm, my = mcu / g.mcus_x, mx = mcu % g.mcus_x, luma = g.hs * g.vs;     // (grey: hs = vs = 1)
     if (j < luma) {
         comp = 0, by = my * g.vs + j / g.hs, bx = mx * g.hs + j % g.hs;
-        dummy = by >= g.hb || bx >= g.wb;
+        dummy = !g.all_real && (by >= g.hb || bx >= g.wb);
     } else {
         comp = j - luma + 1, by = my, bx = mx, dummy = false;
     }
@@ -154,7 +182,7 @@ JPEG_FN void jpeg_enc_block_place(const JpegEncGeom& g, int b, int& comp, int& b
 
 // the block whose DC predicts block b's: the nearest earlier block of its component that is no dummy (a dummy repeats the DC in
 // front of it, so it changes no prediction), or -1 at the start of the frame.  At most hs vs steps: block 0 of an MCU is never a dummy.
-JPEG_FN int jpeg_enc_pred_block(const JpegEncGeom& g, int b) {
+JPEG_FN int jpeg_enc_pred_block_frame(const JpegEncGeom& g, int b) {
     const int luma = g.hs * g.vs, j = b % g.bpm;
     if (j >= luma) return b >= g.bpm ? b - g.bpm : -1;
     int p = b;
@@ -167,6 +195,13 @@ JPEG_FN int jpeg_enc_pred_block(const JpegEncGeom& g, int b) {
         if (!dummy) return p;
     }
     return -1;                                                       // (not reached)
+}
+
+// the same inside restart segments: a prediction does not reach into the segment in front (a segment starts with an MCU, whose
+// block 0 is no dummy, so the dummies of a segment still find the DC they repeat)
+JPEG_FN int jpeg_enc_pred_block(const JpegEncGeom& g, int b) {
+    const int p = jpeg_enc_pred_block_frame(g, b);
+    return g.nseg > 1 && p >= 0 && p / g.seg_blocks != b / g.seg_blocks ? -1 : p;
 }
 
 // ---- samples ---------------------------------------------------------------------------------------------------------------------
@@ -312,18 +347,27 @@ inline void jpeg_enc_put(JpegEncWriter& wr, uint64_t bits, int len) {
 }
 
 // sagen_jpeg_encode on host pointers, after jpeg_enc_args_check: frame by frame, block by block, bit by bit; the scratch is not used
-inline void jpeg_encode_host(const uint8_t* frames, const JpegEncGeom& g, const uint16_t* qtabs, uint8_t* out, int32_t* sizes, int32_t* status) {
+// With `coef` ([n][blocks][64] int16, zigzag order: sagen_jpeg_transcode) the blocks are taken from there, frames and qtabs are not read.
+inline void jpeg_encode_host(const uint8_t* frames, const JpegEncGeom& g, const uint16_t* qtabs, uint8_t* out, int32_t* sizes, int32_t* status,
+                             const int16_t* coef = nullptr) {
     static const JpegEncHuff huff = jpeg_enc_huff_make();
-    const bool qok = jpeg_enc_qtabs_ok(qtabs, g.ncomp);
+    const bool qok = coef || jpeg_enc_qtabs_ok(qtabs, g.ncomp);
     for (int f = 0; f < g.n; ++f) {
         status[f] = qok ? 0 : SAGEN_JPEG_ENC_ST_RANGE;
         sizes[f] = 0;
         if (!qok) continue;
-        const uint8_t* frame = frames + (size_t)f * g.h * g.w * g.ncomp;
+        const uint8_t* frame = coef ? nullptr : frames + (size_t)f * g.h * g.w * g.ncomp;
         JpegEncWriter wr = {out + (size_t)f * g.stride, g.stride, 0, 0, 0};
         int pred[3] = {0, 0, 0};
         bool range = false;
         for (int b = 0; b < g.blocks; ++b) {
+            if (g.nseg > 1 && b > 0 && b % g.seg_blocks == 0) {       // a restart: ones to the byte, the marker unstuffed, predictions to 0
+                if (wr.nacc) jpeg_enc_put(wr, 0x7F, 8 - wr.nacc);
+                const uint8_t marker[2] = {0xFF, (uint8_t)(0xD0 + ((b / g.seg_blocks - 1) & 7))};
+                for (int i = 0; i < 2; ++i, ++wr.pos)
+                    if (wr.pos < wr.stride) wr.out[wr.pos] = marker[i];
+                pred[0] = pred[1] = pred[2] = 0;
+            }
             int comp, by, bx;
             bool dummy;
             jpeg_enc_block_place(g, b, comp, by, bx, dummy);
@@ -336,7 +380,10 @@ inline void jpeg_encode_host(const uint8_t* frames, const JpegEncGeom& g, const 
                 continue;
             }
             int16_t zz[64];
-            jpeg_enc_block(g, frame, qtabs, comp, by, bx, zz);
+            if (coef)
+                for (int k = 0; k < 64; ++k) zz[k] = coef[((size_t)f * g.blocks + b) * 64 + k];
+            else
+                jpeg_enc_block(g, frame, qtabs, comp, by, bx, zz);
             int len = jpeg_enc_code(huff, tab, true, 0, zz[0] - pred[comp], bits, range);
             jpeg_enc_put(wr, bits, len);
             pred[comp] = zz[0];
@@ -357,6 +404,84 @@ inline void jpeg_encode_host(const uint8_t* frames, const JpegEncGeom& g, const 
         if (wr.pos > g.stride) status[f] |= SAGEN_JPEG_ENC_ST_CAPACITY;
         if (range) status[f] |= SAGEN_JPEG_ENC_ST_RANGE;
     }
+}
+
+// ---- sagen_jpeg_transcode: the decoder's entropy stage into coefficients, the encoder's entropy half out of them ------------------------
+// a block of a file can hold what the tables allow, not only what 8-bit samples reach: the bound is taken at JPEG_ENC_CODE_BITS
+inline long long jpeg_transcode_max_bytes(long long blocks, long long nseg) { return 2 * ((blocks * JPEG_ENC_CODE_BITS + 7) / 8) + 2 + 4 * (nseg - 1); }
+
+struct JpegTranscodeScratch {
+    size_t dec, enc, enc_status, total;            // the decoder's tables + natural-order coefficients, the encoder's regions, int32 [n]
+};
+
+inline JpegTranscodeScratch jpeg_transcode_scratch_layout(const JpegGeom& d, const JpegEncGeom& g, int n_hufftabs) {
+    JpegTranscodeScratch s;
+    s.dec = 0;
+    s.enc = (jpeg_scratch_layout(d, n_hufftabs).planes + 15) / 16 * 16;            // (the planes are not made)
+    s.enc_status = (s.enc + jpeg_enc_scratch_layout(g).total + 15) / 16 * 16;
+    s.total = (s.enc_status + (size_t)g.n * sizeof(int32_t) + 15) / 16 * 16;
+    return s;
+}
+
+// the geometry of both halves; every block of the source scan is coded (all_real)
+inline int jpeg_transcode_geom_fill(JpegGeom& d, JpegEncGeom& g, int n, int w, int h, int ncomp, int hs, int vs, int restart_interval, long long stride,
+                                    int n_hufftabs, const char** why) {
+    int rc = jpeg_geom_fill(d, n, w, h, ncomp, hs, vs, why);
+    if (rc != SAGEN_OK) return rc;
+    rc = jpeg_enc_geom_fill(g, n, w, h, ncomp, hs, vs, stride, why);
+    if (rc != SAGEN_OK) return rc;
+    rc = jpeg_enc_geom_rst(g, restart_interval, why);
+    if (rc != SAGEN_OK) return rc;
+    if (n_hufftabs < 1) return *why = "a table count < 1", SAGEN_ERR_SHAPE;
+    if (n_hufftabs > 65536) return *why = "more than 65536 tables", SAGEN_ERR_UNSUPPORTED;
+    g.all_real = 1;
+    return SAGEN_OK;
+}
+
+inline int jpeg_transcode_args_check(JpegGeom& d, JpegEncGeom& g, const void* bytes, long long total_bytes, const void* frames, int n, const void* segments,
+                                     int n_segments, const void* hufftabs, int n_hufftabs, int w, int h, int ncomp, int hs, int vs, int restart_interval,
+                                     const void* out, long long stride, const void* sizes, const void* status, const void* scratch, size_t scratch_bytes,
+                                     const char** why) {
+    const int rc = jpeg_transcode_geom_fill(d, g, n, w, h, ncomp, hs, vs, restart_interval, stride, n_hufftabs, why);
+    if (rc != SAGEN_OK) return rc;
+    if (!bytes || !frames || !segments || !hufftabs || !out || !sizes || !status || !scratch) return *why = "null argument", SAGEN_ERR_NULL;
+    if (total_bytes < 0 || total_bytes % 4) return *why = "total_bytes negative or not a multiple of 4", SAGEN_ERR_SHAPE;
+    if (total_bytes > 0x7fffffffLL) return *why = "more than 2^31 - 1 bytes in one call", SAGEN_ERR_UNSUPPORTED;
+    if (n_segments < n) return *why = "n_segments < n", SAGEN_ERR_SHAPE;
+    if ((uintptr_t)bytes % 4 || (uintptr_t)frames % 8 || (uintptr_t)segments % 4 || (uintptr_t)out % 4 || (uintptr_t)sizes % 4 || (uintptr_t)status % 4 ||
+        (uintptr_t)scratch % 16)
+        return *why = "bytes / frames / segments / out / sizes / status / scratch must be aligned to 4 / 8 / 4 / 4 / 4 / 4 / 16 bytes", SAGEN_ERR_SHAPE;
+    if (scratch_bytes < jpeg_transcode_scratch_layout(d, g, n_hufftabs).total) return *why = "transcode scratch too small", SAGEN_ERR_WORKSPACE;
+    return SAGEN_OK;
+}
+
+constexpr int JPEG_TRANSCODE_QTABS = 0x7fffffff;   // no quantisation table is read: any non-negative index of a descriptor passes the check
+
+// sagen_jpeg_transcode on host pointers, after jpeg_transcode_args_check
+inline void jpeg_transcode_host(const uint8_t* bytes, long long total_bytes, const sagen_jpeg_frame* frames, const int32_t* segments, int n_segments,
+                                const uint8_t* hufftabs, int n_hufftabs, const JpegGeom& d, const JpegEncGeom& g, uint8_t* out, int32_t* sizes,
+                                int32_t* status, void* scratch) {
+    const JpegTranscodeScratch lay = jpeg_transcode_scratch_layout(d, g, n_hufftabs);
+    const JpegScratch dl = jpeg_scratch_layout(d, n_hufftabs);
+    JpegHuff* huff = (JpegHuff*)((char*)scratch + dl.huff);
+    int16_t* nat = (int16_t*)((char*)scratch + dl.coef);
+    int16_t* zz = (int16_t*)((char*)scratch + lay.enc + jpeg_enc_scratch_layout(g).coef);
+    int32_t* enc_status = (int32_t*)((char*)scratch + lay.enc_status);
+    const size_t total = (size_t)d.n * d.blocks * 64;
+    for (size_t i = 0; i < total; ++i) nat[i] = 0;
+    for (int t = 0; t < n_hufftabs; ++t) jpeg_huff_build(hufftabs + (size_t)t * JPEG_HUFF_SPEC, huff[t]);
+    for (int f = 0; f < d.n; ++f)
+        status[f] = (int32_t)jpeg_check_frame(frames[f], f, segments, n_segments, total_bytes, JPEG_TRANSCODE_QTABS, n_hufftabs, d, huff);
+    for (int s = 0; s < n_segments; ++s) {
+        const int f = segments[2 * (size_t)s];
+        if (f < 0 || f >= d.n || (status[f] & (SAGEN_JPEG_ST_DESC | SAGEN_JPEG_ST_TABLE))) continue;
+        const long long k = (long long)s - frames[f].first_segment;
+        if (k < 0 || k >= frames[f].n_segments) continue;
+        status[f] |= (int32_t)jpeg_decode_segment(bytes, frames[f], segments, (int)k, d, huff, nat + (size_t)f * d.blocks * 64);
+    }
+    for (size_t i = 0; i < total; ++i) zz[i] = nat[(i & ~(size_t)63) + jpeg_natural((int)(i & 63))];
+    jpeg_encode_host(nullptr, g, nullptr, out, sizes, enc_status, zz);
+    for (int f = 0; f < d.n; ++f) status[f] |= enc_status[f] << 8;
 }
 
 }  // namespace sagen

@@ -27,6 +27,7 @@
 #include "../csrc/op_entries_feed.h"
 #include "../csrc/op_entries_audio.h"
 #include "../csrc/op_entries_png.h"
+#include "../csrc/op_entries_jpeg_rst.h"
 #include "../csrc/stft_frames.h"
 
 namespace {
@@ -748,6 +749,15 @@ int run_jpeg_decode(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_
 int run_jpeg_encode(const uint8_t* frames, const JpegEncGeom& g, const uint16_t* qtabs, uint8_t* out, int32_t* sizes, int32_t* status, void*,
                     void*) {
     jpeg_encode_host(frames, g, qtabs, out, sizes, status);
+    return SAGEN_OK;
+}
+
+/* Lossless re-segmenting (include/sagen.h: sagen_jpeg_transcode): the decoder's entropy loop into coefficients, the encoder's bit loop
+ * out of them (csrc/jpeg_enc_core.h: jpeg_transcode_host).  The scratch is used as the device uses it. */
+int run_jpeg_transcode(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_frame* frames, const int32_t* segments, int n_segments,
+                       const uint8_t* hufftabs, int n_hufftabs, const JpegGeom& d, const JpegEncGeom& g, uint8_t* out, int32_t* sizes, int32_t* status,
+                       void* scratch, void*) {
+    jpeg_transcode_host(bytes, total_bytes, frames, segments, n_segments, hufftabs, n_hufftabs, d, g, out, sizes, status, scratch);
     return SAGEN_OK;
 }
 

@@ -1,7 +1,7 @@
 """Estimate dense optical flow on the device and write the flow folder of a clip.
 
     python -m spatialaudiogen_amd.flow VIDEO_DIR FLOW_DIR [--levels L] [--warps W] [--iters I] [--alpha A] [--no_wrap] [--block 64]
-        [--format {jpg,png}] [--encode {host,device}] [--overwrite]
+        [--format {jpg,png}] [--encode {host,device}] [--restart_rows N] [--overwrite]
 
 VIDEO_DIR holds the frames %06d.jpg (what `python -m spatialaudiogen_amd.project ... --size 224 448` writes); FLOW_DIR receives
 %06d.jpg (or .png) and flow_limits.npy, float32 [n, 2]: the folder feeder.FlowFrames decodes and the flow encoder reads.  Frame k
@@ -95,12 +95,15 @@ class FlowEstimator(object):
         return ops.optical_flow(torch.cat([first, frames], 0), self.params.struct(h, w))
 
 
-def write_flow_folder(video_dir, flow_dir, params=None, block=64, fmt='jpg', device=None, decode='host', encode='host'):
+def write_flow_folder(video_dir, flow_dir, params=None, block=64, fmt='jpg', device=None, decode='host', encode='host', restart_rows=0):
     """Flow folder of the frames %06d.jpg of video_dir: flow_dir/%06d.<fmt> + flow_dir/flow_limits.npy.  Returns (n, h, w, levels).
     decode 'device': the frames are decoded on the device (jpeg.load_frames_device) instead of by PIL on the host; same pixels.
-    encode 'device' (jpg only): the flow frames are encoded on the device (jpeg.JpegEncoder) instead of by PIL on the host; same files."""
+    encode 'device' (jpg only): the flow frames are encoded on the device (jpeg.JpegEncoder) instead of by PIL on the host; same files.
+    restart_rows (jpg only): rows of MCUs per restart interval of the files written, 0 for none; same files either way."""
     if encode == 'device' and fmt != 'jpg':
         raise ValueError('encode=device writes jpg only (fmt=%s)' % fmt)
+    if restart_rows < 0 or (restart_rows and fmt != 'jpg'):
+        raise ValueError('restart_rows takes 0 or a positive number of MCU rows and belongs to jpg (restart_rows=%d fmt=%s)' % (restart_rows, fmt))
     import torch
     from .overlay import frame_names, load_frames
     from .project import save_frames
@@ -116,7 +119,7 @@ def write_flow_folder(video_dir, flow_dir, params=None, block=64, fmt='jpg', dev
         decoder = JpegDecoder(est.device)
     if encode == 'device':
         from .jpeg import JpegEncoder, save_frames_device
-        encoder = JpegEncoder(est.device)                             # quality 95, 4:2:0: what save_frames writes
+        encoder = JpegEncoder(est.device, restart_rows=restart_rows)  # quality 95, 4:2:0: what save_frames writes
     for first, stop in block_ranges(len(names), block):
         start = first if prev is None else first + 1
         frames = decoder.decode(names[start:stop]) if decode == 'device' else torch.as_tensor(load_frames(names[start:stop])).to(est.device)
@@ -125,7 +128,7 @@ def write_flow_folder(video_dir, flow_dir, params=None, block=64, fmt='jpg', dev
         if encode == 'device':
             save_frames_device(flow_dir, rgb, start, encoder)
         else:
-            save_frames(flow_dir, rgb.cpu().numpy(), start, fmt)
+            save_frames(flow_dir, rgb.cpu().numpy(), start, fmt, restart_rows)
         limits.append(lim.cpu().numpy())
         prev, hw = frames[-1], tuple(frames.shape[1:3])
     np.save(os.path.join(flow_dir, 'flow_limits.npy'), np.concatenate(limits, 0).astype(np.float32))
@@ -159,6 +162,8 @@ def parse_arguments(argv=None):
     parser.add_argument('--decode', default='host', choices=['host', 'device'], help="where the input frames are decoded: host (PIL, one thread) or device (jpeg.py: the files' bytes go to the device; same pixels)")
     from .project import ENCODE_HELP
     parser.add_argument('--encode', default='host', choices=['host', 'device'], help=ENCODE_HELP)
+    from .project import RESTART_HELP
+    parser.add_argument('--restart_rows', type=int, default=0, metavar='N', help=RESTART_HELP)
     return parser.parse_args(argv)
 
 
@@ -183,13 +188,16 @@ def main(argv=None):
         levels = params.levels_for(h, w)
     except ValueError as e:
         raise SystemExit('flow: %s' % e)
+    from .project import check_restart_rows
+    check_restart_rows('flow', args.restart_rows, args.format, w)
     prepare_output_dir(args.flow_dir, args.overwrite)               # every refusal is behind us
     import torch
     from . import _lib
     _lib.lib()
     if not _lib.IS_CPU_TWIN:
         torch.cuda.set_device(args.gpu)
-    n, h, w, levels = write_flow_folder(args.video_dir, args.flow_dir, params, args.block, args.format, decode=args.decode, encode=args.encode)
+    n, h, w, levels = write_flow_folder(args.video_dir, args.flow_dir, params, args.block, args.format, decode=args.decode, encode=args.encode,
+                                          restart_rows=args.restart_rows)
     print('wrote %d flow frames of %dx%d to %s (levels %d, warps %d, iters %d)' % (n, h, w, args.flow_dir, levels, params.warps, params.iters))
 
 

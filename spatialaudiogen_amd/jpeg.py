@@ -14,9 +14,18 @@ Image.fromarray(f).save(path, quality=q, subsampling=s) writes on libjpeg (stand
 produces the entropy-coded data; the header and FF D9 are put around it here.
 
     quality_tables(quality)             -> uint16 [2][64], natural order (libjpeg's scaling of Annex K.1 / K.2)
-    encode_header(w, h, components, hs, vs, qtabs) -> bytes: SOI .. SOS
-    JpegEncoder(device, quality, subsampling).encode(frames) -> list of bytes; frames uint8 [n, h, w, 3] or [n, h, w] on the device
+    encode_header(w, h, components, hs, vs, qtabs, restart_interval=0) -> bytes: SOI .. SOS
+    restart_interval_of(w, h, components, hs, vs, restart_rows, restart_blocks) -> MCUs, by PIL's rule (rows win)
+    JpegEncoder(device, quality, subsampling, restart_rows=0, restart_blocks=0).encode(frames) -> list of bytes; frames uint8
+                                        [n, h, w, 3] or [n, h, w] on the device; with a restart interval (sagen_jpeg_encode_rst) the
+                                        files are PIL's for restart_marker_rows / restart_marker_blocks
     save_frames_device(out_dir, frames, first, encoder)      the device form of project.save_frames(..., 'jpg')
+
+Files that exist get their restart interval without a pixel being computed (sagen_jpeg_transcode: the decoder's entropy stage into
+coefficients, the encoder's entropy half out of them):
+
+    transcode_files(datas, restart_rows=1, device=None) -> list of bytes, the coefficients of each file unchanged
+    python -m spatialaudiogen_amd.jpeg restart IN_DIR OUT_DIR [--rows 1 | --blocks N] [--block 256] [--overwrite]
 """
 import collections
 import ctypes as C
@@ -373,9 +382,11 @@ def _segment(marker, body):
     return bytes([0xFF, marker, (len(body) + 2) >> 8, (len(body) + 2) & 255]) + body
 
 
-def encode_header(w, h, components, hs, vs, qtabs):
-    """SOI, the JFIF APP0 PIL writes without dpi, DQT per table, SOF0, DHT per table, SOS: everything in front of the entropy-coded data.
-    qtabs: [2][64] in natural order."""
+def encode_header(w, h, components, hs, vs, qtabs, restart_interval=0):
+    """SOI, the JFIF APP0 PIL writes without dpi, DQT per table, SOF0, DHT per table, (DRI,) SOS: everything in front of the entropy-coded
+    data.  qtabs: [2][64] in natural order; restart_interval: MCUs, 0 for none - libjpeg puts DRI directly in front of SOS."""
+    if not 0 <= int(restart_interval) <= 65535:
+        raise ValueError('a restart interval of %d MCUs is outside 0..65535 (what DRI can name)' % restart_interval)
     if components not in (1, 3) or (components == 1 and (hs, vs) != (1, 1)) or (hs, vs) not in SUBSAMPLING.values():
         raise ValueError('components %d with sampling %dx%d is outside baseline grey / 4:4:4 / 4:2:2 / 4:2:0' % (components, hs, vs))
     qtabs = np.asarray(qtabs)
@@ -386,12 +397,28 @@ def encode_header(w, h, components, hs, vs, qtabs):
     out += _segment(0xC0, bytes([8, h >> 8, h & 255, w >> 8, w & 255, components]) + b''.join(bytes(c) for c in comps))
     for ident, spec in zip((0x00, 0x10, 0x01, 0x11), _STD_HUFF[:2 if components == 1 else 4]):
         out += _segment(0xC4, bytes([ident]) + spec)
+    if restart_interval:
+        out += _segment(0xDD, bytes([int(restart_interval) >> 8, int(restart_interval) & 255]))
     return out + _segment(0xDA, bytes([components]) + b''.join(bytes([c[0], c[2] * 0x11]) for c in comps) + b'\0\x3f\0')
 
 
-def encode_streams(frames, qtabs, hs, vs, stride, out=None):
+def restart_interval_of(w, h, components, hs, vs, restart_rows=0, restart_blocks=0):
+    """The interval in MCUs as PIL's restart_marker_rows / restart_marker_blocks give it: rows win, and mean rows x MCUs per row.  An
+    interval DRI cannot name is refused, not clamped."""
+    if restart_rows < 0 or restart_blocks < 0:
+        raise ValueError('restart_rows and restart_blocks must not be negative')
+    fh, fv = (hs, vs) if components == 3 else (1, 1)
+    interval = int(restart_rows) * (-(-w // (8 * fh))) if restart_rows else int(restart_blocks)
+    if interval > 65535:
+        raise ValueError('a restart interval of %d MCUs (%s) is above 65535, the most a DRI segment can name'
+                         % (interval, 'restart_rows=%d at %d MCUs per row' % (restart_rows, -(-w // (8 * fh))) if restart_rows else 'restart_blocks'))
+    return interval
+
+
+def encode_streams(frames, qtabs, hs, vs, stride, out=None, restart_interval=0):
     """sagen_jpeg_encode on `frames` (uint8 [n, h, w, 3] or [n, h, w], device memory; the host with the CPU twin); qtabs uint16 [2][64] in
-    natural order (host).  Returns (out [n, stride] uint8, sizes [n] int32, status [n] int32) on that device; nothing is synchronised."""
+    natural order (host); with a restart_interval (MCUs, the caller's DRI) sagen_jpeg_encode_rst.  Returns (out [n, stride] uint8,
+    sizes [n] int32, status [n] int32) on that device; nothing is synchronised."""
     import torch
     from .ops import _ptr, _stream
     l = _lib.lib()
@@ -406,6 +433,14 @@ def encode_streams(frames, qtabs, hs, vs, stride, out=None):
         out = torch.empty((n, stride), dtype=torch.uint8, device=dev)
     sizes = torch.empty(n, dtype=torch.int32, device=dev)
     status = torch.empty(n, dtype=torch.int32, device=dev)
+    if restart_interval:
+        if not 0 < int(restart_interval) <= 65535:
+            raise ValueError('a restart interval of %d MCUs is outside 0..65535 (what DRI can name)' % restart_interval)
+        nbytes = int(l.sagen_jpeg_encode_rst_scratch_bytes(n, w, h, comps, hs, vs, int(restart_interval), stride))
+        scratch = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=dev)
+        _lib.check(l.sagen_jpeg_encode_rst(_ptr(frames), n, w, h, comps, hs, vs, int(restart_interval), _ptr(zz), _ptr(out), stride, _ptr(sizes),
+                                           _ptr(status), _ptr(scratch), nbytes, _stream()))
+        return out, sizes, status
     nbytes = int(l.sagen_jpeg_encode_scratch_bytes(n, w, h, comps, hs, vs, stride))
     scratch = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=dev)
     _lib.check(l.sagen_jpeg_encode(_ptr(frames), n, w, h, comps, hs, vs, _ptr(zz), _ptr(out), stride, _ptr(sizes), _ptr(status), _ptr(scratch),
@@ -416,15 +451,20 @@ def encode_streams(frames, qtabs, hs, vs, stride, out=None):
 class JpegEncoder(object):
     """encode(frames) -> list of complete files (bytes), one per frame: what PIL writes for the same pixels at `quality` and `subsampling`
     ('4:4:4', '4:2:2', '4:2:0'; grey frames [n, h, w] have none).  One device call per block of frames, one copy of sizes + status, one
-    copy of the streams cut at the longest; a frame whose stream does not fit the stride is encoded again, alone, at the bound."""
+    copy of the streams cut at the longest; a frame whose stream does not fit the stride is encoded again, alone, at the bound.
+    restart_rows / restart_blocks: PIL's restart_marker_rows / restart_marker_blocks (rows win; rows x MCUs per row): the files then
+    hold a DRI segment and restart markers, and the device decoder reads them with one lane per segment."""
 
-    def __init__(self, device=None, quality=95, subsampling='4:2:0', stride=None):
+    def __init__(self, device=None, quality=95, subsampling='4:2:0', stride=None, restart_rows=0, restart_blocks=0):
         import torch
         _lib.lib()
         if subsampling not in SUBSAMPLING:
             raise ValueError('subsampling %r is none of %s' % (subsampling, ', '.join(sorted(SUBSAMPLING))))
         self.device = torch.device(device if device is not None else ('cpu' if _lib.IS_CPU_TWIN else 'cuda'))
         self.quality, self.subsampling, self.stride = quality, subsampling, stride
+        if restart_rows < 0 or restart_blocks < 0:
+            raise ValueError('restart_rows and restart_blocks must not be negative')
+        self.restart_rows, self.restart_blocks = int(restart_rows), int(restart_blocks)
         self.qtabs = quality_tables(quality)
 
     def _fetch(self, out, longest):
@@ -449,8 +489,9 @@ class JpegEncoder(object):
         comps = 3 if frames.dim() == 4 else 1
         hs, vs = SUBSAMPLING[self.subsampling] if comps == 3 else (1, 1)
         stride = self.stride if self.stride is not None else max((w * h * comps + 63) // 64 * 64, 4096)
-        head = encode_header(w, h, comps, hs, vs, self.qtabs)
-        out, sizes, status = encode_streams(frames, self.qtabs, hs, vs, stride)
+        rst = restart_interval_of(w, h, comps, hs, vs, self.restart_rows, self.restart_blocks)
+        head = encode_header(w, h, comps, hs, vs, self.qtabs, rst)
+        out, sizes, status = encode_streams(frames, self.qtabs, hs, vs, stride, restart_interval=rst)
         both = torch.stack([sizes, status], 0).cpu().numpy()                      # the one copy of both
         sizes, status = both[0], both[1]
         for f in np.flatnonzero(status & _lib.SAGEN_JPEG_ENC_ST_RANGE):
@@ -459,13 +500,172 @@ class JpegEncoder(object):
         data = self._fetch(out, longest) if longest else np.zeros((n, 0), np.uint8)
         files = [head + data[f, :sizes[f]].tobytes() + b'\xff\xd9' for f in range(n)]
         for f in np.flatnonzero(status & _lib.SAGEN_JPEG_ENC_ST_CAPACITY):
-            bound = (int(_lib.lib().sagen_jpeg_encode_max_bytes(w, h, comps, hs, vs)) + 3) // 4 * 4
-            o, sz, st = encode_streams(frames[f:f + 1], self.qtabs, hs, vs, bound)
+            bound = (int(_lib.lib().sagen_jpeg_encode_rst_max_bytes(w, h, comps, hs, vs, rst)) + 3) // 4 * 4
+            o, sz, st = encode_streams(frames[f:f + 1], self.qtabs, hs, vs, bound, restart_interval=rst)
             sz, st = int(sz.cpu()[0]), int(st.cpu()[0])
             if st:
                 raise RuntimeError('frame %d: status %d at the stride that cannot be too small' % (first + f, st))
             files[f] = head + self._fetch(o, sz)[0].tobytes() + b'\xff\xd9'
         return files
+
+
+# ---- re-segmenting files that exist ------------------------------------------------------------------------------------------------------
+def transcode_header(data, info, restart_interval):
+    """The header of `data` (SOI .. SOS) for its re-coded scan: the file's own segments in their order, each DHT replaced by the standard
+    tables (the four of Annex K, two for grey, where the first DHT stood), any DRI dropped, the new one directly in front of SOS, and
+    the scan header naming tables 0 for luma and 1 for chroma."""
+    out, pos, tables = b'\xff\xd8', 2, False
+    while True:
+        while data[pos] == 0xFF:
+            pos += 1
+        m = data[pos]
+        pos += 1
+        if m == 0x01 or 0xD0 <= m <= 0xD7:
+            continue
+        length = _be16(data, pos)
+        body = data[pos + 2:pos + length]
+        pos += length
+        if m == 0xC4:
+            if not tables:
+                for ident, spec in zip((0x00, 0x10, 0x01, 0x11), _STD_HUFF[:2 if info.components == 1 else 4]):
+                    out += _segment(0xC4, bytes([ident]) + spec)
+            tables = True
+        elif m == 0xDA:
+            if restart_interval:
+                out += _segment(0xDD, bytes([restart_interval >> 8, restart_interval & 255]))
+            sel = b''.join(bytes([body[1 + 2 * i], 0x11 if i else 0x00]) for i in range(info.components))
+            return out + _segment(0xDA, bytes([info.components]) + sel + b'\0\x3f\0')
+        elif m != 0xDD:
+            out += _segment(m, body)
+
+
+def transcode_streams(packed, staged, restart_interval, stride):
+    """sagen_jpeg_transcode on `staged`, the uint8 tensor holding packed.buffer where the library reads.  Returns (out [n, stride] uint8,
+    sizes [n] int32, status [n] int32) on that device; nothing is synchronised."""
+    import torch
+    from .ops import _ptr, _stream
+    l = _lib.lib()
+    w, h, comps, hs, vs = packed.geometry
+    n = packed.n
+    out = torch.empty((n, stride), dtype=torch.uint8, device=staged.device)
+    sizes = torch.empty(n, dtype=torch.int32, device=staged.device)
+    status = torch.empty(n, dtype=torch.int32, device=staged.device)
+    nbytes = int(l.sagen_jpeg_transcode_scratch_bytes(n, w, h, comps, hs, vs, packed.n_hufftabs, restart_interval, stride))
+    scratch = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=staged.device)
+    at = lambda off: C.c_void_p(staged.data_ptr() + off)
+    _lib.check(l.sagen_jpeg_transcode(at(packed.bytes_at), packed.total_bytes, at(packed.frames_at), n, at(packed.segments_at), packed.n_segments,
+                                      at(packed.hufftabs_at), packed.n_hufftabs, w, h, comps, hs, vs, restart_interval, _ptr(out), stride,
+                                      _ptr(sizes), _ptr(status), _ptr(scratch), nbytes, _stream()))
+    return out, sizes, status
+
+
+def transcode_status_text(code):
+    enc = [name for bit, name in ((1, 'capacity'), (2, 'range')) if (code >> 8) & bit]
+    return ' + '.join(([status_text(code & 255)] if code & 255 else []) + ['encode ' + e for e in enc]) or 'ok'
+
+
+def transcode_files(datas, restart_rows=1, device=None, restart_blocks=0, names=None):
+    """The files `datas` (bytes) with a restart interval of `restart_rows` rows of MCUs (or `restart_blocks` MCUs; rows win, as in PIL),
+    re-coded on the device WITHOUT a pixel being computed: the coefficients of each written file equal those of its source
+    (sagen_jpeg_transcode).  One parse per file; the header is the file's own with the standard Huffman tables and the new DRI
+    (transcode_header).  A file outside the decoder's scope is passed through byte for byte, with one JpegFallbackWarning per call.
+    A damaged file raises IOError."""
+    import torch
+    _lib.lib()
+    device = torch.device(device if device is not None else ('cpu' if _lib.IS_CPU_TWIN else 'cuda'))
+    datas = [bytes(d) for d in datas]
+    names = names or ['<item %d>' % k for k in range(len(datas))]
+    result, groups, warned = list(datas), collections.OrderedDict(), False
+    for k, d in enumerate(datas):
+        try:
+            info = parse(d)
+            groups.setdefault(tuple(info[:5]), []).append((k, info))
+        except JpegUnsupported as e:
+            if not warned:
+                warnings.warn('%s is passed through as it is (%s); further files of this kind are not reported' % (names[k], e.reason), JpegFallbackWarning)
+                warned = True
+    for geometry, members in groups.items():
+        w, h, comps, hs, vs = geometry
+        rst = restart_interval_of(w, h, comps, hs, vs, restart_rows, restart_blocks)
+        idx, infos = [k for k, _ in members], [i for _, i in members]
+        packed = pack([datas[k] for k in idx], infos)
+        staged = torch.as_tensor(packed.buffer).to(device)
+        bound = (int(_lib.lib().sagen_jpeg_transcode_max_bytes(w, h, comps, hs, vs, rst)) + 3) // 4 * 4
+        mcus = -(-w // (8 * hs)) * -(-h // (8 * vs))
+        # the standard tables can be longer than a file's own: half as much again, the markers and their fills, and a floor
+        stride = min(bound, (max(i.scan_bytes for i in infos) * 3 // 2 + 4 * mcus + 4096 + 63) // 64 * 64)
+        out, sizes, status = transcode_streams(packed, staged, rst, stride)
+        both = torch.stack([sizes, status], 0).cpu().numpy()
+        sizes, status = both[0], both[1]
+        longest = int(min(sizes.max(), stride))
+        data = out[:, :longest].cpu().numpy()
+        for j, k in enumerate(idx):
+            st, stream = int(status[j]), None
+            if st == _lib.SAGEN_JPEG_ENC_ST_CAPACITY << 8:               # alone, at the stride that cannot be too small
+                one = pack([datas[k]], [infos[j]])
+                o, sz, s1 = transcode_streams(one, torch.as_tensor(one.buffer).to(device), rst, bound)
+                st, stream = int(s1.cpu()[0]), o[0, :int(sz.cpu()[0])].cpu().numpy().tobytes()
+            if st:
+                raise IOError('%s: the JPEG stream cannot be re-segmented (%s)' % (names[k], transcode_status_text(st)))
+            result[k] = transcode_header(datas[k], infos[j], rst) + (stream if stream is not None else data[j, :sizes[j]].tobytes()) + b'\xff\xd9'
+    return result
+
+
+def main(argv=None):
+    """python -m spatialaudiogen_amd.jpeg restart IN_DIR OUT_DIR [--rows 1 | --blocks N] [--block 256] [--overwrite]"""
+    import argparse
+    import os
+    parser = argparse.ArgumentParser(prog='python -m spatialaudiogen_amd.jpeg', description='Tools around the JPEG frames of a clip folder.')
+    sub = parser.add_subparsers(dest='command', required=True)
+    p = sub.add_parser('restart', help='give the .jpg files of a folder a restart interval, losslessly (the coefficients stay; the device decoder '
+                                       'then reads each frame with one lane per segment)')
+    p.add_argument('in_dir', help='folder of .jpg files')
+    p.add_argument('out_dir', help='folder for the re-segmented files, same names')
+    which = p.add_mutually_exclusive_group()
+    which.add_argument('--rows', type=int, default=None, help='rows of MCUs per restart interval (default 1)')
+    which.add_argument('--blocks', type=int, default=None, help='MCUs per restart interval')
+    p.add_argument('--block', type=int, default=256, help='files per device call')
+    p.add_argument('--overwrite', action='store_true', help='Whether to replace .jpg files already in the output folder.')
+    p.add_argument('--gpu', type=int, default=0, help='GPU id')
+    args = parser.parse_args(argv)
+    rows, blocks = (0, args.blocks) if args.blocks is not None else (1 if args.rows is None else args.rows, 0)
+    if rows < 0 or blocks < 0 or (rows == 0 and blocks == 0):
+        raise SystemExit('jpeg restart: --rows and --blocks take a positive number')
+    if args.block < 1:
+        raise SystemExit('jpeg restart: --block takes a positive value')
+    if not os.path.isdir(args.in_dir):
+        raise SystemExit('jpeg restart: %s is not a folder' % args.in_dir)
+    files = sorted(f for f in os.listdir(args.in_dir) if f.lower().endswith(('.jpg', '.jpeg')))
+    if not files:
+        raise SystemExit('jpeg restart: %s holds no .jpg file' % args.in_dir)
+    if os.path.abspath(args.in_dir) == os.path.abspath(args.out_dir):
+        raise SystemExit('jpeg restart: the output folder is the input folder')
+    held = [f for f in os.listdir(args.out_dir) if f.lower().endswith(('.jpg', '.jpeg'))] if os.path.isdir(args.out_dir) else []
+    if held and not args.overwrite:
+        raise SystemExit('jpeg restart: %s already holds frames (--overwrite)' % args.out_dir)
+    import torch
+    _lib.lib()
+    if not _lib.IS_CPU_TWIN:
+        torch.cuda.set_device(args.gpu)
+    for f in held:
+        os.remove(os.path.join(args.out_dir, f))
+    os.makedirs(args.out_dir, exist_ok=True)
+    before = after = 0
+    for i in range(0, len(files), args.block):
+        part = files[i:i + args.block]
+        datas = []
+        for f in part:
+            with open(os.path.join(args.in_dir, f), 'rb') as fh:
+                datas.append(fh.read())
+        try:
+            done = transcode_files(datas, rows, None, blocks, [os.path.join(args.in_dir, f) for f in part])
+        except (ValueError, IOError) as e:
+            raise SystemExit('jpeg restart: %s' % e)
+        for f, d in zip(part, done):
+            with open(os.path.join(args.out_dir, f), 'wb') as fh:
+                fh.write(d)
+        before, after = before + sum(len(d) for d in datas), after + sum(len(d) for d in done)
+    print('wrote %d files to %s: %d bytes before, %d after (%+.2f %%)' % (len(files), args.out_dir, before, after, 100. * (after - before) / before))
 
 
 def save_frames_device(out_dir, frames, first, encoder):
@@ -474,3 +674,7 @@ def save_frames_device(out_dir, frames, first, encoder):
     for i, data in enumerate(encoder.encode(frames, first)):
         with open(os.path.join(out_dir, '%06d.jpg' % (first + i)), 'wb') as f:
             f.write(data)
+
+
+if __name__ == '__main__':
+    main()

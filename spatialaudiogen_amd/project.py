@@ -2,7 +2,7 @@
 stereo, and the pinhole view of a listener who turns their head.
 
     python -m spatialaudiogen_amd.project IN_DIR OUT_DIR --from {er,er_tb,cube,eac,eac_stereo} --to {er,cube,eac,view} --size H W
-        [--hfov DEG] [--yaw DEG ..] [--pitch DEG ..] [--roll DEG ..] [--supersample S] [--format {jpg,png}] [--encode {host,device}] [--overwrite]
+        [--hfov DEG] [--yaw DEG ..] [--pitch DEG ..] [--roll DEG ..] [--supersample S] [--format {jpg,png}] [--encode {host,device}] [--restart_rows N] [--overwrite]
 
 IN_DIR holds the frames %06d.jpg; OUT_DIR receives %06d.jpg (or .png).  `--from eac --to er --size 224 448` turns an EAC clip into
 the video folder deploy and the feeder read.  `--to view --hfov 90 --yaw 0 90` writes what a listener sees whose head turns from 0
@@ -223,13 +223,33 @@ SOURCES = {'er': lambda: equirect(), 'er_tb': lambda: equirect('top_bottom'), 'c
 TARGETS = {'er': equirect, 'cube': cubemap3x2, 'eac': eac3x2}
 
 
-def save_frames(out_dir, frames, first, fmt):
+def save_frames(out_dir, frames, first, fmt, restart_rows=0):
+    """restart_rows (jpg only): a restart interval of that many rows of MCUs, PIL's restart_marker_rows; 0: none, the files as ever."""
     if fmt == 'png':
+        if restart_rows:
+            raise ValueError('restart_rows belongs to jpg (fmt=png)')
         from .overlay import save_frames as save_png
         return save_png(out_dir, frames, first)
     from PIL import Image
+    extra = dict(restart_marker_rows=int(restart_rows)) if restart_rows else {}
     for i, f in enumerate(frames):
-        Image.fromarray(f).save(os.path.join(out_dir, '%06d.jpg' % (first + i)), quality=95)
+        Image.fromarray(f).save(os.path.join(out_dir, '%06d.jpg' % (first + i)), quality=95, **extra)
+
+
+RESTART_HELP = ("rows of MCUs (16 pixel rows at 4:2:0) per restart interval of the jpg files written, 0: none (--format jpg only).  The device "
+                "decoder (--decode device) runs one lane per restart segment, so it reads such a folder in parallel inside each frame; every "
+                "other reader sees the same pixels.  The same files with --encode host (PIL's restart_marker_rows) and --encode device.")
+
+
+def check_restart_rows(tool, restart_rows, fmt, w):
+    """the refusals of --restart_rows, in front of any file: negative, png, or an interval DRI cannot name (16 x 16 MCUs: 4:2:0)"""
+    if restart_rows < 0:
+        raise SystemExit('%s: --restart_rows takes 0 or a positive number of MCU rows' % tool)
+    if restart_rows and fmt != 'jpg':
+        raise SystemExit('%s: --restart_rows belongs to --format jpg (--format %s)' % (tool, fmt))
+    if restart_rows * (-(-w // 16)) > 65535:
+        raise SystemExit('%s: --restart_rows %d at %d MCUs per row is an interval above 65535 MCUs, the most a JPEG file can name'
+                         % (tool, restart_rows, -(-w // 16)))
 
 
 ENCODE_HELP = ("where the output frames are encoded (--format jpg only): host (PIL, one thread, after the raw frames came back) or device "
@@ -271,6 +291,7 @@ def parse_arguments(argv=None):
     parser.add_argument('--block', type=int, default=16, help='frames per device call')
     parser.add_argument('--decode', default='host', choices=['host', 'device'], help="where the input frames are decoded: host (PIL, one thread) or device (jpeg.py: the files' bytes go to the device; same pixels)")
     parser.add_argument('--encode', default='host', choices=['host', 'device'], help=ENCODE_HELP)
+    parser.add_argument('--restart_rows', type=int, default=0, metavar='N', help=RESTART_HELP)
     return parser.parse_args(argv)
 
 
@@ -279,6 +300,7 @@ def main(argv=None):
     from .overlay import frame_names, check_frame_sizes, load_frames
     if args.encode == 'device' and args.format != 'jpg':
         raise SystemExit('project: --encode device writes jpg only (--format %s)' % args.format)
+    check_restart_rows('project', args.restart_rows, args.format, args.size[1])
     if args.dst == 'view' and args.hfov is None:
         raise SystemExit('project: --to view needs --hfov')
     if args.dst != 'view' and args.hfov is not None:
@@ -320,7 +342,7 @@ def main(argv=None):
         decoder = JpegDecoder(pr.device)
     if args.encode == 'device':
         from .jpeg import JpegEncoder, save_frames_device
-        encoder = JpegEncoder(pr.device)                              # quality 95, 4:2:0: what save_frames writes
+        encoder = JpegEncoder(pr.device, restart_rows=args.restart_rows)     # quality 95, 4:2:0: what save_frames writes
     for i in range(0, n, args.block):
         block = names[i:i + args.block]
         frames = decoder.decode(block) if args.decode == 'device' else torch.as_tensor(load_frames(block)).to(pr.device)
@@ -328,7 +350,7 @@ def main(argv=None):
         if args.encode == 'device':
             save_frames_device(args.output_dir, out, i, encoder)
         else:
-            save_frames(args.output_dir, out.cpu().numpy(), i, args.format)
+            save_frames(args.output_dir, out.cpu().numpy(), i, args.format, args.restart_rows)
     S = pr.supersample or auto_supersample(src, (h, w), dst, pr.size)
     print('wrote %d frames of %dx%d to %s (%s -> %s, supersample %d)' % (n, pr.size[0], pr.size[1], args.output_dir, args.src, args.dst, S))
 
