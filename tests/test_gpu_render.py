@@ -5,6 +5,11 @@ Bar: relative RMS error <= 1e-5 against the oracle.  Basis: an fp32 restatement 
 (K = 200, C = 4, O = 2, white noise, decaying random responses) measures 6.0e-7; 1e-5 leaves 16x for another order of summation
 and is still 10x under the project's 1e-4 bar.  A stream cut into pieces must equal the one-call result BIT FOR BIT.
 
+What this bar does not see: one wrong sample, or one wrong path of the kernel (at n = 12 000 the last tap dropped at the first sample
+of every 1024-sample tile measures 1.06e-5 to 2.3e-5 by the seed, one output sample off by 0.1 % 3e-6 to 6e-6), and a kernel
+wrong in the same way in one call and in pieces.  tests/test_gpu_output_ops.py holds render_fir_kernel to the header's order of summation bit for bit, to an elementwise
+bound and to integer known answers, on every tap-loop path, output count, history length and rotation seam.
+
 The op-level cases (OP_CASES) also run against the CPU twin in a container without a GPU (tests/test_cpu_twin_render.py)."""
 import os
 

@@ -5,7 +5,9 @@ power map, and the two command lines.
 Bars.  Directions: 1e-12 absolute - fp64 sin / cos differ by ulps (~1e-16) between libraries and the angles stay below 10 rad, which
 leaves three orders of margin.  Nearest indices: exact (the test first shows that no sample is ambiguous).  Sample sums: relative RMS
 error <= 1e-5 against the oracle, the bar and basis of tests/test_gpu_render.py (an fp32 restatement of a 200-term sum with one
-sequential accumulator measures 6e-7).  A stream cut into pieces must equal the one-call result BIT FOR BIT.
+sequential accumulator measures 6e-7).  A stream cut into pieces must equal the one-call result BIT FOR BIT.  What the RMS bar does
+not see - one wrong sample, the one-tap-at-a-time hrir variant, the two-chunk direction search and its ties, nframes == N - 1 - is
+held by tests/test_gpu_output_ops.py: the fp32 sums bit for bit in the header's order, an elementwise bound, integer known answers.
 
 Base shape: rate 48000; three sources of 12000, 12001 and 11999 samples (not multiples of the 256-sample tile: the last workgroup
 is partial) - one static, one with two control points crossing phi = +-pi the long way, one with five whose nu runs past pi / 2, with
