@@ -457,8 +457,8 @@ def main(argv=None):
     render.check_render_arguments(args, 4, 'deploy')
     rendering = render.rendering_from_arguments(args, 4, params.audio_rate, 'deploy') if args.render else None   # host only (HRIR files, refusals)
     if args.overlay_dir:
-        from . import overlay
-        overlay.prepare_output_dir(args.overlay_dir, args.overwrite, 'deploy')
+        from . import frames, overlay
+        frames.prepare_output_dir(args.overlay_dir, args.overwrite, 'deploy')
     torch.cuda.set_device(args.gpu)
     renderer = render.Renderer(*rendering) if rendering else None
     model = W2XYZ(args.model_dir, decode=args.frame_decode)
@@ -466,11 +466,8 @@ def main(argv=None):
     painted = None
     if args.overlay_dir:
         ov = overlay.Overlay(4, audio_rate=params.audio_rate, video_rate=params.video_rate)
-        encoder = None
-        if args.encode == 'device':
-            from .png import PngEncoder
-            encoder = PngEncoder(ov.device)
-        res = model.deploy_and_overlay(args.input_folder, args.deploy_start, args.deploy_duration, ov, renderer, encoder=encoder)
+        writer = frames.FrameWriter(args.overlay_dir, 'png', args.encode, ov.device)
+        res = model.deploy_and_overlay(args.input_folder, args.deploy_start, args.deploy_duration, ov, renderer, encoder=writer.encoder)
         ambi_pred, painted = res[0], res[1]
         rendered = res[2] if renderer is not None else None
     elif renderer is None:
@@ -486,13 +483,10 @@ def main(argv=None):
         print('wrote %s: %d samples x %d channels (%s)' % (args.render_fn, rendered.shape[0], rendered.shape[1], args.render))
     if painted is not None:
         if args.encode == 'device':
-            for i, data in enumerate(painted):
-                with open(os.path.join(args.overlay_dir, '%06d.png' % i), 'wb') as f:
-                    f.write(data)
-            count = len(painted)
+            writer.write_files(painted)
         else:
-            overlay.save_frames(args.overlay_dir, painted)
-            count = painted.shape[0]
+            writer.write(torch.as_tensor(painted))
+        count = len(painted)
         if args.save_maps:
             np.savez(args.save_maps, maps=ov.maps().cpu().numpy())
         print('wrote %d frames to %s (%d maps of %dx%d)' % (count, args.overlay_dir, ov.maps().shape[0], ov.map_shape[0], ov.map_shape[1]))

@@ -365,7 +365,7 @@ class DeviceFrames(object):
 
     def __init__(self, folder, kind='video', device=None, decoder=None, block=256, rate=None, prep=None, flow_prep=None):
         import torch
-        from . import _lib
+        from . import ops
         if kind not in ('video', 'flow'):
             raise ValueError("kind must be 'video' or 'flow', not %r" % (kind,))
         if prep is not None or flow_prep is not None:
@@ -382,9 +382,9 @@ class DeviceFrames(object):
         from PIL import Image
         with Image.open(os.path.join(self.folder, names[0])) as im:       # (the header only: nothing is decoded here)
             self.frame_shape = (im.size[1], im.size[0], 3)
-        _lib.lib()
-        self.device = torch.device(device if device is not None else (decoder.device if decoder is not None else
-                                                                       ('cpu' if _lib.IS_CPU_TWIN else 'cuda')))
+        if device is None and decoder is not None:
+            device = decoder.device
+        self.device = ops.default_device(device)
         if decoder is None:
             from .jpeg import JpegDecoder
             decoder = JpegDecoder(self.device)
@@ -499,7 +499,7 @@ class DeviceAudio(object):
     def __init__(self, folder, rate=None, ambi_order=1, device=None):
         import torch
         from scipy.io import wavfile
-        from . import _lib
+        from . import ops
         self.folder = str(folder)
         self.num_files = sum(1 for f in os.listdir(folder) if f.endswith('.wav'))
         if self.num_files == 0:
@@ -536,8 +536,7 @@ class DeviceAudio(object):
         host = np.zeros((self.num_frames, self.num_channels), dtype)
         for i, pcm in enumerate(pieces):
             host[i * per:i * per + pcm.shape[0]] = pcm
-        _lib.lib()
-        self.device = torch.device(device if device is not None else ('cpu' if _lib.IS_CPU_TWIN else 'cuda'))
+        self.device = ops.default_device(device)
         self._samples = torch.as_tensor(host).to(self.device)
 
     def table(self, times, context, size):

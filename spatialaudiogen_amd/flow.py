@@ -75,11 +75,9 @@ class FlowEstimator(object):
     with itself, whose flow is exactly zero.  Nothing is kept between calls."""
 
     def __init__(self, params=None, device=None):
-        from . import _lib
+        from . import ops
         self.params = params if params is not None else FlowParams()
-        _lib.lib()
-        import torch
-        self.device = torch.device(device if device is not None else ('cpu' if _lib.IS_CPU_TWIN else 'cuda'))
+        self.device = ops.default_device(device)
 
     def process(self, frames, prev=None):
         import torch
@@ -102,33 +100,20 @@ def write_flow_folder(video_dir, flow_dir, params=None, block=64, fmt='jpg', dev
     restart_rows (jpg only): rows of MCUs per restart interval of the files written, 0 for none; same files either way."""
     if encode == 'device' and fmt != 'jpg':
         raise ValueError('encode=device writes jpg only (fmt=%s)' % fmt)
-    if restart_rows < 0 or (restart_rows and fmt != 'jpg'):
-        raise ValueError('restart_rows takes 0 or a positive number of MCU rows and belongs to jpg (restart_rows=%d fmt=%s)' % (restart_rows, fmt))
-    import torch
-    from .overlay import frame_names, load_frames
-    from .project import save_frames
+    from . import frames as F, ops
+    writer = F.FrameWriter(flow_dir, fmt, encode, device, restart_rows)       # (its refusals; nothing is loaded or written yet)
     params = params if params is not None else FlowParams()
-    names = frame_names(video_dir)
+    names = F.frame_names(video_dir)
     if not names:
         raise ValueError('%s holds no frame 000000.jpg' % video_dir)
     est = FlowEstimator(params, device)
-    from . import ops
+    reader = F.FrameReader(est.device, decode)
     limits, prev, hw = [], None, None
-    if decode == 'device':
-        from .jpeg import JpegDecoder
-        decoder = JpegDecoder(est.device)
-    if encode == 'device':
-        from .jpeg import JpegEncoder, save_frames_device
-        encoder = JpegEncoder(est.device, restart_rows=restart_rows)  # quality 95, 4:2:0: what save_frames writes
     for first, stop in block_ranges(len(names), block):
         start = first if prev is None else first + 1
-        frames = decoder.decode(names[start:stop]) if decode == 'device' else torch.as_tensor(load_frames(names[start:stop])).to(est.device)
-        flow = est.process(frames, prev)
-        rgb, lim = ops.flow_encode(flow)
-        if encode == 'device':
-            save_frames_device(flow_dir, rgb, start, encoder)
-        else:
-            save_frames(flow_dir, rgb.cpu().numpy(), start, fmt, restart_rows)
+        frames = reader.read(names[start:stop])
+        rgb, lim = ops.flow_encode(est.process(frames, prev))
+        writer.write(rgb, start)
         limits.append(lim.cpu().numpy())
         prev, hw = frames[-1], tuple(frames.shape[1:3])
     np.save(os.path.join(flow_dir, 'flow_limits.npy'), np.concatenate(limits, 0).astype(np.float32))
@@ -136,17 +121,9 @@ def write_flow_folder(video_dir, flow_dir, params=None, block=64, fmt='jpg', dev
 
 
 # ---- command line ---------------------------------------------------------------------------------------------------------------
-def prepare_output_dir(out_dir, overwrite):
-    held = [f for f in os.listdir(out_dir) if f.endswith(('.png', '.jpg')) or f == 'flow_limits.npy'] if os.path.isdir(out_dir) else []
-    if os.path.isdir(out_dir) and os.listdir(out_dir) and not overwrite:
-        raise SystemExit('flow: %s is not empty (--overwrite)' % out_dir)
-    for f in held:
-        os.remove(os.path.join(out_dir, f))
-    os.makedirs(out_dir, exist_ok=True)
-
-
 def parse_arguments(argv=None):
     import argparse
+    from .frames import add_frame_arguments
     parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     parser.add_argument('video_dir', help='Folder of the frames %%06d.jpg.')
     parser.add_argument('flow_dir', help='Folder for the flow frames and flow_limits.npy.')
@@ -155,47 +132,35 @@ def parse_arguments(argv=None):
     parser.add_argument('--iters', type=int, default=30, help='Jacobi iterations per warp')
     parser.add_argument('--alpha', type=float, default=8., help='smoothness weight, in levels of 0..255')
     parser.add_argument('--no_wrap', action='store_true', help='the frames do not close on themselves in x (not equirectangular)')
-    parser.add_argument('--block', type=int, default=64, help='new frames per device call')
     parser.add_argument('--format', default='jpg', choices=['jpg', 'png'], help='jpg (quality 95: what the feeder reads) or png (lossless)')
-    parser.add_argument('--overwrite', action='store_true', help='Whether to replace a flow folder that is not empty.')
-    parser.add_argument('--gpu', type=int, default=0, help='GPU id')
-    parser.add_argument('--decode', default='host', choices=['host', 'device'], help="where the input frames are decoded: host (PIL, one thread) or device (jpeg.py: the files' bytes go to the device; same pixels)")
-    from .project import ENCODE_HELP
-    parser.add_argument('--encode', default='host', choices=['host', 'device'], help=ENCODE_HELP)
-    from .project import RESTART_HELP
-    parser.add_argument('--restart_rows', type=int, default=0, metavar='N', help=RESTART_HELP)
+    add_frame_arguments(parser, block=64, restart_rows=True, block_help='new frames per device call',
+                        overwrite_help='Whether to replace a flow folder that is not empty.')
     return parser.parse_args(argv)
 
 
 def main(argv=None):
     args = parse_arguments(argv)
-    from .overlay import frame_names, check_frame_sizes
+    from . import frames as F
     if args.encode == 'device' and args.format != 'jpg':
         raise SystemExit('flow: --encode device writes jpg only (--format %s)' % args.format)
     if args.block < 1:
         raise SystemExit('flow: --block takes a positive value')
     if not os.path.isdir(args.video_dir):
         raise SystemExit('flow: %s is not a folder' % args.video_dir)
-    names = frame_names(args.video_dir)
+    names = F.frame_names(args.video_dir)
     if not names:
         raise SystemExit('flow: %s holds no frame 000000.jpg' % args.video_dir)
-    check_frame_sizes(names, 'flow')
-    from PIL import Image
-    with Image.open(names[0]) as im:
-        w, h = im.size
+    F.check_frame_sizes(names, 'flow')
+    w, h = F.frame_size(names[0])
     try:
         params = FlowParams(args.levels, args.warps, args.iters, args.alpha, not args.no_wrap)
         levels = params.levels_for(h, w)
     except ValueError as e:
         raise SystemExit('flow: %s' % e)
-    from .project import check_restart_rows
-    check_restart_rows('flow', args.restart_rows, args.format, w)
-    prepare_output_dir(args.flow_dir, args.overwrite)               # every refusal is behind us
-    import torch
-    from . import _lib
-    _lib.lib()
-    if not _lib.IS_CPU_TWIN:
-        torch.cuda.set_device(args.gpu)
+    F.check_restart_rows('flow', args.restart_rows, args.format, w)
+    F.prepare_output_dir(args.flow_dir, args.overwrite, 'flow', ('.png', '.jpg'), extras=('flow_limits.npy',), refuse_any=True)   # every refusal is behind us
+    from . import ops
+    ops.select_device(args.gpu)
     n, h, w, levels = write_flow_folder(args.video_dir, args.flow_dir, params, args.block, args.format, decode=args.decode, encode=args.encode,
                                           restart_rows=args.restart_rows)
     print('wrote %d flow frames of %dx%d to %s (levels %d, warps %d, iters %d)' % (n, h, w, args.flow_dir, levels, params.warps, params.iters))

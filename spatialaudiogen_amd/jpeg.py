@@ -4,7 +4,7 @@ the device gets the file bytes and produces [N, H, W, 3] uint8, byte for byte wh
 
     parse(data)                         -> JpegInfo, JpegUnsupported(reason) outside the scope, ValueError for no JPEG at all
     JpegDecoder(device).decode(items)   -> torch.uint8 [N, H, W, 3] on the device; items: bytes or paths
-    load_frames_device(names, device)   the drop-in for torch.as_tensor(overlay.load_frames(names)).to(device)
+    load_frames_device(names, device)   the drop-in for torch.as_tensor(frames.load_frames(names)).to(device); frames.FrameReader chooses
 
 Scope (the header has the details): SOF0, 8 bit, Huffman, one interleaved scan, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0, optional
 restart interval.  A file outside it is decoded by feeder.imread and copied in, with one warning per decoder.
@@ -19,7 +19,7 @@ produces the entropy-coded data; the header and FF D9 are put around it here.
     JpegEncoder(device, quality, subsampling, restart_rows=0, restart_blocks=0).encode(frames) -> list of bytes; frames uint8
                                         [n, h, w, 3] or [n, h, w] on the device; with a restart interval (sagen_jpeg_encode_rst) the
                                         files are PIL's for restart_marker_rows / restart_marker_blocks
-    save_frames_device(out_dir, frames, first, encoder)      the device form of project.save_frames(..., 'jpg')
+                                        frames.FrameWriter(out_dir, 'jpg', encode='device') puts them into a folder
 
 Files that exist get their restart interval without a pixel being computed (sagen_jpeg_transcode: the decoder's entropy stage into
 coefficients, the encoder's entropy half out of them):
@@ -242,7 +242,7 @@ def decode_packed(packed, staged, out=None):
     """sagen_jpeg_decode on `staged`, the uint8 tensor holding packed.buffer where the library reads (device memory; the host with
     the CPU twin).  Returns (out [n, h, w, 3] uint8, status [n] int32) on that device; nothing is synchronised."""
     import torch
-    from .ops import _ptr, _stream
+    from .ops import _ptr, _scratch64, _stream
     l = _lib.lib()
     w, h, comps, hs, vs = packed.geometry
     n = packed.n
@@ -250,7 +250,7 @@ def decode_packed(packed, staged, out=None):
         out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=staged.device)
     status = torch.empty(n, dtype=torch.int32, device=staged.device)
     nbytes = int(l.sagen_jpeg_decode_scratch_bytes(n, w, h, comps, hs, vs, packed.n_hufftabs))
-    scratch = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=staged.device)
+    scratch = _scratch64(nbytes, staged.device)
     base = staged.data_ptr()
     at = lambda off: C.c_void_p(base + off)
     _lib.check(l.sagen_jpeg_decode(at(packed.bytes_at), packed.total_bytes, at(packed.frames_at), n, at(packed.segments_at), packed.n_segments,
@@ -269,9 +269,8 @@ class JpegDecoder(object):
     dict, receives 'parse' and 'pack' in host seconds of the last call."""
 
     def __init__(self, device=None):
-        import torch
-        _lib.lib()
-        self.device = torch.device(device if device is not None else ('cpu' if _lib.IS_CPU_TWIN else 'cuda'))
+        from .ops import default_device
+        self.device = default_device(device)
         self._warned = False
         self.timing = None
 
@@ -348,7 +347,7 @@ def _host_decode(data):
 
 
 def load_frames_device(names, device=None, decoder=None):
-    """[len(names), H, W, 3] uint8 on the device: what torch.as_tensor(overlay.load_frames(names)).to(device) holds."""
+    """[len(names), H, W, 3] uint8 on the device: what torch.as_tensor(frames.load_frames(names)).to(device) holds."""
     return (decoder or JpegDecoder(device)).decode(list(names))
 
 
@@ -420,7 +419,7 @@ def encode_streams(frames, qtabs, hs, vs, stride, out=None, restart_interval=0):
     natural order (host); with a restart_interval (MCUs, the caller's DRI) sagen_jpeg_encode_rst.  Returns (out [n, stride] uint8,
     sizes [n] int32, status [n] int32) on that device; nothing is synchronised."""
     import torch
-    from .ops import _ptr, _stream
+    from .ops import _ptr, _scratch64, _stream
     l = _lib.lib()
     if frames.dtype != torch.uint8 or frames.dim() not in (3, 4) or (frames.dim() == 4 and frames.shape[3] != 3):
         raise TypeError('frames must be uint8 [n, h, w, 3] (RGB) or [n, h, w] (grey)')
@@ -437,12 +436,12 @@ def encode_streams(frames, qtabs, hs, vs, stride, out=None, restart_interval=0):
         if not 0 < int(restart_interval) <= 65535:
             raise ValueError('a restart interval of %d MCUs is outside 0..65535 (what DRI can name)' % restart_interval)
         nbytes = int(l.sagen_jpeg_encode_rst_scratch_bytes(n, w, h, comps, hs, vs, int(restart_interval), stride))
-        scratch = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=dev)
+        scratch = _scratch64(nbytes, dev)
         _lib.check(l.sagen_jpeg_encode_rst(_ptr(frames), n, w, h, comps, hs, vs, int(restart_interval), _ptr(zz), _ptr(out), stride, _ptr(sizes),
                                            _ptr(status), _ptr(scratch), nbytes, _stream()))
         return out, sizes, status
     nbytes = int(l.sagen_jpeg_encode_scratch_bytes(n, w, h, comps, hs, vs, stride))
-    scratch = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=dev)
+    scratch = _scratch64(nbytes, dev)
     _lib.check(l.sagen_jpeg_encode(_ptr(frames), n, w, h, comps, hs, vs, _ptr(zz), _ptr(out), stride, _ptr(sizes), _ptr(status), _ptr(scratch),
                                    nbytes, _stream()))
     return out, sizes, status
@@ -456,30 +455,21 @@ class JpegEncoder(object):
     hold a DRI segment and restart markers, and the device decoder reads them with one lane per segment."""
 
     def __init__(self, device=None, quality=95, subsampling='4:2:0', stride=None, restart_rows=0, restart_blocks=0):
-        import torch
+        from .ops import default_device
         _lib.lib()
         if subsampling not in SUBSAMPLING:
             raise ValueError('subsampling %r is none of %s' % (subsampling, ', '.join(sorted(SUBSAMPLING))))
-        self.device = torch.device(device if device is not None else ('cpu' if _lib.IS_CPU_TWIN else 'cuda'))
+        self.device = default_device(device)
         self.quality, self.subsampling, self.stride = quality, subsampling, stride
         if restart_rows < 0 or restart_blocks < 0:
             raise ValueError('restart_rows and restart_blocks must not be negative')
         self.restart_rows, self.restart_blocks = int(restart_rows), int(restart_blocks)
         self.qtabs = quality_tables(quality)
 
-    def _fetch(self, out, longest):
-        """out[:, :longest] on the host, through a pinned buffer"""
-        import torch
-        if out.device.type != 'cuda':
-            return out[:, :longest].numpy()
-        pinned = torch.empty((out.shape[0], longest), dtype=torch.uint8, pin_memory=True)
-        pinned.copy_(out[:, :longest], non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        return pinned.numpy()
-
     def encode(self, frames, first=0):
         """`first`: the number of frames[0], for the message of a frame that cannot be coded."""
         import torch
+        from .ops import encode_with_retry
         if not isinstance(frames, torch.Tensor) or frames.device.type != self.device.type:
             raise TypeError('frames must be a uint8 tensor on %s' % self.device)
         n = int(frames.shape[0])
@@ -491,22 +481,15 @@ class JpegEncoder(object):
         stride = self.stride if self.stride is not None else max((w * h * comps + 63) // 64 * 64, 4096)
         rst = restart_interval_of(w, h, comps, hs, vs, self.restart_rows, self.restart_blocks)
         head = encode_header(w, h, comps, hs, vs, self.qtabs, rst)
-        out, sizes, status = encode_streams(frames, self.qtabs, hs, vs, stride, restart_interval=rst)
-        both = torch.stack([sizes, status], 0).cpu().numpy()                      # the one copy of both
-        sizes, status = both[0], both[1]
-        for f in np.flatnonzero(status & _lib.SAGEN_JPEG_ENC_ST_RANGE):
-            raise ValueError('frame %d: a coefficient outside what baseline JPEG can code (DC category > 11 or AC category > 10)' % (first + f))
-        longest = int(min(sizes.max(), stride))
-        data = self._fetch(out, longest) if longest else np.zeros((n, 0), np.uint8)
-        files = [head + data[f, :sizes[f]].tobytes() + b'\xff\xd9' for f in range(n)]
-        for f in np.flatnonzero(status & _lib.SAGEN_JPEG_ENC_ST_CAPACITY):
-            bound = (int(_lib.lib().sagen_jpeg_encode_rst_max_bytes(w, h, comps, hs, vs, rst)) + 3) // 4 * 4
-            o, sz, st = encode_streams(frames[f:f + 1], self.qtabs, hs, vs, bound, restart_interval=rst)
-            sz, st = int(sz.cpu()[0]), int(st.cpu()[0])
-            if st:
-                raise RuntimeError('frame %d: status %d at the stride that cannot be too small' % (first + f, st))
-            files[f] = head + self._fetch(o, sz)[0].tobytes() + b'\xff\xd9'
-        return files
+        bound = (int(_lib.lib().sagen_jpeg_encode_rst_max_bytes(w, h, comps, hs, vs, rst)) + 3) // 4 * 4
+
+        def run(part, at):
+            return encode_streams(frames[part], self.qtabs, hs, vs, at, restart_interval=rst)
+
+        def out_of_range(f, st):
+            return ValueError('frame %d: a coefficient outside what baseline JPEG can code (DC category > 11 or AC category > 10)' % (first + f))
+        return encode_with_retry(run, n, stride, bound, _lib.SAGEN_JPEG_ENC_ST_CAPACITY, wrap=lambda stream, f: head + stream + b'\xff\xd9',
+                                 fatal=_lib.SAGEN_JPEG_ENC_ST_RANGE, fatal_error=out_of_range, label=lambda f: 'frame %d' % (first + f))
 
 
 # ---- re-segmenting files that exist ------------------------------------------------------------------------------------------------------
@@ -543,7 +526,7 @@ def transcode_streams(packed, staged, restart_interval, stride):
     """sagen_jpeg_transcode on `staged`, the uint8 tensor holding packed.buffer where the library reads.  Returns (out [n, stride] uint8,
     sizes [n] int32, status [n] int32) on that device; nothing is synchronised."""
     import torch
-    from .ops import _ptr, _stream
+    from .ops import _ptr, _scratch64, _stream
     l = _lib.lib()
     w, h, comps, hs, vs = packed.geometry
     n = packed.n
@@ -551,7 +534,7 @@ def transcode_streams(packed, staged, restart_interval, stride):
     sizes = torch.empty(n, dtype=torch.int32, device=staged.device)
     status = torch.empty(n, dtype=torch.int32, device=staged.device)
     nbytes = int(l.sagen_jpeg_transcode_scratch_bytes(n, w, h, comps, hs, vs, packed.n_hufftabs, restart_interval, stride))
-    scratch = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=staged.device)
+    scratch = _scratch64(nbytes, staged.device)
     at = lambda off: C.c_void_p(staged.data_ptr() + off)
     _lib.check(l.sagen_jpeg_transcode(at(packed.bytes_at), packed.total_bytes, at(packed.frames_at), n, at(packed.segments_at), packed.n_segments,
                                       at(packed.hufftabs_at), packed.n_hufftabs, w, h, comps, hs, vs, restart_interval, _ptr(out), stride,
@@ -571,8 +554,8 @@ def transcode_files(datas, restart_rows=1, device=None, restart_blocks=0, names=
     (transcode_header).  A file outside the decoder's scope is passed through byte for byte, with one JpegFallbackWarning per call.
     A damaged file raises IOError."""
     import torch
-    _lib.lib()
-    device = torch.device(device if device is not None else ('cpu' if _lib.IS_CPU_TWIN else 'cuda'))
+    from .ops import default_device, encode_with_retry
+    device = default_device(device)
     datas = [bytes(d) for d in datas]
     names = names or ['<item %d>' % k for k in range(len(datas))]
     result, groups, warned = list(datas), collections.OrderedDict(), False
@@ -588,26 +571,24 @@ def transcode_files(datas, restart_rows=1, device=None, restart_blocks=0, names=
         w, h, comps, hs, vs = geometry
         rst = restart_interval_of(w, h, comps, hs, vs, restart_rows, restart_blocks)
         idx, infos = [k for k, _ in members], [i for _, i in members]
-        packed = pack([datas[k] for k in idx], infos)
-        staged = torch.as_tensor(packed.buffer).to(device)
         bound = (int(_lib.lib().sagen_jpeg_transcode_max_bytes(w, h, comps, hs, vs, rst)) + 3) // 4 * 4
         mcus = -(-w // (8 * hs)) * -(-h // (8 * vs))
         # the standard tables can be longer than a file's own: half as much again, the markers and their fills, and a floor
         stride = min(bound, (max(i.scan_bytes for i in infos) * 3 // 2 + 4 * mcus + 4096 + 63) // 64 * 64)
-        out, sizes, status = transcode_streams(packed, staged, rst, stride)
-        both = torch.stack([sizes, status], 0).cpu().numpy()
-        sizes, status = both[0], both[1]
-        longest = int(min(sizes.max(), stride))
-        data = out[:, :longest].cpu().numpy()
+
+        def run(part, at):
+            packed = pack([datas[k] for k in idx[part]], infos[part])
+            return transcode_streams(packed, torch.as_tensor(packed.buffer).to(device), rst, at)
+
+        def wrap(stream, j):
+            return transcode_header(datas[idx[j]], infos[j], rst) + stream + b'\xff\xd9'
+
+        def damaged(j, st):
+            return IOError('%s: the JPEG stream cannot be re-segmented (%s)' % (names[idx[j]], transcode_status_text(st)))
+        capacity = _lib.SAGEN_JPEG_ENC_ST_CAPACITY << 8                         # by itself: with any other bit the file is damaged
+        done = encode_with_retry(run, len(idx), stride, bound, capacity, wrap, fatal=~capacity, fatal_error=damaged, label=lambda j: names[idx[j]])
         for j, k in enumerate(idx):
-            st, stream = int(status[j]), None
-            if st == _lib.SAGEN_JPEG_ENC_ST_CAPACITY << 8:               # alone, at the stride that cannot be too small
-                one = pack([datas[k]], [infos[j]])
-                o, sz, s1 = transcode_streams(one, torch.as_tensor(one.buffer).to(device), rst, bound)
-                st, stream = int(s1.cpu()[0]), o[0, :int(sz.cpu()[0])].cpu().numpy().tobytes()
-            if st:
-                raise IOError('%s: the JPEG stream cannot be re-segmented (%s)' % (names[k], transcode_status_text(st)))
-            result[k] = transcode_header(datas[k], infos[j], rst) + (stream if stream is not None else data[j, :sizes[j]].tobytes()) + b'\xff\xd9'
+            result[k] = done[j]
     return result
 
 
@@ -643,10 +624,8 @@ def main(argv=None):
     held = [f for f in os.listdir(args.out_dir) if f.lower().endswith(('.jpg', '.jpeg'))] if os.path.isdir(args.out_dir) else []
     if held and not args.overwrite:
         raise SystemExit('jpeg restart: %s already holds frames (--overwrite)' % args.out_dir)
-    import torch
-    _lib.lib()
-    if not _lib.IS_CPU_TWIN:
-        torch.cuda.set_device(args.gpu)
+    from .ops import select_device
+    select_device(args.gpu)
     for f in held:
         os.remove(os.path.join(args.out_dir, f))
     os.makedirs(args.out_dir, exist_ok=True)
@@ -666,14 +645,6 @@ def main(argv=None):
                 fh.write(d)
         before, after = before + sum(len(d) for d in datas), after + sum(len(d) for d in done)
     print('wrote %d files to %s: %d bytes before, %d after (%+.2f %%)' % (len(files), args.out_dir, before, after, 100. * (after - before) / before))
-
-
-def save_frames_device(out_dir, frames, first, encoder):
-    """frames (uint8 [n, h, w, 3] on the encoder's device) -> out_dir/%06d.jpg from `first` on: project.save_frames without the raw copy."""
-    import os
-    for i, data in enumerate(encoder.encode(frames, first)):
-        with open(os.path.join(out_dir, '%06d.jpg' % (first + i)), 'wb') as f:
-            f.write(data)
 
 
 if __name__ == '__main__':

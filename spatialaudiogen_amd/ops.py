@@ -4,6 +4,8 @@ of myutils.stft / istft (myutils.py:119-211).  Tensors are torch CUDA fp32, NHWC
 torch is only the owner of device memory and streams here; all arithmetic is in libsagen_hip.so.
 """
 import ctypes as C
+
+import numpy as np
 import torch
 
 from . import _lib
@@ -33,8 +35,62 @@ def _f32(t, name):
     return t.contiguous()
 
 
+def default_device(device=None):
+    """torch.device(device); None: where the library computes - 'cuda', or 'cpu' under the CPU twin.  Loads the library either way."""
+    twin = _twin()
+    return torch.device(device if device is not None else ('cpu' if twin else 'cuda'))
+
+
+def select_device(gpu):
+    """What a command line does once every refusal is behind it: load the library and make `gpu` the current device (the CPU twin has none)."""
+    if not _twin():
+        torch.cuda.set_device(gpu)
+
+
 def _scratch(nbytes, dev):
     return torch.empty((int(nbytes) + 255) // 256 * 64, dtype=torch.float32, device=dev)
+
+
+def _scratch64(nbytes, dev):
+    """nbytes rounded up to 16, in 8-byte elements: the alignment the media ops' entry points check"""
+    return torch.empty((int(nbytes) + 15) // 16 * 2, dtype=torch.float64, device=dev)
+
+
+def fetch_rows(out, longest):
+    """out[:, :longest] on the host, through a pinned buffer"""
+    if out.device.type != 'cuda':
+        return out[:, :longest].numpy()
+    pinned = torch.empty((out.shape[0], longest), dtype=torch.uint8, pin_memory=True)
+    pinned.copy_(out[:, :longest], non_blocking=True)
+    torch.cuda.current_stream().synchronize()
+    return pinned.numpy()
+
+
+def encode_with_retry(run, n, stride, bound, capacity, wrap, fatal=0, fatal_error=None, label=lambda k: 'frame %d' % k):
+    """The protocol of the encoders that write n byte streams of unknown length into rows of `stride` bytes (jpeg.JpegEncoder, png.PngEncoder,
+    jpeg.transcode_files): run(slice, stride) -> (out [k, stride] uint8, sizes [k] int32, status [k] int32) on the device, nothing
+    synchronised.  One run of the whole block at `stride`, one copy of sizes + status, one copy of the streams cut at the longest; an item
+    with the `capacity` bit did not fit and is run again, by itself, at `bound`, the stride that cannot be too small.
+    An item with a bit of the `fatal` mask raises fatal_error(k, status), in the block call before anything is fetched.  Returns
+    [wrap(stream bytes, k)]; label(k) names item k where a status persists at the bound."""
+    out, sizes, status = run(slice(0, n), stride)
+    both = torch.stack([sizes, status], 0).cpu().numpy()                      # the one copy of both
+    sizes, status = both[0], both[1]
+    for k in np.flatnonzero(status & fatal):
+        raise fatal_error(int(k), int(status[k]))
+    longest = int(min(sizes.max(), stride))
+    data = fetch_rows(out, longest) if longest else np.zeros((n, 0), np.uint8)
+    files = [wrap(data[k, :sizes[k]].tobytes(), k) for k in range(n)]
+    for k in np.flatnonzero(status & capacity):
+        k = int(k)
+        o, sz, st = run(slice(k, k + 1), bound)
+        sz, st = int(sz.cpu()[0]), int(st.cpu()[0])
+        if st & fatal:
+            raise fatal_error(k, st)
+        if st:
+            raise RuntimeError('%s: status %d at the stride that cannot be too small' % (label(k), st))
+        files[k] = wrap(fetch_rows(o, sz)[0].tobytes(), k)
+    return files
 
 
 def stft_mag(audio, f0, f1, c0=None, c1=None):

@@ -17,8 +17,6 @@ IN_AMBIX.wav holds 4 or 9 channels (ACN / SN3D, orders 1 and 2), FRAMES_DIR the 
 Two quirks of the reference are kept: the first map is only ever `prev` (nothing is blended with beta < 0 before it), and
 5 (n_maps - 1) frames are written - the frames of the last half second, and any frame past the audio, are not.
 """
-import os
-
 import numpy as np
 
 from . import ambisonics
@@ -63,14 +61,11 @@ class Overlay(object):
     returned: frames past that stay pending."""
 
     def __init__(self, channels, audio_rate=48000, video_rate=10, angular_res=5.0, decimate=5, frames_per_map=5, device=None):
-        import torch
-        from . import _lib
         if channels not in (4, 9):
             raise ValueError('%d channels is not first- or second-order ambisonics (4 or 9)' % channels)
-        _lib.lib()
-        if device is None:
-            device = 'cpu' if _lib.IS_CPU_TWIN else 'cuda'
-        self.device = torch.device(device)
+        import torch
+        from . import ops
+        self.device = ops.default_device(device)
         self.channels, self.decimate, self.frames_per_map = int(channels), int(decimate), int(frames_per_map)
         # SphericalAmbisonicsVisualizer(ambix[::5], rate / 5., 5. / fps, 5.): window_frames = int(window * rate) (distance.py:29)
         self.window = int(frames_per_map / float(video_rate) * (audio_rate / float(decimate)))
@@ -148,66 +143,23 @@ class Overlay(object):
 
 
 # ---- command line ---------------------------------------------------------------------------------------------------------------
-def frame_names(folder):
-    """The %06d.jpg frames of a folder from 000000 on, in order."""
-    names = []
-    while os.path.exists(os.path.join(folder, '%06d.jpg' % len(names))):
-        names.append(os.path.join(folder, '%06d.jpg' % len(names)))
-    return names
-
-
-def check_frame_sizes(names, tool='overlay'):
-    """Refuse frames of differing sizes from the files' headers alone (nothing is decoded)."""
-    from PIL import Image
-    first = None
-    for n in names:
-        with Image.open(n) as im:
-            size = im.size
-        first = first or size
-        if size != first:
-            raise SystemExit('%s: %s is %dx%d, the first frame %dx%d (all frames must have one size)' % ((tool, n) + size + first))
-
-
-def load_frames(names):
-    from .feeder import imread
-    return np.stack([imread(n) for n in names], 0)
-
-
-def save_frames(out_dir, frames, first=0):
-    from PIL import Image
-    for i, f in enumerate(frames):
-        Image.fromarray(f).save(os.path.join(out_dir, '%06d.png' % (first + i)))
-
-
-def prepare_output_dir(out_dir, overwrite, tool='overlay'):
-    if os.path.isdir(out_dir) and any(f.endswith('.png') for f in os.listdir(out_dir)):
-        if not overwrite:
-            raise SystemExit('%s: %s already holds frames (--overwrite)' % (tool, out_dir))
-        for f in os.listdir(out_dir):
-            if f.endswith('.png'):
-                os.remove(os.path.join(out_dir, f))
-    os.makedirs(out_dir, exist_ok=True)
-
-
 def parse_arguments(argv=None):
     import argparse
+    from .frames import add_frame_arguments
     parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     parser.add_argument('input_fn', help='Input ambisonics file (ACN / SN3D, 4 or 9 channels).')
     parser.add_argument('frames_dir', help='Folder of the frames %%06d.jpg, 10 per second.')
     parser.add_argument('output_dir', help='Folder for the blended frames %%06d.png.')
     parser.add_argument('--angular_res', type=float, default=5., help='mesh step of the maps in degrees')
     parser.add_argument('--save_maps', default=None, metavar='FILE.npz', help='also write the raw maps [n, rows, columns]')
-    parser.add_argument('--overwrite', action='store_true', help='Whether to replace frames already in the output folder.')
-    parser.add_argument('--gpu', type=int, default=0, help='GPU id')
-    parser.add_argument('--block', type=int, default=50, help='frames per device call')
-    parser.add_argument('--decode', default='host', choices=['host', 'device'], help="where the input frames are decoded: host (PIL, one thread) or device (jpeg.py: the files' bytes go to the device; same pixels)")
-    parser.add_argument('--encode', default='host', choices=['host', 'device'], help="where the output frames are compressed: host (PIL, one thread) or device (png.py: the files' bytes come back instead of the pixels; other bytes, the same pixels)")
+    add_frame_arguments(parser, block=50, encode_help="where the output frames are compressed: host (PIL, one thread) or device (png.py: the files' "
+                                                      "bytes come back instead of the pixels; other bytes, the same pixels)")
     return parser.parse_args(argv)
 
 
 def main(argv=None):
     import torch
-    from . import _lib
+    from . import frames as F
     from .feeder import load_wav
     args = parse_arguments(argv)
     data, rate = load_wav(args.input_fn)
@@ -215,33 +167,20 @@ def main(argv=None):
         raise SystemExit('overlay: %d channels is not first- or second-order ambisonics (4 or 9)' % data.shape[1])
     if args.block < 1 or not args.angular_res > 0:
         raise SystemExit('overlay: --block and --angular_res take positive values')
-    if os.path.isdir(args.output_dir) and any(f.endswith('.png') for f in os.listdir(args.output_dir)) and not args.overwrite:
-        raise SystemExit('overlay: %s already holds frames (--overwrite)' % args.output_dir)
-    names = frame_names(args.frames_dir)
-    check_frame_sizes(names)
-    prepare_output_dir(args.output_dir, args.overwrite)             # every refusal is behind us
+    names = F.frame_names(args.frames_dir)
+    F.check_frame_sizes(names, 'overlay')
+    F.prepare_output_dir(args.output_dir, args.overwrite, 'overlay')        # every refusal is behind us
     # only the frames that will be written are decoded, a block at a time: the host holds --block frames whatever the clip's length
     names = names[:emitted_frames(data.shape[0], len(names), audio_rate=rate)[1]]
-    _lib.lib()
-    if not _lib.IS_CPU_TWIN:
-        torch.cuda.set_device(args.gpu)
+    from . import ops
+    ops.select_device(args.gpu)
     ov = Overlay(data.shape[1], audio_rate=rate, angular_res=args.angular_res)
     ov.process(torch.as_tensor(data.astype(np.float32)).to(ov.device), None)
+    reader, writer = F.FrameReader(ov.device, args.decode), F.FrameWriter(args.output_dir, 'png', args.encode, ov.device)
     written = 0
-    if args.decode == 'device':
-        from .jpeg import JpegDecoder
-        decoder = JpegDecoder(ov.device)
-    if args.encode == 'device':
-        from .png import PngEncoder, save_frames_device
-        encoder = PngEncoder(ov.device)
     for i in range(0, len(names), args.block):
-        block = names[i:i + args.block]
-        frames = decoder.decode(block) if args.decode == 'device' else torch.as_tensor(load_frames(block)).to(ov.device)
-        out = ov.process(None, frames)
-        if args.encode == 'device':
-            save_frames_device(args.output_dir, out, written, encoder)
-        else:
-            save_frames(args.output_dir, out.cpu().numpy(), written)
+        out = ov.process(None, reader.read(names[i:i + args.block]))
+        writer.write(out, written)
         written += out.shape[0]
     if args.save_maps:
         np.savez(args.save_maps, maps=ov.maps().cpu().numpy())

@@ -8,12 +8,10 @@ host thread.  This module is the device path (include/sagen.h: sagen_png_filter,
     png_file(w, h, c, stream)               signature, IHDR, one IDAT, IEND; the chunk CRCs are zlib.crc32 on the host
 
 8 bit, RGB or grey, no interlace.  The files' bytes differ from PIL's; every file decodes to the pixels it was given.
+frames.FrameWriter(out_dir, 'png', encode='device') puts the files of PngEncoder into a folder.
 """
-import os
 import struct
 import zlib
-
-import numpy as np
 
 from . import _lib
 
@@ -45,7 +43,7 @@ def deflate(rows, stride=None, out=None):
     string.  Returns (out [n, stride] uint8, sizes [n] int32, status [n] int32) on that device; nothing is synchronised.  stride: None
     for the bound."""
     import torch
-    from .ops import _ptr, _stream
+    from .ops import _ptr, _scratch64, _stream
     l = _lib.lib()
     if not isinstance(rows, torch.Tensor) or rows.dtype != torch.uint8 or rows.dim() < 1:
         raise TypeError('rows must be a uint8 tensor [n, ...]')
@@ -60,7 +58,7 @@ def deflate(rows, stride=None, out=None):
     sizes = torch.empty(n, dtype=torch.int32, device=dev)
     status = torch.empty(n, dtype=torch.int32, device=dev)
     nbytes = int(l.sagen_deflate_scratch_bytes(n, length, stride))
-    scratch = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.float64, device=dev)
+    scratch = _scratch64(nbytes, dev)
     _lib.check(l.sagen_deflate(_ptr(rows) if length else None, n, length, _ptr(out), stride, _ptr(sizes), _ptr(status), _ptr(scratch), nbytes,
                                _stream()))
     return out, sizes, status
@@ -85,24 +83,14 @@ class PngEncoder(object):
     stream either way)."""
 
     def __init__(self, device=None, stride=None):
-        import torch
-        _lib.lib()
-        self.device = torch.device(device if device is not None else ('cpu' if _lib.IS_CPU_TWIN else 'cuda'))
+        from .ops import default_device
+        self.device = default_device(device)
         self.stride = stride
-
-    def _fetch(self, out, longest):
-        """out[:, :longest] on the host, through a pinned buffer"""
-        import torch
-        if out.device.type != 'cuda':
-            return out[:, :longest].numpy()
-        pinned = torch.empty((out.shape[0], longest), dtype=torch.uint8, pin_memory=True)
-        pinned.copy_(out[:, :longest], non_blocking=True)
-        torch.cuda.current_stream().synchronize()
-        return pinned.numpy()
 
     def encode(self, frames, first=0):
         """`first`: the number of frames[0], for the message of a frame that cannot be coded."""
         import torch
+        from .ops import encode_with_retry
         if not isinstance(frames, torch.Tensor) or frames.device.type != self.device.type:
             raise TypeError('frames must be a uint8 tensor on %s' % self.device)
         n = int(frames.shape[0])
@@ -111,29 +99,6 @@ class PngEncoder(object):
         rows = filter_rows(frames)
         h, w = int(frames.shape[1]), int(frames.shape[2])
         comps = 3 if frames.dim() == 4 else 1
-        length = h * (1 + w * comps)
-        stride = self.stride if self.stride is not None else max_bytes(length)
-        out, sizes, status = deflate(rows, stride)
-        both = torch.stack([sizes, status], 0).cpu().numpy()                      # the one copy of both
-        sizes, status = both[0], both[1]
-        longest = int(min(sizes.max(), stride))
-        data = self._fetch(out, longest)
-        files = [png_file(w, h, comps, data[f, :sizes[f]].tobytes()) for f in range(n)]
-        for f in np.flatnonzero(status & _lib.SAGEN_DEFLATE_ST_CAPACITY):
-            o, sz, st = deflate(rows[f:f + 1])
-            sz, st = int(sz.cpu()[0]), int(st.cpu()[0])
-            if st:
-                raise RuntimeError('frame %d: status %d at the stride that cannot be too small' % (first + f, st))
-            files[f] = png_file(w, h, comps, self._fetch(o, sz)[0].tobytes())
-        return files
-
-
-def save_frames_device(out_dir, frames, first, encoder):
-    """frames (uint8 [n, h, w, 3] on the encoder's device) -> out_dir/%06d.png from `first` on: overlay.save_frames without the raw copy.
-    Returns the files' names."""
-    names = []
-    for i, data in enumerate(encoder.encode(frames, first)):
-        names.append(os.path.join(out_dir, '%06d.png' % (first + i)))
-        with open(names[-1], 'wb') as f:
-            f.write(data)
-    return names
+        bound = max_bytes(h * (1 + w * comps))
+        return encode_with_retry(lambda part, at: deflate(rows[part], at), n, self.stride if self.stride is not None else bound, bound,
+                                 _lib.SAGEN_DEFLATE_ST_CAPACITY, wrap=lambda stream, f: png_file(w, h, comps, stream), label=lambda f: 'frame %d' % (first + f))

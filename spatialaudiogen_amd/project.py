@@ -192,16 +192,14 @@ class Projector(object):
     kept between calls: a clip cut into pieces gives the frames of the whole.  supersample None: auto_supersample per source size."""
 
     def __init__(self, src, dst, size, supersample=None, device=None):
-        from . import _lib
         if src.kind == 'view':
             raise ValueError('a perspective view cannot be a source')
         if supersample is not None and not 1 <= int(supersample) <= 8:
             raise ValueError('supersample takes 1..8')
         self.src, self.dst, self.size, self.supersample = src, dst, (int(size[0]), int(size[1])), supersample
         self.dst_struct = dst.struct(*self.size)
-        _lib.lib()
-        import torch
-        self.device = torch.device(device if device is not None else ('cpu' if _lib.IS_CPU_TWIN else 'cuda'))
+        from . import ops
+        self.device = ops.default_device(device)
 
     def process(self, frames, rotation=None):
         import torch
@@ -223,49 +221,6 @@ SOURCES = {'er': lambda: equirect(), 'er_tb': lambda: equirect('top_bottom'), 'c
 TARGETS = {'er': equirect, 'cube': cubemap3x2, 'eac': eac3x2}
 
 
-def save_frames(out_dir, frames, first, fmt, restart_rows=0):
-    """restart_rows (jpg only): a restart interval of that many rows of MCUs, PIL's restart_marker_rows; 0: none, the files as ever."""
-    if fmt == 'png':
-        if restart_rows:
-            raise ValueError('restart_rows belongs to jpg (fmt=png)')
-        from .overlay import save_frames as save_png
-        return save_png(out_dir, frames, first)
-    from PIL import Image
-    extra = dict(restart_marker_rows=int(restart_rows)) if restart_rows else {}
-    for i, f in enumerate(frames):
-        Image.fromarray(f).save(os.path.join(out_dir, '%06d.jpg' % (first + i)), quality=95, **extra)
-
-
-RESTART_HELP = ("rows of MCUs (16 pixel rows at 4:2:0) per restart interval of the jpg files written, 0: none (--format jpg only).  The device "
-                "decoder (--decode device) runs one lane per restart segment, so it reads such a folder in parallel inside each frame; every "
-                "other reader sees the same pixels.  The same files with --encode host (PIL's restart_marker_rows) and --encode device.")
-
-
-def check_restart_rows(tool, restart_rows, fmt, w):
-    """the refusals of --restart_rows, in front of any file: negative, png, or an interval DRI cannot name (16 x 16 MCUs: 4:2:0)"""
-    if restart_rows < 0:
-        raise SystemExit('%s: --restart_rows takes 0 or a positive number of MCU rows' % tool)
-    if restart_rows and fmt != 'jpg':
-        raise SystemExit('%s: --restart_rows belongs to --format jpg (--format %s)' % (tool, fmt))
-    if restart_rows * (-(-w // 16)) > 65535:
-        raise SystemExit('%s: --restart_rows %d at %d MCUs per row is an interval above 65535 MCUs, the most a JPEG file can name'
-                         % (tool, restart_rows, -(-w // 16)))
-
-
-ENCODE_HELP = ("where the output frames are encoded (--format jpg only): host (PIL, one thread, after the raw frames came back) or device "
-               "(jpeg.py: only the files' bytes leave the device; the same files).  Measured on one MI355X, 224x448 at quality 95 (profiles/jpeg_encode_rate.jsonl): host 2 949 frames/s; device 44 575 in blocks of 16, "
-               "91 255 in blocks of 64, 111 778 in blocks of 256: it pays from --block 16, the smallest measured, up.")
-
-
-def prepare_output_dir(out_dir, overwrite):
-    held = [f for f in os.listdir(out_dir) if f.endswith(('.png', '.jpg'))] if os.path.isdir(out_dir) else []
-    if held and not overwrite:
-        raise SystemExit('project: %s already holds frames (--overwrite)' % out_dir)
-    for f in held:
-        os.remove(os.path.join(out_dir, f))
-    os.makedirs(out_dir, exist_ok=True)
-
-
 def frame_angles(values, n):
     """One angle per frame from the command line's control points: one value holds, several are spread evenly over the clip."""
     v = np.asarray(values, np.float64)
@@ -274,6 +229,7 @@ def frame_angles(values, n):
 
 def parse_arguments(argv=None):
     import argparse
+    from .frames import add_frame_arguments
     parser = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     parser.add_argument('input_dir', help='Folder of the frames %%06d.jpg.')
     parser.add_argument('output_dir', help='Folder for the reprojected frames.')
@@ -286,21 +242,16 @@ def parse_arguments(argv=None):
                             help='head %s in degrees: one value, or control points spread evenly over the clip' % name)
     parser.add_argument('--supersample', type=int, default=None, metavar='S', help='sub-samples per pixel and axis, 1..8 (default: from the sizes)')
     parser.add_argument('--format', default='jpg', choices=['jpg', 'png'], help='jpg (quality 95: what deploy and overlay read) or png (lossless)')
-    parser.add_argument('--overwrite', action='store_true', help='Whether to replace frames already in the output folder.')
-    parser.add_argument('--gpu', type=int, default=0, help='GPU id')
-    parser.add_argument('--block', type=int, default=16, help='frames per device call')
-    parser.add_argument('--decode', default='host', choices=['host', 'device'], help="where the input frames are decoded: host (PIL, one thread) or device (jpeg.py: the files' bytes go to the device; same pixels)")
-    parser.add_argument('--encode', default='host', choices=['host', 'device'], help=ENCODE_HELP)
-    parser.add_argument('--restart_rows', type=int, default=0, metavar='N', help=RESTART_HELP)
+    add_frame_arguments(parser, block=16, restart_rows=True)
     return parser.parse_args(argv)
 
 
 def main(argv=None):
     args = parse_arguments(argv)
-    from .overlay import frame_names, check_frame_sizes, load_frames
+    from . import frames as F
     if args.encode == 'device' and args.format != 'jpg':
         raise SystemExit('project: --encode device writes jpg only (--format %s)' % args.format)
-    check_restart_rows('project', args.restart_rows, args.format, args.size[1])
+    F.check_restart_rows('project', args.restart_rows, args.format, args.size[1])
     if args.dst == 'view' and args.hfov is None:
         raise SystemExit('project: --to view needs --hfov')
     if args.dst != 'view' and args.hfov is not None:
@@ -311,13 +262,11 @@ def main(argv=None):
         raise SystemExit('project: --block takes a positive value')
     if not os.path.isdir(args.input_dir):
         raise SystemExit('project: %s is not a folder' % args.input_dir)
-    names = frame_names(args.input_dir)
+    names = F.frame_names(args.input_dir)
     if not names:
         raise SystemExit('project: %s holds no frame 000000.jpg' % args.input_dir)
-    check_frame_sizes(names, 'project')
-    from PIL import Image
-    with Image.open(names[0]) as im:
-        w, h = im.size
+    F.check_frame_sizes(names, 'project')
+    w, h = F.frame_size(names[0])
     try:
         src = SOURCES[args.src]()
         dst = perspective(args.hfov) if args.dst == 'view' else TARGETS[args.dst]()
@@ -325,32 +274,18 @@ def main(argv=None):
         dst.check(*args.size)
     except ValueError as e:
         raise SystemExit('project: %s' % e)
-    if os.path.isdir(args.output_dir) and any(f.endswith(('.png', '.jpg')) for f in os.listdir(args.output_dir)) and not args.overwrite:
-        raise SystemExit('project: %s already holds frames (--overwrite)' % args.output_dir)
-    prepare_output_dir(args.output_dir, args.overwrite)             # every refusal is behind us
-    import torch
-    from . import _lib
-    _lib.lib()
-    if not _lib.IS_CPU_TWIN:
-        torch.cuda.set_device(args.gpu)
+    F.prepare_output_dir(args.output_dir, args.overwrite, 'project', ('.png', '.jpg'))      # every refusal is behind us
+    from . import ops
+    ops.select_device(args.gpu)
     n = len(names)
     turned = any(np.any(np.asarray(getattr(args, k)) != 0.) for k in ('yaw', 'pitch', 'roll'))
     rot = view_trajectory(frame_angles(args.yaw, n), frame_angles(args.pitch, n), frame_angles(args.roll, n)) if turned else None
     pr = Projector(src, dst, args.size, args.supersample)
-    if args.decode == 'device':
-        from .jpeg import JpegDecoder
-        decoder = JpegDecoder(pr.device)
-    if args.encode == 'device':
-        from .jpeg import JpegEncoder, save_frames_device
-        encoder = JpegEncoder(pr.device, restart_rows=args.restart_rows)     # quality 95, 4:2:0: what save_frames writes
+    reader = F.FrameReader(pr.device, args.decode)
+    writer = F.FrameWriter(args.output_dir, args.format, args.encode, pr.device, args.restart_rows)
     for i in range(0, n, args.block):
-        block = names[i:i + args.block]
-        frames = decoder.decode(block) if args.decode == 'device' else torch.as_tensor(load_frames(block)).to(pr.device)
-        out = pr.process(frames, None if rot is None else rot[i:i + args.block])
-        if args.encode == 'device':
-            save_frames_device(args.output_dir, out, i, encoder)
-        else:
-            save_frames(args.output_dir, out.cpu().numpy(), i, args.format, args.restart_rows)
+        out = pr.process(reader.read(names[i:i + args.block]), None if rot is None else rot[i:i + args.block])
+        writer.write(out, i)
     S = pr.supersample or auto_supersample(src, (h, w), dst, pr.size)
     print('wrote %d frames of %dx%d to %s (%s -> %s, supersample %d)' % (n, pr.size[0], pr.size[1], args.output_dir, args.src, args.dst, S))
 

@@ -187,14 +187,11 @@ class Renderer(object):
 
     def __init__(self, taps, zero_before=0, rotation=None, rot_hop=4800, device=None):
         import torch
-        from . import _lib
+        from . import ops
         taps = np.asarray(taps, np.float64)
         if taps.ndim != 3:
             raise ValueError('taps must be [outputs, channels, taps]')
-        _lib.lib()
-        if device is None:
-            device = 'cpu' if _lib.IS_CPU_TWIN else 'cuda'
-        self.device = torch.device(device)
+        self.device = ops.default_device(device)
         self.outputs, self.channels, self.ntaps = taps.shape
         self.taps = torch.as_tensor(taps.astype(np.float32)).contiguous().to(self.device)
         self.zero_before, self.rot_hop = int(zero_before), int(rot_hop)
@@ -265,11 +262,8 @@ def rendering_from_arguments(args, channels, rate, tool):
         quality = getattr(args, 'resample_hrir', None)
         device = None
         if quality is not None and hrir is not None and hrir.rate != int(rate):         # the one rendering that reaches the device here
-            from . import _lib
-            _lib.lib()
-            if not _lib.IS_CPU_TWIN:
-                import torch
-                torch.cuda.set_device(getattr(args, 'gpu', 0))                      # (what the caller does next anyway)
+            from . import ops
+            ops.select_device(getattr(args, 'gpu', 0))                              # (what the caller does next anyway)
         taps, zero_before = build_taps(args.render, order, rate, hrir=hrir, decode=args.decode, resample=quality, device=device)
     except (ValueError, IOError) as e:
         raise SystemExit('%s: %s' % (tool, e))
@@ -300,7 +294,7 @@ def parse_arguments(argv=None):
 def main(argv=None):
     """scripts/binauralize_ambisonics.py:8-20, streamed through a Renderer in blocks."""
     import torch
-    from . import _lib
+    from . import ops
     from .feeder import load_wav, save_wav
     args = parse_arguments(argv)
     if os.path.exists(args.output_fn) and not args.overwrite:
@@ -310,9 +304,7 @@ def main(argv=None):
     if args.block < 1:
         raise SystemExit('render: --block takes a positive count')
     taps, zero_before, rotation = rendering_from_arguments(args, data.shape[1], rate, 'render')      # host only: every refusal is behind us
-    _lib.lib()
-    if not _lib.IS_CPU_TWIN:
-        torch.cuda.set_device(args.gpu)
+    ops.select_device(args.gpu)
     r = Renderer(taps, zero_before, rotation)
     x = torch.as_tensor(data.astype(np.float32))
     out = [r.process(x[i:i + args.block].to(r.device)).cpu().numpy() for i in range(0, x.shape[0], args.block)]

@@ -129,14 +129,11 @@ class Resampler(object):
 
     def __init__(self, rate_in, rate_out, channels, mix=None, quality='best', device=None):
         import torch
-        from . import _lib
+        from . import ops
         self.L, self.M, self.H, taps = design(rate_in, rate_out, quality)
         self.channels = int(channels)
         self.outputs = self.channels
-        _lib.lib()
-        if device is None:
-            device = 'cpu' if _lib.IS_CPU_TWIN else 'cuda'
-        self.device = torch.device(device)
+        self.device = ops.default_device(device)
         self.taps = torch.as_tensor(taps).to(self.device)
         self.mix = None
         if mix is not None:
@@ -243,10 +240,8 @@ def window_powers(stored, starts, length, device=None):
     """RMS of channel 0 over the windows [start, start + length) of `stored` [n, C] (host, fp32-exact values) on the device: one
     ops.window_rms call per run of evenly spaced starts."""
     import torch
-    from . import _lib, ops
-    _lib.lib()
-    if device is None:
-        device = 'cpu' if _lib.IS_CPU_TWIN else 'cuda'
+    from . import ops
+    device = ops.default_device(device)
     x = torch.as_tensor(np.ascontiguousarray(stored[:, :1], np.float32)).to(device)
     out, i = [], 0
     while i < len(starts):
@@ -318,8 +313,7 @@ def parse_arguments(argv=None):
 
 
 def main(argv=None):
-    import torch
-    from . import _lib
+    from . import ops
     from .feeder import load_wav, save_wav
     args = parse_arguments(argv)
     tool = 'resample %s' % args.command
@@ -338,9 +332,7 @@ def main(argv=None):
             raise SystemExit('%s: %s already holds audio (--overwrite)' % (tool, args.clip_dir))
     data, rate_in = load_wav(args.input_fn)
     mix = mix_from_arguments(args, data.shape[1], tool)
-    _lib.lib()
-    if not _lib.IS_CPU_TWIN:
-        torch.cuda.set_device(args.gpu)
+    ops.select_device(args.gpu)
     if int(rate_in) == args.rate and mix is None:
         y = data.astype(np.float32)
     else:

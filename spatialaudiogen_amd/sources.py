@@ -92,13 +92,10 @@ class SourceScene(object):
 
     def __init__(self, signals, control_points, rate, device=None):
         import torch
-        from . import _lib, ops
+        from . import ops
         if len(signals) != len(control_points) or not len(signals):
             raise ValueError('SourceScene: one signal and one control-point array per source expected')
-        _lib.lib()
-        if device is None:
-            device = 'cpu' if _lib.IS_CPU_TWIN else 'cuda'
-        self.device, self.rate = torch.device(device), rate
+        self.device, self.rate = ops.default_device(device), rate
         sig = [np.asarray(s, np.float32).reshape(-1) for s in signals]
         pts = [np.asarray(p, np.float64).reshape(-1, 3) for p in control_points]
         placed = [k for k in range(len(sig)) if len(pts[k])]
@@ -316,16 +313,13 @@ def parse_arguments(argv=None):
 
 
 def main(argv=None):
-    import torch
-    from . import _lib
+    from . import ops
     args = parse_arguments(argv)
     if os.path.exists(args.output_fn) and not args.overwrite:
         raise SystemExit('sources: %s exists (--overwrite)' % args.output_fn)
     if getattr(args, 'ambi_order', 1) not in (1, 2):
         raise SystemExit('sources: ambisonic order %d is not supported (1 or 2)' % args.ambi_order)
-    _lib.lib()
-    if not _lib.IS_CPU_TWIN:
-        torch.cuda.set_device(args.gpu)
+    ops.select_device(args.gpu)
     if args.command == 'encode':
         out = run_encode(args)
     elif args.command.startswith('binauralize'):

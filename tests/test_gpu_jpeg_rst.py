@@ -355,6 +355,30 @@ def test_a_truncated_source_sets_its_decode_bits_and_leaves_its_neighbours_exact
     assert status[0] == _lib.SAGEN_JPEG_ENC_ST_CAPACITY << 8 and sizes[0] == len(want[0]) and status[1] & 255
 
 
+def test_transcode_of_a_plain_file_that_did_not_fit_is_redone_at_the_bound(monkeypatch):
+    """transcode_files' own guess of the stride never falls short on small files, so the block call is given 64 bytes here: the 16 x 16
+    noise file does not fit, the flat one does; the noise file is redone alone at the bound, and both files are those of the plain call."""
+    from spatialaudiogen_amd import jpeg
+    noise = np.random.RandomState(12).randint(0, 256, (16, 16, 3)).astype(np.uint8)
+    files = [JE.encode(noise, 95, '4:2:0'), JE.encode(np.full_like(noise, 90), 95, '4:2:0')]
+    want = jpeg.transcode_files(files, 1, _dev())
+    real, calls = jpeg.transcode_streams, []
+
+    def short(packed, staged, interval, stride):
+        """the first call's streams are cut at 64 bytes, in rows of the stride that was asked for"""
+        import torch
+        calls.append((packed.n, stride))
+        if len(calls) > 1:
+            return real(packed, staged, interval, stride)
+        out, sizes, status = real(packed, staged, interval, 64)
+        wide = torch.zeros((packed.n, stride), dtype=torch.uint8, device=out.device)
+        wide[:, :64] = out
+        return wide, sizes, status
+    monkeypatch.setattr(jpeg, 'transcode_streams', short)
+    assert jpeg.transcode_files(files, 1, _dev()) == want
+    assert [n for n, _ in calls] == [2, 1] and calls[1][1] >= len(plain_scan_of(want[0]))
+
+
 def test_transcode_on_the_device_equals_the_twin():
     """The four kinds of source above in calls on the device and, through the bare C ABI on numpy buffers, on the CPU twin: sizes,
     status and every byte.  (Needs the device; through the twin alone it would compare the twin with itself.)"""

@@ -24,7 +24,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, 'tests', 'golden', 'png_v1.npz')
 OP_CASES = ('test_filter_rows_equal_the_oracle or test_deflate_case or test_capacity_rule or test_refusals_leave_every_output_untouched or '
-            'test_recorded_streams_are_reproduced or test_encoder_files_open_in_pil')
+            'test_recorded_streams_are_reproduced or test_encoder_files_open_in_pil or test_encoder_retry_at_the_bound')
 POISON = PO.POISON
 B = PO.B
 FILTER_CASES = PO.filter_cases()
@@ -218,6 +218,15 @@ def test_encoder_files_open_in_pil():
                 _same_pixels(data, frames[f])
     assert png.PngEncoder(_dev()).encode(_t(FILTER_CASES['rgb_3x5'][:0])) == []
     assert len(png.png_file(3, 2, 3, b'')) == 57
+
+
+def test_encoder_retry_at_the_bound_gives_the_files_of_the_bound():
+    """Two 8 x 8 noise frames need about 200 bytes each: at stride 16 both are redone alone, and the files are those of stride None."""
+    from spatialaudiogen_amd import png
+    frames = _t(np.random.RandomState(11).randint(0, 256, (2, 8, 8, 3)).astype(np.uint8))
+    status = png.deflate(png.filter_rows(frames), 16)[2]
+    assert status.tolist() == [1, 1]
+    assert png.PngEncoder(_dev(), stride=16).encode(frames) == png.PngEncoder(_dev()).encode(frames)
 
 
 # ---- a flagship-sized call (needs the device) ------------------------------------------------------------------------------------------

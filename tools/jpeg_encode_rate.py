@@ -1,6 +1,6 @@
 """Frames per second of the ways to turn frames that are ON THE DEVICE into JPEG files' bytes on the host, on the same frames and box:
 
-  host_1      frames.cpu().numpy() + PIL's save into memory, one thread: what project / flow do by default (save_frames)
+  host_1      frames.cpu().numpy() + PIL's save into memory, one thread: what project / flow do by default (frames.FrameWriter, encode='host')
   host_16     the same copy, then PIL's save in a pool of 16 threads (PIL releases the GIL while it encodes)
   device      jpeg.JpegEncoder.encode (csrc/jpeg_enc.hip) in blocks of 16, 64, 256 and 640 frames, up to the bytes on the host
 

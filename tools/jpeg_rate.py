@@ -1,6 +1,6 @@
 """Frames per second of the three ways to get a folder of JPEG frames onto the device, on the same files and the same box:
 
-  host_1      overlay.load_frames (PIL, one thread) + .to(device): what project / flow / overlay do by default
+  host_1      frames.load_frames (PIL, one thread) + .to(device): what project / flow / overlay do by default
   host_16     the same PIL decode in a pool of 16 threads (PIL releases the GIL while it decodes) + .to(device)
   device      jpeg.JpegDecoder.decode (csrc/jpeg.hip): the files' bytes go to the device, blocks of 64 frames (16 for the large size)
 
@@ -108,7 +108,7 @@ def measure(name, n, repeats, tmp, more_blocks=()):
     from concurrent.futures import ThreadPoolExecutor
     from spatialaudiogen_amd import jpeg
     from spatialaudiogen_amd.feeder import imread
-    from spatialaudiogen_amd.overlay import load_frames
+    from spatialaudiogen_amd.frames import load_frames
     h, w, block = SIZES[name]
     folder = os.path.join(tmp, name)
     os.makedirs(folder)

@@ -68,7 +68,7 @@ def measure_decode(folders, n, repeats, blocks):
     from jpeg_rate import device_split, rate, timed
     from spatialaudiogen_amd import jpeg
     from spatialaudiogen_amd.feeder import imread
-    from spatialaudiogen_amd.overlay import load_frames
+    from spatialaudiogen_amd.frames import load_frames
     pool = ThreadPoolExecutor(16)
     dec = jpeg.JpegDecoder('cuda')
     keep, lines = {}, []

@@ -1,6 +1,6 @@
 """Frames per second of the ways to turn frames that are ON THE DEVICE into PNG files' bytes on the host, on the same frames and box:
 
-  host_1      frames.cpu().numpy() + PIL's save into memory, one thread: what overlay / deploy --overlay_dir do by default (save_frames)
+  host_1      frames.cpu().numpy() + PIL's save into memory, one thread: what overlay / deploy --overlay_dir do by default (frames.FrameWriter, encode='host')
   host_16     the same copy, then PIL's save in a pool of 16 threads (PIL releases the GIL while zlib runs)
   device      png.PngEncoder.encode (csrc/png.hip) in blocks of 16, 50, 64 and 256 frames, up to the bytes on the host
 
