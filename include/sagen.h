@@ -580,6 +580,35 @@ int sagen_jpeg_decode(const uint8_t* bytes, int64_t total_bytes, const sagen_jpe
                       int n_segments, const uint16_t* qtabs, int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, int w, int h,
                       int components, int hs, int vs, uint8_t* out, int32_t* status, void* scratch, size_t scratch_bytes, void* stream);
 
+/* ---- baseline JPEG decode, scans without restart markers on many lanes ---------------------------------------------------------
+ * sagen_jpeg_decode_split takes every argument of sagen_jpeg_decode, in the same order, and writes EXACTLY the out and status that
+ * call writes for them, hostile input included.  Its entropy stage cuts every restart segment - the whole scan of a file without
+ * an interval - into chunks of chunk_bytes bytes with one lane per chunk; the lanes find their entry states by self-synchronisation
+ * of the Huffman stream in `rounds` passes (csrc/jpeg_split_core.h has the algorithm and the argument for the guarantee).
+ *   chunk_bytes  bytes of scan per lane: a multiple of 4 in [16, 65536]
+ *   rounds       synchronisation passes, [1, 64]; rounds >= the chunks of the longest segment always settles
+ *   max_chunks   capacity of the chunk tables in the scratch, n_segments <= max_chunks <= 2^31 - 1; a segment of L bytes has
+ *                max(1, ceil(L / chunk_bytes)) chunks, and segments are placed in the order of their rows
+ *   path         [n] int32 DEVICE, may be null: who produced the frame's coefficients.  0: the split path (also a frame the
+ *                descriptor check refused: nothing decodes it).  Otherwise the frame was zeroed again and decoded by one lane per
+ *                segment, as sagen_jpeg_decode does it, because (the first that applies) its chunks did not fit max_chunks
+ *                (CAPACITY), a chunk was not synchronised after `rounds` passes (UNSETTLED), or the split path met anything the
+ *                one-lane path would report, or an inconsistency of its own (ANOMALY).  A deterministic function of the arguments.
+ * Returns: as sagen_jpeg_decode; SAGEN_ERR_SHAPE also for chunk_bytes, rounds or max_chunks outside their ranges and a path that is
+ * not 4-byte aligned; SAGEN_ERR_WORKSPACE for scratch smaller than sagen_jpeg_decode_split_scratch_bytes(...), which is 0 for a call
+ * that would be refused.  n == 0 SAGEN_OK, nothing touched.  A refused call writes nothing.  No host synchronisation, no allocation;
+ * the number of launches depends on the arguments only. */
+enum {
+    SAGEN_JPEG_PATH_UNSETTLED = 1,
+    SAGEN_JPEG_PATH_ANOMALY = 2,
+    SAGEN_JPEG_PATH_CAPACITY = 4
+};
+size_t sagen_jpeg_decode_split_scratch_bytes(int n, int w, int h, int components, int hs, int vs, int n_hufftabs, int n_segments, int64_t max_chunks);
+int sagen_jpeg_decode_split(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_frame* frames, int n, const int32_t* segments,
+                            int n_segments, const uint16_t* qtabs, int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, int w, int h,
+                            int components, int hs, int vs, uint8_t* out, int32_t* status, void* scratch, size_t scratch_bytes, void* stream,
+                            int chunk_bytes, int rounds, int64_t max_chunks, int32_t* path);
+
 /* ---- baseline JPEG encode ---------------------------------------------------------------------------------------------------
  * The reference gets its frame folders from ffmpeg's "%06d.jpg" extraction (scraping/preprocess.py:183-196) and leaves every later
  * frame write to the host's libjpeg.  sagen_jpeg_encode takes n frames on the device and writes the ENTROPY-CODED DATA of each,

@@ -12,6 +12,7 @@ SAGEN_SOURCES_MIC, SAGEN_SOURCES_HRIR = 0, 1
 SAGEN_PROJ_ER, SAGEN_PROJ_CUBE, SAGEN_PROJ_EAC, SAGEN_PROJ_VIEW = 0, 1, 2, 3
 SAGEN_JPEG_ENC_ST_CAPACITY, SAGEN_JPEG_ENC_ST_RANGE = 1, 2
 SAGEN_DEFLATE_ST_CAPACITY = 1
+SAGEN_JPEG_PATH_UNSETTLED, SAGEN_JPEG_PATH_ANOMALY, SAGEN_JPEG_PATH_CAPACITY = 1, 2, 4
 SAGEN_JPEG_STATUS = {1: 'overrun', 2: 'code', 4: 'index', 8: 'marker', 16: 'descriptor', 32: 'table', 64: 'range', 128: 'trailing'}
 
 
@@ -125,6 +126,8 @@ SIGNATURES = {
     'sagen_resample_fir': (C.c_int, [_P, _I64, _I64, _I, _P, _I, _I, _I, _I, _P, _I, _I64, _I64, _P, _P]),
     'sagen_jpeg_decode_scratch_bytes': (_SZ, [_I] * 7),
     'sagen_jpeg_decode': (C.c_int, [_P, _I64, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P]),
+    'sagen_jpeg_decode_split_scratch_bytes': (_SZ, [_I] * 8 + [_I64]),
+    'sagen_jpeg_decode_split': (C.c_int, [_P, _I64, _P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _SZ, _P, _I, _I, _I64, _P]),
     'sagen_jpeg_encode_scratch_bytes': (_SZ, [_I] * 6 + [_I64]),
     'sagen_jpeg_encode_max_bytes': (_I64, [_I] * 5),
     'sagen_jpeg_encode': (C.c_int, [_P, _I, _I, _I, _I, _I, _I, _P, _P, _I64, _P, _P, _P, _SZ, _P]),

@@ -6,6 +6,7 @@
 #include "op_entries_audio.h"  // sagen_assemble_audio, likewise
 #include "op_entries_png.h"    // sagen_png_filter, sagen_deflate, likewise
 #include "op_entries_jpeg_rst.h"   // sagen_jpeg_encode_rst, likewise
+#include "op_entries_jpeg_split.h" // sagen_jpeg_decode_split, likewise
 #include <new>
 #include <cstdlib>
 #include <algorithm>

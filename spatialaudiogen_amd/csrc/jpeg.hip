@@ -59,6 +59,24 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
     if (st) atomicOr(&status[f], (int32_t)st);
 }
 
+// the same for the frames sagen_jpeg_decode_split decodes again (jpeg_split.hip): gate[f] != 0, written launches ago and zeroed since
+__global__ __launch_bounds__(64) void jpeg_entropy_redo_kernel(const uint8_t* __restrict__ bytes, const sagen_jpeg_frame* __restrict__ frames,
+                                                               const int32_t* __restrict__ segments, int n_segments, int lanes, const JpegGeom g,
+                                                               const JpegHuff* __restrict__ huff, int16_t* __restrict__ coef, int32_t* status,
+                                                               const int32_t* __restrict__ gate) {
+    if ((int)threadIdx.x >= lanes) return;
+    const long long s = (long long)blockIdx.x * lanes + threadIdx.x;
+    if (s >= n_segments) return;
+    const int f = segments[2 * s];
+    if (f < 0 || f >= g.n || !gate[f]) return;
+    if (__hip_atomic_load(&status[f], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & (SAGEN_JPEG_ST_DESC | SAGEN_JPEG_ST_TABLE)) return;
+    const sagen_jpeg_frame& fr = frames[f];
+    const long long k = s - fr.first_segment;
+    if (k < 0 || k >= fr.n_segments) return;
+    const uint32_t st = jpeg_decode_segment(bytes, fr, segments, (int)k, g, huff, coef + (size_t)f * g.blocks * 64);
+    if (st) atomicOr(&status[f], (int32_t)st);
+}
+
 __global__ __launch_bounds__(JPEG_THREADS) void jpeg_idct_kernel(const int16_t* __restrict__ coef, const sagen_jpeg_frame* __restrict__ frames,
                                                                  const uint16_t* __restrict__ qtabs, const JpegGeom g,
                                                                  const int32_t* __restrict__ status, uint8_t* __restrict__ planes) {
@@ -97,16 +115,25 @@ __global__ __launch_bounds__(JPEG_THREADS) void jpeg_pixel_kernel(const uint8_t*
 
 }  // namespace
 
-// The first three stages: the tables, the check and the entropy decode into the natural-order coefficients (zeroed here).
-// sagen_jpeg_transcode (jpeg_enc.hip) stops behind them; n_qtabs bounds the descriptors' table indices and nothing else.
-int jpeg_coefficients_launch(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_frame* frames, const int32_t* segments, int n_segments,
-                             int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, const JpegGeom& g, JpegHuff* huff, int16_t* coef, int32_t* status,
-                             void* stream) {
+// The first stages: zeroed coefficients, the derived tables, every frame's initial status.
+int jpeg_front_launch(int64_t total_bytes, const sagen_jpeg_frame* frames, const int32_t* segments, int n_segments, int n_qtabs, const uint8_t* hufftabs,
+                      int n_hufftabs, const JpegGeom& g, JpegHuff* huff, int16_t* coef, int32_t* status, void* stream) {
     const hipStream_t s = (hipStream_t)stream;
     SAGEN_HIP_CHECK(hipMemsetAsync(coef, 0, (size_t)g.n * g.blocks * 64 * sizeof(int16_t), s));
     hipLaunchKernelGGL(jpeg_tables_kernel, dim3(cdiv(n_hufftabs, 64)), dim3(64), 0, s, hufftabs, huff, n_hufftabs);
     hipLaunchKernelGGL(jpeg_check_kernel, dim3(cdiv(g.n, 64)), dim3(64), 0, s, frames, segments, n_segments, total_bytes, n_qtabs, n_hufftabs, g,
                        huff, status);
+    return SAGEN_OK;
+}
+
+// The three stages in front of the inverse DCT: the tables, the check and the entropy decode into the natural-order coefficients (zeroed
+// here).  sagen_jpeg_transcode (jpeg_enc.hip) stops behind them; n_qtabs bounds the descriptors' table indices and nothing else.
+int jpeg_coefficients_launch(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_frame* frames, const int32_t* segments, int n_segments,
+                             int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, const JpegGeom& g, JpegHuff* huff, int16_t* coef, int32_t* status,
+                             void* stream) {
+    const hipStream_t s = (hipStream_t)stream;
+    const int rc = jpeg_front_launch(total_bytes, frames, segments, n_segments, n_qtabs, hufftabs, n_hufftabs, g, huff, coef, status, stream);
+    if (rc != SAGEN_OK) return rc;
     int lanes = cdiv(n_segments, JPEG_ENTROPY_WAVES);
     lanes = lanes > 64 ? 64 : lanes;
     hipLaunchKernelGGL(jpeg_entropy_kernel, dim3(cdiv(n_segments, lanes)), dim3(64), 0, s, bytes, frames, segments, n_segments, lanes, g, huff,
@@ -114,22 +141,38 @@ int jpeg_coefficients_launch(const uint8_t* bytes, int64_t total_bytes, const sa
     return SAGEN_OK;
 }
 
-int run_jpeg_decode(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_frame* frames, const int32_t* segments, int n_segments,
-                    const uint16_t* qtabs, int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, const JpegGeom& g, uint8_t* out,
-                    int32_t* status, void* scratch, void* stream) {
+// one lane per segment of the frames with gate[f] != 0 (sagen_jpeg_decode_split's redo)
+int jpeg_entropy_redo_launch(const uint8_t* bytes, const sagen_jpeg_frame* frames, const int32_t* segments, int n_segments, const JpegGeom& g,
+                             const JpegHuff* huff, int16_t* coef, int32_t* status, const int32_t* gate, void* stream) {
+    int lanes = cdiv(n_segments, JPEG_ENTROPY_WAVES);
+    lanes = lanes > 64 ? 64 : lanes;
+    hipLaunchKernelGGL(jpeg_entropy_redo_kernel, dim3(cdiv(n_segments, lanes)), dim3(64), 0, (hipStream_t)stream, bytes, frames, segments, n_segments,
+                       lanes, g, huff, coef, status, gate);
+    return SAGEN_OK;
+}
+
+// the inverse DCT into the planes, upsampling and colour into out
+int jpeg_back_launch(const sagen_jpeg_frame* frames, const uint16_t* qtabs, const JpegGeom& g, const int16_t* coef, const int32_t* status, uint8_t* planes,
+                     uint8_t* out, void* stream) {
     const hipStream_t s = (hipStream_t)stream;
-    const JpegScratch lay = jpeg_scratch_layout(g, n_hufftabs);
-    JpegHuff* huff = (JpegHuff*)((char*)scratch + lay.huff);
-    int16_t* coef = (int16_t*)((char*)scratch + lay.coef);
-    uint8_t* planes = (uint8_t*)scratch + lay.planes;
-    const int rc = jpeg_coefficients_launch(bytes, total_bytes, frames, segments, n_segments, n_qtabs, hufftabs, n_hufftabs, g, huff, coef, status, stream);
-    if (rc != SAGEN_OK) return rc;
     hipLaunchKernelGGL(jpeg_idct_kernel, dim3(cdiv((long)g.n * g.blocks, JPEG_THREADS)), dim3(JPEG_THREADS), 0, s, coef, frames, qtabs, g, status,
                        planes);
     hipLaunchKernelGGL(jpeg_pixel_kernel, dim3(cdiv((long)g.w * g.h, JPEG_THREADS), g.n < JPEG_GRID_FRAMES ? g.n : JPEG_GRID_FRAMES),
                        dim3(JPEG_THREADS), 0, s, planes, g, out);
     SAGEN_LAUNCH_CHECK();
     return SAGEN_OK;
+}
+
+int run_jpeg_decode(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_frame* frames, const int32_t* segments, int n_segments,
+                    const uint16_t* qtabs, int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, const JpegGeom& g, uint8_t* out,
+                    int32_t* status, void* scratch, void* stream) {
+    const JpegScratch lay = jpeg_scratch_layout(g, n_hufftabs);
+    JpegHuff* huff = (JpegHuff*)((char*)scratch + lay.huff);
+    int16_t* coef = (int16_t*)((char*)scratch + lay.coef);
+    uint8_t* planes = (uint8_t*)scratch + lay.planes;
+    const int rc = jpeg_coefficients_launch(bytes, total_bytes, frames, segments, n_segments, n_qtabs, hufftabs, n_hufftabs, g, huff, coef, status, stream);
+    if (rc != SAGEN_OK) return rc;
+    return jpeg_back_launch(frames, qtabs, g, coef, status, planes, out, stream);
 }
 
 }  // namespace sagen

@@ -391,23 +391,30 @@ JPEG_FN void jpeg_pixel(const JpegGeom& g, const uint8_t* planes, int x, int y, 
 
 // ---- the whole decode as plain loops on host pointers (the CPU twin and tools/jpeg_mutate.cpp; jpeg.hip runs the same five
 // stages as kernels) ----------------------------------------------------------------------------------------------------------------
-inline void jpeg_decode_host(const uint8_t* bytes, long long total_bytes, const sagen_jpeg_frame* frames, const int32_t* segments, int n_segments,
-                             const uint16_t* qtabs, int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, const JpegGeom& g, uint8_t* out,
-                             int32_t* status, void* scratch) {
-    const JpegScratch lay = jpeg_scratch_layout(g, n_hufftabs);
-    JpegHuff* huff = (JpegHuff*)((char*)scratch + lay.huff);
-    int16_t* coef = (int16_t*)((char*)scratch + lay.coef);
-    uint8_t* planes = (uint8_t*)scratch + lay.planes;
-    for (size_t i = 0; i < (lay.planes - lay.coef) / sizeof(int16_t); ++i) coef[i] = 0;
+// the first stages: zeroed coefficients, the derived tables, every frame's initial status
+inline void jpeg_front_host(long long total_bytes, const sagen_jpeg_frame* frames, const int32_t* segments, int n_segments, int n_qtabs,
+                            const uint8_t* hufftabs, int n_hufftabs, const JpegGeom& g, JpegHuff* huff, int16_t* coef, int32_t* status) {
+    for (size_t i = 0; i < (size_t)g.n * g.blocks * 64; ++i) coef[i] = 0;
     for (int t = 0; t < n_hufftabs; ++t) jpeg_huff_build(hufftabs + (size_t)t * JPEG_HUFF_SPEC, huff[t]);
     for (int f = 0; f < g.n; ++f) status[f] = (int32_t)jpeg_check_frame(frames[f], f, segments, n_segments, total_bytes, n_qtabs, n_hufftabs, g, huff);
+}
+
+// one lane per segment; gate (may be null): only the frames whose gate[f] is not 0
+inline void jpeg_entropy_host(const uint8_t* bytes, const sagen_jpeg_frame* frames, const int32_t* segments, int n_segments, const JpegGeom& g,
+                              const JpegHuff* huff, int16_t* coef, int32_t* status, const int32_t* gate) {
     for (int s = 0; s < n_segments; ++s) {
         const int f = segments[2 * (size_t)s];
         if (f < 0 || f >= g.n || (status[f] & (SAGEN_JPEG_ST_DESC | SAGEN_JPEG_ST_TABLE))) continue;
+        if (gate && !gate[f]) continue;
         const long long k = (long long)s - frames[f].first_segment;
         if (k < 0 || k >= frames[f].n_segments) continue;
         status[f] |= (int32_t)jpeg_decode_segment(bytes, frames[f], segments, (int)k, g, huff, coef + (size_t)f * g.blocks * 64);
     }
+}
+
+// inverse DCT into the planes, upsampling and colour into out
+inline void jpeg_back_host(const sagen_jpeg_frame* frames, const uint16_t* qtabs, const JpegGeom& g, const int16_t* coef, const int32_t* status,
+                           uint8_t* planes, uint8_t* out) {
     for (int f = 0; f < g.n; ++f) {
         if (status[f] & SAGEN_JPEG_ST_DESC) continue;
         uint8_t* fp = planes + (size_t)f * g.plane_bytes;
@@ -423,6 +430,18 @@ inline void jpeg_decode_host(const uint8_t* bytes, long long total_bytes, const 
         for (int y = 0; y < g.h; ++y)
             for (int x = 0; x < g.w; ++x) jpeg_pixel(g, fp, x, y, out + (((size_t)f * g.h + y) * g.w + x) * 3);
     }
+}
+
+inline void jpeg_decode_host(const uint8_t* bytes, long long total_bytes, const sagen_jpeg_frame* frames, const int32_t* segments, int n_segments,
+                             const uint16_t* qtabs, int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, const JpegGeom& g, uint8_t* out,
+                             int32_t* status, void* scratch) {
+    const JpegScratch lay = jpeg_scratch_layout(g, n_hufftabs);
+    JpegHuff* huff = (JpegHuff*)((char*)scratch + lay.huff);
+    int16_t* coef = (int16_t*)((char*)scratch + lay.coef);
+    uint8_t* planes = (uint8_t*)scratch + lay.planes;
+    jpeg_front_host(total_bytes, frames, segments, n_segments, n_qtabs, hufftabs, n_hufftabs, g, huff, coef, status);
+    jpeg_entropy_host(bytes, frames, segments, n_segments, g, huff, coef, status, nullptr);
+    jpeg_back_host(frames, qtabs, g, coef, status, planes, out);
 }
 
 }  // namespace sagen

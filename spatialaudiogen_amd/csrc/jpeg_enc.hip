@@ -30,49 +30,17 @@
 // tools/jpeg_encode_rate.py measures the stages; DESIGN.md says what they cost.
 #include "kernels.h"
 #include "jpeg_enc_core.h"
-#include "wave_reduce.h"
+#include "group_scan.h"
 
 namespace sagen {
 
 namespace {
 
 constexpr int ENC_THREADS = 256;
-constexpr int ENC_WAVES = ENC_THREADS / 64;
+constexpr int ENC_WAVES = SCAN_WAVES;               // (group_scan.h: the scans are over workgroups of ENC_THREADS)
 constexpr int ENC_WORDS = 56;                      // (31 + 1660 + 7 fill bits) / 32: 54 words; the last lane starts in word 52 at most and reaches two further
 
 __constant__ JpegEncHuff c_enc_huff = jpeg_enc_huff_make();
-
-// exclusive prefix sum over the 64 lanes (pre) and the wave's sum (tot), by the butterfly of wave_reduce.h: after the step of mask M
-// tot is the sum of the lane's aligned group of 2 M lanes, and the lanes of its upper half have added the lower half's sum
-template <int M = 1>
-__device__ __forceinline__ void wave_scan(int lane, int& pre, int& tot) {
-    if constexpr (M < 64) {
-        int a, b;
-        lane_pair<M>(tot, a, b);
-        const int other = a + b - tot;
-        if (lane & M) pre += other;
-        tot = a + b;
-        wave_scan<M * 2>(lane, pre, tot);
-    }
-}
-
-// the same over the 256 threads of a workgroup; lds: ENC_WAVES ints, free again on return
-__device__ __forceinline__ int group_scan(int v, int* lds, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int pre = 0, tot = v;
-    wave_scan(lane, pre, tot);
-    if (lane == 0) lds[wave] = tot;
-    __syncthreads();
-    int base = 0;
-    total = 0;
-    for (int i = 0; i < ENC_WAVES; ++i) {
-        const int t = lds[i];
-        base += i < wave ? t : 0;
-        total += t;
-    }
-    __syncthreads();
-    return base + pre;
-}
 
 __global__ __launch_bounds__(64) void jpeg_enc_init_kernel(const uint16_t* __restrict__ qtabs, const JpegEncGeom g, int32_t* __restrict__ qok,
                                                            int32_t* __restrict__ status) {

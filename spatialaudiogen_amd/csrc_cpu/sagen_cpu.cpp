@@ -28,6 +28,7 @@
 #include "../csrc/op_entries_audio.h"
 #include "../csrc/op_entries_png.h"
 #include "../csrc/op_entries_jpeg_rst.h"
+#include "../csrc/op_entries_jpeg_split.h"
 #include "../csrc/stft_frames.h"
 
 namespace {
@@ -740,6 +741,16 @@ int run_jpeg_decode(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_
                     const uint16_t* qtabs, int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, const JpegGeom& g, uint8_t* out,
                     int32_t* status, void* scratch, void*) {
     jpeg_decode_host(bytes, total_bytes, frames, segments, n_segments, qtabs, n_qtabs, hufftabs, n_hufftabs, g, out, status, scratch);
+    return SAGEN_OK;
+}
+
+/* The same with the entropy stage of a segment on many lanes (include/sagen.h: sagen_jpeg_decode_split): the stages of
+ * csrc/jpeg_split.hip in their order as plain loops (csrc/jpeg_split_core.h: jpeg_split_decode_host), the same rounds, the same path */
+int run_jpeg_decode_split(const uint8_t* bytes, int64_t total_bytes, const sagen_jpeg_frame* frames, const int32_t* segments, int n_segments,
+                          const uint16_t* qtabs, int n_qtabs, const uint8_t* hufftabs, int n_hufftabs, const JpegGeom& g, uint8_t* out, int32_t* status,
+                          void* scratch, void*, int chunk_bytes, int rounds, int64_t max_chunks, int32_t* path) {
+    jpeg_split_decode_host(bytes, total_bytes, frames, segments, n_segments, qtabs, n_qtabs, hufftabs, n_hufftabs, g, out, status, scratch, chunk_bytes,
+                           rounds, max_chunks, path);
     return SAGEN_OK;
 }
 

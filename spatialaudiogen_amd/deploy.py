@@ -155,10 +155,12 @@ class W2XYZ(object):
     # The model sees the same bits either way; a ClipArrays source holds decoded arrays already and ignores this
     decode = 'host'
 
-    def __init__(self, model_dir=None, params=None, variables=None, device=None, decode='host'):
+    def __init__(self, model_dir=None, params=None, variables=None, device=None, decode='host', entropy='lane'):
         if decode not in ('host', 'device'):
             raise ValueError("decode must be 'host' or 'device', not %r" % (decode,))
-        self.decode = decode
+        from .frames import check_entropy
+        check_entropy(None, decode, entropy)
+        self.decode, self.entropy = decode, entropy      # entropy: the device decoder's 'lane' or 'split' (jpeg.JpegDecoder)
         if params is None:
             params = load_params(model_dir)
         self.params = params
@@ -274,10 +276,10 @@ class W2XYZ(object):
             adev = DeviceAudio(os.path.join(input_folder, 'ambix'), p.audio_rate, p.ambi_order, device=m.device)
             wanted = [frame_index(t, p.video_rate) for t in reader.chunks_t]
             if use_v or overlay is not None:
-                vdev = DeviceFrames(os.path.join(input_folder, 'video'), 'video', device=m.device, rate=p.video_rate)
+                vdev = DeviceFrames(os.path.join(input_folder, 'video'), 'video', device=m.device, rate=p.video_rate, entropy=self.entropy)
                 vdev.ensure(min(wanted), max(wanted) + 1)
             if use_f:
-                fdev = DeviceFrames(os.path.join(input_folder, 'flow'), 'flow', device=m.device, rate=p.video_rate)
+                fdev = DeviceFrames(os.path.join(input_folder, 'flow'), 'flow', device=m.device, rate=p.video_rate, entropy=self.entropy)
                 fdev.ensure(min(wanted), max(wanted) + 1)
 
         def next_chunk():
@@ -426,6 +428,8 @@ def parse_arguments(argv=None):
                              "the files' bytes go to the device, jpeg.py decodes and every batch is assembled there; same output, bit for bit).  "
                              'projection | pseudoinv: the decoder of --render ears (default pseudoinv) / speakers (default projection)')
     parser.set_defaults(frame_decode='host')
+    from .frames import ENTROPY_HELP
+    parser.add_argument('--entropy', default='lane', choices=['lane', 'split'], help=ENTROPY_HELP)
     parser.add_argument('--render_fn', default=None, help='Output wav of --render.')
     parser.add_argument('--overlay_dir', default=None, metavar='DIR',
                         help='paint the sound-direction heat map over the frames of <input_folder>/video and write them here as %%06d.png (overlay.py)')
@@ -452,6 +456,8 @@ def main(argv=None):
     from .feeder import save_wav
     from . import render
     args = parse_arguments(argv)
+    from .frames import check_entropy
+    check_entropy('deploy', args.frame_decode, args.entropy)
     params = load_params(args.model_dir)
     require_first_order(params.ambi_order, 'deploy')
     render.check_render_arguments(args, 4, 'deploy')
@@ -461,7 +467,7 @@ def main(argv=None):
         frames.prepare_output_dir(args.overlay_dir, args.overwrite, 'deploy')
     torch.cuda.set_device(args.gpu)
     renderer = render.Renderer(*rendering) if rendering else None
-    model = W2XYZ(args.model_dir, decode=args.frame_decode)
+    model = W2XYZ(args.model_dir, decode=args.frame_decode, entropy=args.entropy)
     model.groups = max(1, args.groups)
     painted = None
     if args.overlay_dir:

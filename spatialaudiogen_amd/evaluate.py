@@ -223,7 +223,7 @@ class DeviceFeed(object):
     goes in as decoded (uint8); flow through sagen_assemble_frames mode 2 with the scale_lo rows of those frames; a zero-padded
     partial batch through modes 1 / 2 with padding indices (0.0 after normalisation)."""
 
-    def __init__(self, db_dir, params, device, keep=2):
+    def __init__(self, db_dir, params, device, keep=2, entropy='lane'):
         import torch
         from .feeder import DeviceAudio, flow_table, video_table
         from .jpeg import JpegDecoder
@@ -233,7 +233,7 @@ class DeviceFeed(object):
         self.ss, self.t = int(params.audio_rate * params.context) // 2, int(params.audio_rate * 0.1)
         self.audio = _ReaderCache(lambda yid: DeviceAudio(os.path.join(db_dir, yid, 'ambix'), params.audio_rate, params.ambi_order,
                                                           device=device), keep)
-        self.decoder = JpegDecoder(device) if self.use_v or self.use_f else None
+        self.decoder = JpegDecoder(device, entropy=entropy) if self.use_v or self.use_f else None
         self._tables = {k: torch.as_tensor(np.ascontiguousarray(f(), dtype=np.float32)).to(device)
                         for k, f in (('video', video_table), ('flow', flow_table)) if (self.use_v if k == 'video' else self.use_f)}
         self._scale_lo = _ReaderCache(self._load_scale_lo, keep)
@@ -278,7 +278,7 @@ class DeviceFeed(object):
 
 
 def evaluate(model_dir, db_dir, subset_fn=None, layouts_fn=None, variables=None, params=None, overwrite=True,
-             partial_batch='drop', power_maps=False, groups=1, all_metrics=False, decode='host'):
+             partial_batch='drop', power_maps=False, groups=1, all_metrics=False, decode='host', entropy='lane'):
     """decode: 'host' (SampleReader: numpy windows, PIL frames, one upload per batch) or 'device' (DeviceFeed); the rows written are the
     same, line for line."""
     import torch
@@ -286,13 +286,15 @@ def evaluate(model_dir, db_dir, subset_fn=None, layouts_fn=None, variables=None,
     from .feeder import SampleReader
     if decode not in ('host', 'device'):
         raise ValueError("decode must be 'host' or 'device', not %r" % (decode,))
+    from .frames import check_entropy
+    check_entropy(None, decode, entropy)                     # ('split' belongs to the device decoder)
     rank, world = init_process_group()
     if torch.cuda.is_available():
         torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', 0)) % torch.cuda.device_count())
     params = params or load_params(model_dir)
     w2 = W2XYZ(model_dir, params=params, variables=variables)
     net = w2.model
-    feed = DeviceFeed(db_dir, params, net.device) if decode == 'device' else None
+    feed = DeviceFeed(db_dir, params, net.device, entropy=entropy) if decode == 'device' else None
     ids = [l.strip() for l in open(subset_fn)] if subset_fn else sorted(os.listdir(db_dir))
     ids = [i for i in ids if i and os.path.isdir(os.path.join(db_dir, i))]
     layouts = read_layouts(layouts_fn)
@@ -413,16 +415,20 @@ def arg_parser():
                          "(the clips' wav pieces stay on the device and sagen_assemble_audio cuts input and target there; the frame files' bytes go "
                          'up and jpeg.py decodes them); the same rows, line for line.  A decode call costs the same whatever it holds: measured, device is slower than '
                          'host below --groups 4 and faster from there on (README)')
+    from .frames import ENTROPY_HELP
+    ap.add_argument('--entropy', choices=['lane', 'split'], default='lane', help=ENTROPY_HELP)
     return ap
 
 
 def main(argv=None):
     args = arg_parser().parse_args(argv)
     from .deploy import load_params, require_first_order
+    from .frames import check_entropy
+    check_entropy('evaluate', args.decode, args.entropy)
     require_first_order(load_params(args.model_dir).ambi_order, 'evaluate')
     means, count = evaluate(args.model_dir, args.db_dir, args.subset_fn, args.layouts_fn, overwrite=args.overwrite,
                             partial_batch=args.partial_batch, power_maps=args.power_maps, groups=args.groups,
-                            all_metrics=args.all_metrics, decode=args.decode)
+                            all_metrics=args.all_metrics, decode=args.decode, entropy=args.entropy)
     if args.power_maps and evaluate.last_maps:
         maps = evaluate.last_maps                      # [pred, gt, pred, gt, ...] per batch, each [n, 7, 12]
         np.savez(os.path.join(args.model_dir, 'eval-powermaps-rank%d.npz' % int(os.environ.get('RANK', 0))),

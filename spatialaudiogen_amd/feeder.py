@@ -363,7 +363,7 @@ class DeviceFrames(object):
 
     RAW_RATE = JpgFrames.RAW_RATE
 
-    def __init__(self, folder, kind='video', device=None, decoder=None, block=256, rate=None, prep=None, flow_prep=None):
+    def __init__(self, folder, kind='video', device=None, decoder=None, block=256, rate=None, prep=None, flow_prep=None, entropy='lane'):
         import torch
         from . import ops
         if kind not in ('video', 'flow'):
@@ -387,7 +387,9 @@ class DeviceFrames(object):
         self.device = ops.default_device(device)
         if decoder is None:
             from .jpeg import JpegDecoder
-            decoder = JpegDecoder(self.device)
+            decoder = JpegDecoder(self.device, entropy=entropy)                 # ('split': many lanes per restart segment; same pixels)
+        elif entropy != 'lane' and getattr(decoder, 'entropy', 'lane') != entropy:
+            raise ValueError('entropy=%r, but the decoder handed in was made with another' % (entropy,))
         self.decoder = decoder
         self.first = self.stop = 0                                      # the resident range
         self._frames = torch.empty((0,) + self.frame_shape, dtype=torch.uint8, device=self.device)

@@ -93,11 +93,13 @@ class FlowEstimator(object):
         return ops.optical_flow(torch.cat([first, frames], 0), self.params.struct(h, w))
 
 
-def write_flow_folder(video_dir, flow_dir, params=None, block=64, fmt='jpg', device=None, decode='host', encode='host', restart_rows=0):
+def write_flow_folder(video_dir, flow_dir, params=None, block=64, fmt='jpg', device=None, decode='host', encode='host', restart_rows=0,
+                      entropy='lane'):
     """Flow folder of the frames %06d.jpg of video_dir: flow_dir/%06d.<fmt> + flow_dir/flow_limits.npy.  Returns (n, h, w, levels).
     decode 'device': the frames are decoded on the device (jpeg.load_frames_device) instead of by PIL on the host; same pixels.
     encode 'device' (jpg only): the flow frames are encoded on the device (jpeg.JpegEncoder) instead of by PIL on the host; same files.
-    restart_rows (jpg only): rows of MCUs per restart interval of the files written, 0 for none; same files either way."""
+    restart_rows (jpg only): rows of MCUs per restart interval of the files written, 0 for none; same files either way.
+    entropy (decode 'device' only): 'lane' or 'split', frames.FrameReader's option; same pixels."""
     if encode == 'device' and fmt != 'jpg':
         raise ValueError('encode=device writes jpg only (fmt=%s)' % fmt)
     from . import frames as F, ops
@@ -107,7 +109,7 @@ def write_flow_folder(video_dir, flow_dir, params=None, block=64, fmt='jpg', dev
     if not names:
         raise ValueError('%s holds no frame 000000.jpg' % video_dir)
     est = FlowEstimator(params, device)
-    reader = F.FrameReader(est.device, decode)
+    reader = F.FrameReader(est.device, decode, entropy)
     limits, prev, hw = [], None, None
     for first, stop in block_ranges(len(names), block):
         start = first if prev is None else first + 1
@@ -145,6 +147,7 @@ def main(argv=None):
         raise SystemExit('flow: --encode device writes jpg only (--format %s)' % args.format)
     if args.block < 1:
         raise SystemExit('flow: --block takes a positive value')
+    F.check_entropy('flow', args.decode, args.entropy)
     if not os.path.isdir(args.video_dir):
         raise SystemExit('flow: %s is not a folder' % args.video_dir)
     names = F.frame_names(args.video_dir)
@@ -162,7 +165,7 @@ def main(argv=None):
     from . import ops
     ops.select_device(args.gpu)
     n, h, w, levels = write_flow_folder(args.video_dir, args.flow_dir, params, args.block, args.format, decode=args.decode, encode=args.encode,
-                                          restart_rows=args.restart_rows)
+                                          restart_rows=args.restart_rows, entropy=args.entropy)
     print('wrote %d flow frames of %dx%d to %s (levels %d, warps %d, iters %d)' % (n, h, w, args.flow_dir, levels, params.warps, params.iters))
 
 

@@ -60,13 +60,15 @@ def prepare_output_dir(out_dir, overwrite, tool, extensions=('.png',), extras=()
 
 class FrameReader(object):
     """read(names) -> uint8 [n, h, w, 3] on `device`.  decode 'host': PIL, one thread, then one copy; 'device': the files' bytes go to the
-    device and jpeg.JpegDecoder decodes them there; the same pixels."""
+    device and jpeg.JpegDecoder decodes them there; the same pixels.  entropy ('device' only): 'lane', one lane per restart segment, or
+    'split', many lanes per segment (jpeg.JpegDecoder)."""
 
-    def __init__(self, device, decode='host'):
+    def __init__(self, device, decode='host', entropy='lane'):
         self.device, self.decoder = device, None
+        check_entropy(None, decode, entropy)
         if decode == 'device':
             from .jpeg import JpegDecoder
-            self.decoder = JpegDecoder(device)
+            self.decoder = JpegDecoder(device, entropy=entropy)
 
     def read(self, names):
         import torch
@@ -123,6 +125,10 @@ ENCODE_HELP = ("where the output frames are encoded (--format jpg only): host (P
                "(jpeg.py: only the files' bytes leave the device; the same files).  Measured on one MI355X, 224x448 at quality 95 (profiles/jpeg_encode_rate.jsonl): host 2 949 frames/s; device 44 575 in blocks of 16, "
                "91 255 in blocks of 64, 111 778 in blocks of 256: it pays from --block 16, the smallest measured, up.")
 
+ENTROPY_HELP = ("how --decode device reads a frame's entropy-coded data: lane (one lane per restart segment: one per frame for a file without "
+                "restart markers, which is every file ffmpeg or PIL writes by default) or split (many lanes per segment, which find their "
+                "places in the stream by themselves; the same pixels and the same errors).  Refused with --decode host.")
+
 RESTART_HELP = ("rows of MCUs (16 pixel rows at 4:2:0) per restart interval of the jpg files written, 0: none (--format jpg only).  The device "
                 "decoder (--decode device) runs one lane per restart segment, so it reads such a folder in parallel inside each frame; every "
                 "other reader sees the same pixels.  The same files with --encode host (PIL's restart_marker_rows) and --encode device.")
@@ -134,9 +140,23 @@ def add_frame_arguments(parser, block, encode_help=ENCODE_HELP, restart_rows=Fal
     parser.add_argument('--gpu', type=int, default=0, help='GPU id')
     parser.add_argument('--block', type=int, default=block, help=block_help)
     parser.add_argument('--decode', default='host', choices=['host', 'device'], help=DECODE_HELP)
+    parser.add_argument('--entropy', default='lane', choices=['lane', 'split'], help=ENTROPY_HELP)
     parser.add_argument('--encode', default='host', choices=['host', 'device'], help=encode_help)
     if restart_rows:
         parser.add_argument('--restart_rows', type=int, default=0, metavar='N', help=RESTART_HELP)
+
+
+def check_entropy(tool, decode, entropy):
+    """the refusals of --entropy, in front of any file (tool None: the same as ValueError, for the classes)"""
+    problem = None
+    if entropy not in ('lane', 'split'):
+        problem = "entropy must be 'lane' or 'split', not %r" % (entropy,)
+    elif entropy != 'lane' and decode != 'device':
+        problem = '--entropy %s belongs to --decode device (--decode %s decodes with PIL)' % (entropy, decode)
+    if problem and tool is None:
+        raise ValueError(problem)
+    if problem:
+        raise SystemExit('%s: %s' % (tool, problem))
 
 
 def check_restart_rows(tool, restart_rows, fmt, w):

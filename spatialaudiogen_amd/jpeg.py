@@ -6,6 +6,10 @@ the device gets the file bytes and produces [N, H, W, 3] uint8, byte for byte wh
     JpegDecoder(device).decode(items)   -> torch.uint8 [N, H, W, 3] on the device; items: bytes or paths
     load_frames_device(names, device)   the drop-in for torch.as_tensor(frames.load_frames(names)).to(device); frames.FrameReader chooses
 
+    JpegDecoder(device, entropy='split')  the same pixels with many lanes per frame (sagen_jpeg_decode_split, csrc/jpeg_split.hip): for files
+                                        without restart markers; chunk_bytes, rounds: its options; last_paths: who decoded the frames
+    split_chunks(packed, chunk_bytes)   the chunks of a packed call: the capacity decode_packed(entropy='split') asks for
+
 Scope (the header has the details): SOF0, 8 bit, Huffman, one interleaved scan, grey or YCbCr 4:4:4 / 4:2:2 / 4:2:0, optional
 restart interval.  A file outside it is decoded by feeder.imread and copied in, with one warning per decoder.
 
@@ -238,21 +242,72 @@ def pack(datas, infos, buffer_factory=None):
     return Packed(buf, size, total, at[0], len(infos), at[1], segs.shape[0], at[2], len(qindex), at[3], len(hindex), geometry)
 
 
-def decode_packed(packed, staged, out=None):
+ENTROPY = ('lane', 'split')
+SPLIT_CHUNK_BYTES, SPLIT_ROUNDS = 256, 8        # entropy='split' without further word: the defaults DESIGN.md's split table names
+
+
+def split_chunks(packed, chunk_bytes):
+    """The chunks sagen_jpeg_decode_split cuts the call `packed` into: max(1, ceil(bytes / chunk_bytes)) per restart segment (the whole
+    scan where there is no interval) - the smallest max_chunks at which no frame comes out CAPACITY."""
+    frames = packed.buffer[packed.frames_at:packed.frames_at + 64 * packed.n].view(FRAME_DTYPE)
+    rows = packed.buffer[packed.segments_at:packed.segments_at + 8 * packed.n_segments].view(np.int32).reshape(-1, 2)
+    total = 0
+    for fr in frames:
+        first, count = int(fr['first_segment']), int(fr['n_segments'])
+        starts = rows[first:first + count, 1].astype(np.int64)
+        ends = np.concatenate([starts[1:] - 2, [int(fr['scan_bytes'])]])
+        total += int(np.maximum(-(-(ends - starts) // int(chunk_bytes)), 1).sum())
+    return total
+
+
+def _entropy_options(entropy, chunk_bytes, rounds):
+    if entropy not in ENTROPY:
+        raise ValueError('entropy %r is none of %s' % (entropy, ', '.join(ENTROPY)))
+    if entropy == 'lane':
+        if chunk_bytes is not None or rounds is not None:
+            raise ValueError("chunk_bytes and rounds belong to entropy='split'")
+        return None, None
+    chunk_bytes = SPLIT_CHUNK_BYTES if chunk_bytes is None else int(chunk_bytes)
+    rounds = SPLIT_ROUNDS if rounds is None else int(rounds)
+    if chunk_bytes % 4 or not 16 <= chunk_bytes <= 65536:
+        raise ValueError('chunk_bytes %d is no multiple of 4 in [16, 65536]' % chunk_bytes)
+    if not 1 <= rounds <= 64:
+        raise ValueError('rounds %d is outside [1, 64]' % rounds)
+    return chunk_bytes, rounds
+
+
+def decode_packed(packed, staged, out=None, entropy='lane', chunk_bytes=None, rounds=None, want_path=False, max_chunks=None):
     """sagen_jpeg_decode on `staged`, the uint8 tensor holding packed.buffer where the library reads (device memory; the host with
-    the CPU twin).  Returns (out [n, h, w, 3] uint8, status [n] int32) on that device; nothing is synchronised."""
+    the CPU twin).  Returns (out [n, h, w, 3] uint8, status [n] int32) on that device; nothing is synchronised.
+    entropy='split': sagen_jpeg_decode_split with chunk_bytes bytes of scan per lane and `rounds` synchronisation passes (defaults
+    SPLIT_CHUNK_BYTES, SPLIT_ROUNDS), the same out and status; want_path adds path [n] int32 (who decoded each frame) as a third
+    value; max_chunks (default: split_chunks(packed, chunk_bytes), the exact count) is the capacity of the chunk tables."""
     import torch
     from .ops import _ptr, _scratch64, _stream
     l = _lib.lib()
+    chunk_bytes, rounds = _entropy_options(entropy, chunk_bytes, rounds)
+    if entropy == 'lane' and (want_path or max_chunks is not None):
+        raise ValueError("want_path and max_chunks belong to entropy='split'")
     w, h, comps, hs, vs = packed.geometry
     n = packed.n
     if out is None:
         out = torch.empty((n, h, w, 3), dtype=torch.uint8, device=staged.device)
     status = torch.empty(n, dtype=torch.int32, device=staged.device)
-    nbytes = int(l.sagen_jpeg_decode_scratch_bytes(n, w, h, comps, hs, vs, packed.n_hufftabs))
-    scratch = _scratch64(nbytes, staged.device)
     base = staged.data_ptr()
     at = lambda off: C.c_void_p(base + off)
+    if entropy == 'split':
+        if max_chunks is None:
+            max_chunks = split_chunks(packed, chunk_bytes)
+        path = torch.empty(n, dtype=torch.int32, device=staged.device) if want_path else None
+        nbytes = int(l.sagen_jpeg_decode_split_scratch_bytes(n, w, h, comps, hs, vs, packed.n_hufftabs, packed.n_segments, max_chunks))
+        scratch = _scratch64(nbytes, staged.device)
+        _lib.check(l.sagen_jpeg_decode_split(at(packed.bytes_at), packed.total_bytes, at(packed.frames_at), n, at(packed.segments_at),
+                                             packed.n_segments, at(packed.qtabs_at), packed.n_qtabs, at(packed.hufftabs_at), packed.n_hufftabs, w, h,
+                                             comps, hs, vs, _ptr(out), _ptr(status), _ptr(scratch), nbytes, _stream(), chunk_bytes, rounds, max_chunks,
+                                             _ptr(path) if want_path else None))
+        return (out, status, path) if want_path else (out, status)
+    nbytes = int(l.sagen_jpeg_decode_scratch_bytes(n, w, h, comps, hs, vs, packed.n_hufftabs))
+    scratch = _scratch64(nbytes, staged.device)
     _lib.check(l.sagen_jpeg_decode(at(packed.bytes_at), packed.total_bytes, at(packed.frames_at), n, at(packed.segments_at), packed.n_segments,
                                    at(packed.qtabs_at), packed.n_qtabs, at(packed.hufftabs_at), packed.n_hufftabs, w, h, comps, hs, vs,
                                    _ptr(out), _ptr(status), _ptr(scratch), nbytes, _stream()))
@@ -266,10 +321,16 @@ def status_text(code):
 class JpegDecoder(object):
     """decode(items) -> uint8 [N, H, W, 3] on the device, in the order of `items` (bytes objects or paths of files).  Frames of
     several geometries (sampling, grey / colour) are decoded a group at a time; all must have one size.  `timing`, when set to a
-    dict, receives 'parse' and 'pack' in host seconds of the last call."""
+    dict, receives 'parse' and 'pack' in host seconds of the last call.  entropy='split' decodes each restart segment - each frame of
+    a file without an interval - on many lanes (sagen_jpeg_decode_split; chunk_bytes, rounds: its options, default SPLIT_CHUNK_BYTES
+    and SPLIT_ROUNDS): the same pixels and the same errors.  last_paths then holds {path value: frames} of the last call (0: the split
+    path; the SAGEN_JPEG_PATH_* values: decoded again by one lane per segment), read with the status that comes back anyway."""
 
-    def __init__(self, device=None):
+    def __init__(self, device=None, entropy='lane', chunk_bytes=None, rounds=None):
         from .ops import default_device
+        self.chunk_bytes, self.rounds = _entropy_options(entropy, chunk_bytes, rounds)
+        self.entropy = entropy
+        self.last_paths = {}
         self.device = default_device(device)
         self._warned = False
         self.timing = None
@@ -318,14 +379,23 @@ class JpegDecoder(object):
             t_pack += time.perf_counter() - tp
             staged = self._pinned.to(self.device, non_blocking=True)             # the one copy of this group
             whole = idx == list(range(len(datas)))
-            got, status = decode_packed(packed, staged, out if whole else None)
+            if self.entropy == 'split':
+                got, status, path = decode_packed(packed, staged, out if whole else None, 'split', self.chunk_bytes, self.rounds, want_path=True)
+                status = torch.stack([status, path])                              # (one copy back for both)
+            else:
+                got, status = decode_packed(packed, staged, out if whole else None)
             if not whole:
                 out[torch.as_tensor(idx, device=self.device)] = got
             pending.append((idx, status, self._pinned))                           # (the staging buffer lives until the copy has run)
         for k in fallback:
             out[k] = torch.as_tensor(_host_decode(datas[k])).to(self.device)
+        self.last_paths = {}
         for idx, status, _ in pending:
             bad = status.cpu().numpy()
+            if bad.ndim == 2:
+                for v in bad[1].tolist():
+                    self.last_paths[v] = self.last_paths.get(v, 0) + 1
+                bad = bad[0]
             for j in np.flatnonzero(bad):
                 raise IOError('%s: the JPEG stream is damaged (%s)' % (names[idx[j]], status_text(int(bad[j]))))
         if self.timing is not None:

@@ -162,6 +162,7 @@ def main(argv=None):
     from . import frames as F
     from .feeder import load_wav
     args = parse_arguments(argv)
+    F.check_entropy('overlay', args.decode, args.entropy)
     data, rate = load_wav(args.input_fn)
     if data.shape[1] not in (4, 9):
         raise SystemExit('overlay: %d channels is not first- or second-order ambisonics (4 or 9)' % data.shape[1])
@@ -176,7 +177,7 @@ def main(argv=None):
     ops.select_device(args.gpu)
     ov = Overlay(data.shape[1], audio_rate=rate, angular_res=args.angular_res)
     ov.process(torch.as_tensor(data.astype(np.float32)).to(ov.device), None)
-    reader, writer = F.FrameReader(ov.device, args.decode), F.FrameWriter(args.output_dir, 'png', args.encode, ov.device)
+    reader, writer = F.FrameReader(ov.device, args.decode, args.entropy), F.FrameWriter(args.output_dir, 'png', args.encode, ov.device)
     written = 0
     for i in range(0, len(names), args.block):
         out = ov.process(None, reader.read(names[i:i + args.block]))

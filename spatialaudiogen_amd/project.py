@@ -251,6 +251,7 @@ def main(argv=None):
     from . import frames as F
     if args.encode == 'device' and args.format != 'jpg':
         raise SystemExit('project: --encode device writes jpg only (--format %s)' % args.format)
+    F.check_entropy('project', args.decode, args.entropy)
     F.check_restart_rows('project', args.restart_rows, args.format, args.size[1])
     if args.dst == 'view' and args.hfov is None:
         raise SystemExit('project: --to view needs --hfov')
@@ -281,7 +282,7 @@ def main(argv=None):
     turned = any(np.any(np.asarray(getattr(args, k)) != 0.) for k in ('yaw', 'pitch', 'roll'))
     rot = view_trajectory(frame_angles(args.yaw, n), frame_angles(args.pitch, n), frame_angles(args.roll, n)) if turned else None
     pr = Projector(src, dst, args.size, args.supersample)
-    reader = F.FrameReader(pr.device, args.decode)
+    reader = F.FrameReader(pr.device, args.decode, args.entropy)
     writer = F.FrameWriter(args.output_dir, args.format, args.encode, pr.device, args.restart_rows)
     for i in range(0, n, args.block):
         out = pr.process(reader.read(names[i:i + args.block]), None if rot is None else rot[i:i + args.block])
